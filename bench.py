@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- proposals/s of the MT-DREAM(ZS) hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one generation: every chain makes one MT-DREAM(ZS) transition (multitry proposals,
 reference set, Metropolis accept, Z append every `thin` generations).  Workload at N GPUs (weak
@@ -9,19 +9,27 @@ scaling, BASELINE.json north_star / configs[3]): 4096 chains per GPU on the 100-
 pydream/examples/ndim_gaussian, multitry=5, DE+snooker, reference defaults otherwise.  Inputs
 (seed archive, start states, precision matrix) are resident in HBM before the timed region.
 
-Sequence (every part but the timed blocks is untimed):
-  1. convergence run from the over-dispersed starts, in chunks, with the whole run traced on the device: after every
-     chunk R-hat (pydream/convergence.py:3-20: second half of the run so far) over all chains; reports the first
-     generation count at which max R-hat < 1.2 (the reference example's stopping rule, dream_ex_ndim_gaussian.py:80)
-     -- this also takes the GPU out of its idle clock state;
-  2. R-hat over a fixed window of --rhat-window generations after that (independent of --steps);
-  3. W warm-up generations, then blocks of EXACTLY K generations, each bracketed by barrier + device sync on both sides
-     and timed on its own (max over ranks), repeated until at least --min-timed-ms have been timed:
-     value = N k K / median block time (a single block at the default K lasts 30 ms, at K = 20 0.6 ms);
-  4. a pass of max(K, 200) generations with HIP events on every launch (per-kernel durations for the roofline: the median of
-     at least 20 launches of the persistent kernel, capped by what the timed blocks allow);
-  5. (one GPU) the same timed blocks with the reference example's own formula, the dense precision matrix: `dense_value`;
-  6. (rank 0) the CPU restatement on the host cores.
+A plain run does what the headline needs and nothing else (every part but step 3 is untimed):
+  1. set-up of the engine from the seeded inputs, then about 0.5 s of load on a throw-away engine of the same size to take the GPU
+     out of its idle clock state (the measured engine's run does not depend on it);
+  2. (--adapt) the crossover burn-in, run through untimed; W warm-up generations, then the 0..thin-1 more that end a thin-cycle;
+  3. EXACTLY K generations, bracketed by barrier + device sync on both sides and timed as one (max over ranks):
+     value = N k K / that time, ms_per_step = that time / K;
+  4. --dump-outputs DIR: what the K generations computed in their last one (see dump_outputs), as DIR/<name>.npy.
+The same inputs and arguments give the same outputs: a plain run's dump compares two builds output for output.
+
+--full adds every other measurement (what the line carried before this option existed):
+  a. before the warm-up, a convergence run from the over-dispersed starts, in chunks, with the whole run traced on the device: after
+     every chunk R-hat (pydream/convergence.py:3-20: second half of the run so far) over all chains; reports the first generation count
+     at which max R-hat < 1.2 (the reference example's stopping rule, dream_ex_ndim_gaussian.py:80) -- this also takes the GPU out of its
+     idle clock state, in place of step 1's throw-away engine; then R-hat over a fixed window of --rhat-window generations;
+  b. (--adapt) blocks of generations timed inside the burn-in: `burnin_value`;
+  c. a pass of max(K, 200) generations with HIP events on every launch (per-kernel durations for the roofline: the median of
+     at least 20 launches of the persistent kernel, capped by what the timed steps allow);
+  d. (one GPU) blocks of EXACTLY K generations, repeated until at least --min-timed-ms have been timed, with the reference example's own
+     formula, the dense precision matrix: `dense_value`, and with history_lag 0: `value_history_lag0`; the `configs` block of the
+     other BASELINE workloads; (several GPUs) the strong-scaling leg and the RCCL leg;
+  e. (rank 0) the CPU restatement on the host cores.
 
 For N>1 there is one rank per GPU: either a launcher started them (torch.distributed.run: RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the environment), or -- `python bench.py --gpus N` as ONE process, no WORLD_SIZE -- bench.py starts its own N ranks
@@ -217,14 +225,53 @@ def measured_pmc(args, n_local):
     return out
 
 
-def timed_blocks(e, K, min_ms, barrier, dist, max_blocks=400):
-    """Blocks of exactly K generations, each bracketed by barrier + sync on both sides; returns the block times (s, max over ranks)."""
+PLAIN_TRACE_CAP = 2000        # generations the trace buffer of a plain run holds (4096 chains x 100-D: 6.6 GB)
+DUMP_BYTES = 64 << 20        # --dump-outputs writes at most this much
+
+
+def dump_outputs(e, args, last):
+    """--dump-outputs DIR: what the timed generations computed in their last one (trace row last - 1), what a caller of the engine receives
+    from it, as DIR/<name>.npy in float64 -- X and logp (every local chain's state and log density after it), moved / try_idx / cr_idx /
+    snooker (its decisions), history_tail (the archive's newest rows: those of the last history append).  At most DUMP_BYTES in all: where
+    an output would be larger, a fixed sample of its rows (seeded by --seed) is written instead, with the row numbers beside it
+    (chains.npy, history_tail_rows.npy).  On several GPUs rank 0 writes its own chains."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    tr = e.get_trace(last - 1, 1)
+    out = {k: tr[k][0] for k in ("X", "logp", "moved", "try_idx", "cr_idx", "snooker")}
+    rows = e.history_rows()
+    n_tail = min(rows, e.N)
+    tail = e.get_history(rows - n_tail)
+    rng = np.random.default_rng(args.seed)
+
+    def sample(n, row_bytes, budget):
+        cap = max(1, budget // row_bytes)
+        return None if n <= cap else np.sort(rng.choice(n, cap, replace=False))
+    sel = sample(e.nl, 8 * (e.d + 6), DUMP_BYTES * 9 // 16)            # (+1 for the row number)
+    if sel is not None:
+        out = {k: v[sel] for k, v in out.items()}
+        out["chains"] = sel
+    hsel = sample(n_tail, 8 * (e.d + 1), DUMP_BYTES * 6 // 16)
+    out["history_tail"] = tail if hsel is None else tail[hsel]
+    if hsel is not None:
+        out["history_tail_rows"] = hsel
+    assert sum(8 * v.size for v in out.values()) <= DUMP_BYTES
+    for name, v in out.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
+def timed_blocks(e, K, min_ms, barrier, dist, max_blocks=400, chunk=None):
+    """Blocks of exactly K generations, each bracketed by barrier + sync on both sides; returns the block times (s, max over ranks).
+    chunk: the engine's trace capacity when it is below K -- a block is then stepped in pieces of that many generations."""
+    chunk = chunk or K
     times = []
     while True:
         e.trace_reset()
         barrier()
         t0 = time.perf_counter()
-        e.step(K)
+        e.step(min(K, chunk))
+        for g in range(chunk, K, chunk):
+            e.trace_reset()
+            e.step(min(chunk, K - g))
         e.sync()
         dt = time.perf_counter() - t0              # this rank's K generations (its all-gathers waited for every other rank's)
         if dist is not None:
@@ -240,7 +287,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="the block of K timed generations is repeated until this much has been timed")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement besides the headline: convergence run and R-hat, burn-in rate, per-kernel times and roofline, "
+                         "dense / lag-0 / configs / strong-scaling / RCCL legs, CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed generations computed in their last one to DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="--full legs: their block of K timed generations is repeated until this much has been timed")
     ap.add_argument("--rhat-chunk", type=int, default=500, help="generations between R-hat evaluations of the convergence run")
     ap.add_argument("--rhat-max-generations", type=int, default=None,
                     help="the convergence run stops here if R-hat has not passed 1.2 (default: max(10000, 16 * dim) -- the 1000-D shard needs ~13000)")
@@ -354,9 +406,9 @@ def main():
             dist.close()
         return
     default_workload = (args.target == "mvn" and args.dim == 100 and args.chains_per_gpu == 4096 and args.multitry == 5 and not args.adapt)
-    if world == 1 and default_workload and not args.no_configs:
+    if args.full and world == 1 and default_workload and not args.no_configs:
         out["configs"] = baseline_configs(args)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out), flush=True)
     if dist is not None:
@@ -429,11 +481,15 @@ def measure(args, dist, world, rank, sub=False):
     conv_cap = max(chunk, args.rhat_max_generations)
     est_block_s = max(K * 15e-6 * max(1.0, (args.dim / 100.0) ** 2) * max(1.0, n_local / 4096.0), 1e-5)
     max_blocks = int(min(400, max(2, args.min_timed_ms * 1e-3 / est_block_s + 2)))
-    total = conv_cap + args.rhat_window + args.warmup + K * (max_blocks + 2) + max(K, args.event_generations) + 2 * args.thin + (args.burnin_generations + 40 if args.adapt else 0)
-    # The transport north_star names -- an RCCL all-gather of the appended rows -- gets its own number in every N > 1 line: after the blocks
-    # over the default transport (peer: copy-engine pushes) the SAME engines are re-attached to RCCL and the same blocks are timed again
+    full = args.full
+    if full:
+        total = conv_cap + args.rhat_window + args.warmup + K * (max_blocks + 2) + max(K, args.event_generations) + 2 * args.thin + (args.burnin_generations + 40 if args.adapt else 0)
+    else:
+        total = args.warmup + K + 2 * args.thin + (args.burnin_generations + 40 if args.adapt else 0)
+    # The transport north_star names -- an RCCL all-gather of the appended rows -- gets its own number in every N > 1 --full line: after the
+    # blocks over the default transport (peer: copy-engine pushes) the SAME engines are re-attached to RCCL and the same blocks are timed again
     # (`rccl_value`).  --rccl-leg runs it with one rank as well (a world-1 communicator: what a one-GPU box can exercise).
-    want_rccl = not sub and ((world > 1 and not args.no_rccl_leg) or getattr(args, "rccl_leg", False))
+    want_rccl = full and not sub and ((world > 1 and not args.no_rccl_leg) or getattr(args, "rccl_leg", False))
     if want_rccl:
         total += K * (max_blocks + 2) + max(K, 100) + 4 * args.thin
         if local_rank == 0:       # librccl.so is 570 MB: one sequential read puts it in the page cache while the first legs run (dlopen's page faults on a cold file took minutes)
@@ -475,13 +531,51 @@ def measure(args, dist, world, rank, sub=False):
         from pydream_amd.distributed import gelman_rubin_sharded
         return gelman_rubin_sharded(e, nsamples, group=dist.group)
 
-    def converge_and_time(e, with_rhat):
-        """parts 1-3 of the sequence on engine e; returns (block times, convergence record, acceptance of the last block)"""
+    def spin_up(seconds):
+        """load on a throw-away engine of this rank's size until the GPU has left its idle clock state (an idle MI355X needs ~0.1 s of
+        load); the measured engines' runs do not depend on it"""
+        import copy
+        aw = copy.copy(args); aw.adapt = False; aw.thin = 10 ** 6          # (appends once: the archive stays at its seed size however long it runs)
+        ew = setup_engine(_capi.Engine, aw, n_local, n_local, 0, 20000, device=device, trace_capacity=0)
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < seconds:
+            ew.trace_reset(); ew.step(500); ew.sync()
+        ew.close()
+
+    def converge_and_time(e, with_rhat, headline=False):
+        """the sequence of the module docstring on engine e: (--full) the convergence run, then the warm-up and the timed generations --
+        the headline's EXACTLY K of them, timed as one, or (a --full leg, a `configs` workload) blocks of K until --min-timed-ms;
+        returns (times, convergence record or None, acceptance of the last timed generations)"""
         def barrier():
             e.sync()
             if dist is not None:
                 dist.barrier()
                 e.comm_barrier()                   # the ranks leave a device collective closer together than a host barrier
+        tc = int(e.cfg.trace_capacity)
+        conv = None
+        if full:
+            conv = convergence_run(e, with_rhat)
+        barrier()
+        for g in range(0, args.warmup, tc):
+            e.trace_reset()
+            e.step(min(tc, args.warmup - g))
+        # the timed generations start right after a history append (the W warm-up generations are followed by the 0..thin-1 more that
+        # complete the current thin-cycle), so that a block of K generations is K / thin whole launches of the persistent kernel
+        g_now = e.generation() if callable(e.generation) else e.generation
+        align = (-(g_now - 1)) % args.thin
+        for g in range(0, align, tc):
+            e.trace_reset()
+            e.step(min(tc, align - g))
+        barrier()
+        if headline and not sub:
+            times = timed_blocks(e, K, 0.0, barrier, dist, max_blocks=1, chunk=tc)
+        else:
+            times = timed_blocks(e, K, args.min_timed_ms, barrier, dist, max_blocks)
+        acc = float(e.get_trace(0, K - (K - 1) // tc * tc, with_X=False)["moved"].mean())
+        return times, conv, acc
+
+    def convergence_run(e, with_rhat):
+        """--full, part a of the module docstring on engine e; returns the convergence record"""
         conv = {"chunk": chunk, "criterion": "max R-hat < 1.2 (reference rule: second half of the run so far, all %d chains)" % n_global,
                 "generations_to_rhat_below_1p2": None, "history": []}
         done = 0
@@ -515,36 +609,26 @@ def measure(args, dist, world, rank, sub=False):
             e.step(args.rhat_window)
             conv["rhat_window_generations"] = args.rhat_window
             conv["rhat_window_max"] = float(np.max(rhat_now(e, args.rhat_window)))
-        barrier()
-        e.trace_reset()
-        e.step(args.warmup)
-        # the timed blocks start right after a history append (the W warm-up generations are followed by the 0..thin-1 more that
-        # complete the current thin-cycle), so that a block of K generations is K / thin whole launches of the persistent kernel
-        g_now = e.generation() if callable(e.generation) else e.generation
-        align = (-(g_now - 1)) % args.thin
-        if align:
-            e.trace_reset()
-            e.step(align)
-        barrier()
-        times = timed_blocks(e, K, args.min_timed_ms, barrier, dist, max_blocks)
-        acc = float(e.get_trace(0, K, with_X=False)["moved"].mean())
-        return times, conv, acc
+        return conv
 
-    trace_cap = max(conv_cap, args.rhat_window, K, args.warmup, 2)
+    # (a plain run steps more than the trace buffer holds in pieces of PLAIN_TRACE_CAP generations: its size stays bounded at any --steps;
+    #  it holds at least one thin-cycle, so that the 0..thin-1 generations that align the timed ones are one call)
+    trace_cap = max(conv_cap, args.rhat_window, K, args.warmup, 2) if full else max(2, args.thin, min(max(K, args.warmup), PLAIN_TRACE_CAP))
     e = setup_engine(_capi.Engine, args, n_global, n_local, rank * n_local, total, device=device, trace_capacity=trace_cap)
     transport, transport_note = attach(e)
     burn = None
-    if args.adapt:
+    if not full:
+        spin_up(0.5)
+        if args.adapt:       # the crossover burn-in, untimed: `value` is the rate after it, as in a --full run
+            rest = args.burnin_generations + 1 - e.generation
+            while rest > 0:
+                n = min(rest, trace_cap); e.trace_reset(); e.step(n); rest -= n
+    elif args.adapt:
         # The crossover burn-in, timed on its own: blocks of K generations inside it (after 20 generations: the adaptation window opens
-        # at generation 11, Dream.py:371).  The GPU is taken out of its idle clock state first by a throw-away engine (an idle MI355X
-        # needs ~0.1 s of load), because the burn-in is by definition the START of the measured engine's run.
+        # at generation 11, Dream.py:371).  The GPU is taken out of its idle clock state first by a throw-away engine,
+        # because the burn-in is by definition the START of the measured engine's run.
         import copy
-        aw = copy.copy(args); aw.adapt = False; aw.thin = 10 ** 6          # (appends once: the archive stays at its seed size however long it runs)
-        ew = setup_engine(_capi.Engine, aw, n_local, n_local, 0, 20000, device=device, trace_capacity=0)
-        t_w = time.perf_counter()
-        while time.perf_counter() - t_w < 0.4:
-            ew.trace_reset(); ew.step(500); ew.sync()
-        ew.close()
+        spin_up(0.4)
 
         def time_burnin(eb, finish):
             eb.trace_reset(); eb.step(20 + (-(20 - 1)) % args.thin); eb.sync()      # (the blocks start right behind a history append, like the timed blocks after the burn-in: whole launches)
@@ -580,8 +664,10 @@ def measure(args, dist, world, rank, sub=False):
             e0.close()
             burn["adapt_lag0"] = {k_: b0[k_] for k_ in ("value", "ms_per_step", "kernel_variant", "timed_blocks")}
     t_enq0 = time.perf_counter()
-    times, conv, acc = converge_and_time(e, True)
+    times, conv, acc = converge_and_time(e, True, headline=True)
     med = float(np.median(times))
+    if args.dump_outputs and rank == 0 and not sub:
+        dump_outputs(e, args, K - (K - 1) // trace_cap * trace_cap)
 
     # ---- a pass of K generations with HIP events around every kernel launch (per-kernel durations
     #      for the roofline; kept out of the timed blocks because each event record costs a few us) ----
@@ -593,7 +679,7 @@ def measure(args, dist, world, rank, sub=False):
         e.sync()
         xstats = e.exchange_stats()
         xbytes = e.exchange_bytes()
-    if not args.no_events:
+    if full and not args.no_events:
         KE = max(K, args.event_generations)
         KE -= KE % args.thin if KE >= args.thin else 0          # whole thin-cycles: every launch of the persistent kernel is a full one
         done_ev = 0
@@ -633,7 +719,7 @@ def measure(args, dist, world, rank, sub=False):
         e.sync()
         dist.barrier()           # every rank is past its last exchange: only now may a rank unmap its buffers
     strong = None
-    if world > 1 and not sub and not getattr(args, "no_strong", False) and STRONG_CHAINS % world == 0 and args.target == "mvn" and args.dim == 100:
+    if full and world > 1 and not sub and not getattr(args, "no_strong", False) and STRONG_CHAINS % world == 0 and args.target == "mvn" and args.dim == 100:
         # BASELINE configs[3] as written -- 32768 chains, 100-D MVN, "report 1/2/4/8 scaling" -- read as STRONG scaling: the same 32768 chains over
         # this run's N GPUs (the N = 1 point is `configs["configs[3] @ 1 GPU"]` of the one-GPU line); a second set of engines on the transport
         # the weak blocks used, a short warm-up from the seed archive, blocks of K generations
@@ -688,14 +774,16 @@ def measure(args, dist, world, rank, sub=False):
                                       if world > 1 else "single GPU"},
             "timing": {"timed_blocks": len(times), "block_generations": K, "block_ms_median": 1e3 * med, "block_ms_min": 1e3 * min(times),
                        "block_ms_max": 1e3 * max(times), "timed_ms_total": 1e3 * sum(times),
-                       "value_from": "median block", "value_best_block": n_global * args.multitry * K / min(times),
+                       "value_from": "median block" if sub else "the %d timed generations, timed as one" % K,
+                       "value_best_block": n_global * args.multitry * K / min(times),
                        "value_worst_block": n_global * args.multitry * K / max(times)},
             "logp_points_per_s": n_global * (2 * args.multitry - 1) * K / med,
             "acceptance_rate": acc,
-            "generations_executed": conv["generations_run"] + args.rhat_window + args.warmup + K * len(times) + (0 if args.no_events else prof.get("event_pass_generations", 0)),
-            "rhat_max": conv.get("rhat_window_max") if not sub else (conv["history"][-1][1] if conv["history"] else None),
-            "convergence": conv,
+            "generations_executed": (conv["generations_run"] + args.rhat_window if conv else 0) + args.warmup + K * len(times) + prof.get("event_pass_generations", 0),
         }
+        if conv is not None:
+            out["rhat_max"] = conv.get("rhat_window_max") if not sub else (conv["history"][-1][1] if conv["history"] else None)
+            out["convergence"] = conv
         if dense is not None:
             out["dense_value"] = dense["value"]
             out["dense"] = dense
@@ -883,7 +971,7 @@ def measure(args, dist, world, rank, sub=False):
         watchdog.cancel()
     e.close()
 
-    if world == 1 and args.target == "mvn" and args.mvn_kind == "tri" and not args.no_dense and not sub:
+    if full and world == 1 and args.target == "mvn" and args.mvn_kind == "tri" and not args.no_dense and not sub:
         import copy
         a2 = copy.copy(args)
         a2.mvn_kind = "dense"
@@ -893,7 +981,7 @@ def measure(args, dist, world, rank, sub=False):
         m2 = float(np.median(t2))
         dense = {"value": n_global * args.multitry * K / m2, "ms_per_step": 1e3 * m2 / K, "timed_blocks": len(t2),
                  "formula": "log_F - x.(invC.x)/2 with the dense precision matrix (dream_ex_ndim_gaussian.py:49-52)", "acceptance_rate": acc2}
-    if world == 1 and args.history_lag != 0 and not args.no_lag0 and not sub:
+    if full and world == 1 and args.history_lag != 0 and not args.no_lag0 and not sub:
         import copy
         a3 = copy.copy(args)
         a3.history_lag = 0

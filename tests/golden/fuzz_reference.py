@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""Differential fuzzing of the ORACLE against the REFERENCE itself (runs only where /root/reference exists, like make_golden.py whose
-machinery it uses): random small configurations are run through the reference's own Dream.astep with the contract's draws injected
-(make_golden.run_reference), then through the oracle from the same inputs, and compared the way the committed fixtures are
+"""Differential fuzzing of the ORACLE against the REFERENCE itself (a live run needs the reference's `pydream` first on PYTHONPATH, like
+make_golden.py whose machinery it uses): random small configurations are run through the reference's own Dream.astep with the contract's
+draws injected (make_golden.run_reference), then through the oracle from the same inputs, and compared the way the committed fixtures are
 (tests/helpers.compare_with_reference: decision sequences exact, log densities 1e-10, states 1e-9 relative, archive, adapted
-probabilities).  Nothing is written to tests/golden; the point is that the pinning does not hang on the dozen committed cases.
+probabilities).  The point is that the pinning does not hang on the dozen committed cases.
 
-    PYTHONPATH=/root/reference python tests/golden/fuzz_reference.py --n 200 --seed 1
-    PYTHONPATH=/root/reference python tests/golden/fuzz_reference.py --n 300 --seed 1 --tri
+    PYTHONPATH=<reference checkout> python tests/golden/fuzz_reference.py --n 200 --seed 1
+    PYTHONPATH=<reference checkout> python tests/golden/fuzz_reference.py --n 300 --seed 1 --tri
+
+--record PREFIX keeps the reference's side of every case (its inputs and outputs) in PREFIX_<part>.npz; --replay FILE... checks the oracle
+against such a recording without the reference.  tests/test_oracle_reference_fuzz.py replays the recordings tests/golden/fuzz_*.npz.
 
 --tri (round 5): the triangular arm.  Every case has the MVN target, at dimensions up to 100, and after the comparison with the dense
 precision matrix (the reference's own formula, dream_ex_ndim_gaussian.py:49-52) the oracle runs the case AGAIN with the matrix handed over
@@ -25,9 +28,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 sys.path.insert(0, HERE)
 
-import make_golden as MG                      # noqa: E402  (asserts that pydream is the reference's)
 from oracle import oracle as O                # noqa: E402
 from tests import helpers as H                # noqa: E402
+
+MG = None                                     # make_golden, imported by the first capture: it asserts that pydream is the reference's
+
+
+def _mg():
+    global MG
+    if MG is None:
+        import make_golden
+        MG = make_golden
+    return MG
 
 
 def draw_case(rng):
@@ -105,25 +117,33 @@ def draw_pt_case(rng):
                 rng_seed=int(rng.integers(0, 2 ** 31 - 1)), dream_kwargs=kw)
 
 
-def run_pt_case(c):
+def capture(c):
+    """the reference's inputs and outputs for case c (needs the reference), as the fixture dict the oracle is checked against;
+    fuzz_pt / fuzz_tri record which check the case gets"""
+    MG = _mg()
     captured = {}
-    MG.save = lambda name, **arrs: captured.update({k: np.asarray(v) for k, v in arrs.items()})
-    c = dict(c); c.pop("pt")
-    MG.pt_case("fuzz_pt", **c)
-    e = H.pt_engine_from_fixture(O.Engine, captured)
-    e.step(int(captured["cfg_G"]))
-    H.compare_pt_with_reference(e, captured)
+    MG.save = lambda name, **arrs: captured.update({k: np.asarray(v) for k, v in arrs.items()})       # (trace_case hands its arrays to save)
+    c = dict(c); pt = c.pop("pt", False); tri = c.pop("tri", False)
+    if pt:
+        MG.pt_case("fuzz_pt", **c)
+    else:
+        MG.trace_case("fuzz", **c)
+    captured["fuzz_pt"] = np.int32(bool(pt)); captured["fuzz_tri"] = np.int32(bool(tri))
+    return captured
+
+
+def check_pt(fx):
+    e = H.pt_engine_from_fixture(O.Engine, fx)
+    e.step(int(fx["cfg_G"]))
+    H.compare_pt_with_reference(e, fx)
     return 0
 
 
-def run_case(c):
-    if c.get("pt"):
-        return run_pt_case(c)
-    captured = {}
-    MG.save = lambda name, **arrs: captured.update({k: np.asarray(v) for k, v in arrs.items()})       # (trace_case hands its arrays to save)
-    c = dict(c); tri = c.pop("tri", False)
-    MG.trace_case("fuzz", **c)
-    fx = captured
+def check(fx):
+    """the oracle against one captured case (no reference needed); -> rounds with redraws (> 0), 0, or -1: not comparable"""
+    if int(fx["fuzz_pt"]):
+        return check_pt(fx)
+    tri = bool(int(fx["fuzz_tri"]))
     if int(fx["redraws"].max()) >= 64:         # beyond DZ_MAX_REDRAWS the engines give the step up as a rejection (DESIGN.md deviation D1): not comparable
         return -1
     e = H.engine_from_trace_fixture(O.Engine, fx)
@@ -157,24 +177,73 @@ def run_case(c):
     return int((fx["redraws"] > 0).sum())
 
 
+def run_case(c):
+    return check(capture(c))
+
+
+PART_BYTES = 960 * 1024          # a recording is split into files of at most this size (every committed file stays under 1 MiB)
+
+
+def record(cases, prefix):
+    """captured cases -> prefix_<part>.npz files (keys c<i>_<name>), each under PART_BYTES; -> the paths written"""
+    import io
+    paths, part, size = [], {}, 0
+
+    def flush():
+        path = "%s_%d.npz" % (prefix, len(paths))
+        np.savez_compressed(path, **part)
+        paths.append(path)
+    for i, fx in enumerate(cases):
+        b = io.BytesIO(); np.savez_compressed(b, **fx)
+        if part and size + len(b.getvalue()) > PART_BYTES:
+            flush(); part, size = {}, 0
+        part.update({"c%03d_%s" % (i, k): v for k, v in fx.items()})
+        size += len(b.getvalue())
+    if part:
+        flush()
+    return paths
+
+
+def recorded(paths):
+    """the cases of a recording (record()'s files), in case order"""
+    cases = {}
+    for path in paths:
+        with np.load(path, allow_pickle=False) as z:
+            for key in z.files:
+                i, name = key[1:].split("_", 1)
+                cases.setdefault(int(i), {})[name] = z[key]
+    return [cases[i] for i in sorted(cases)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--adapt-lag", action="store_true", help="the adapt_lag arm: every lockstep case with an adaptation gets a lag (else: half of them)")
     ap.add_argument("--tri", action="store_true", help="the triangular arm: MVN cases up to 100-D, each also run with the triangular factor")
+    ap.add_argument("--record", metavar="PREFIX", help="also write the reference's side of every case to PREFIX_<part>.npz (what --replay reads)")
+    ap.add_argument("--replay", metavar="FILE", nargs="+", help="check the oracle against a recording instead (no reference needed; --n / --seed / "
+                                                                 "the arm flags are ignored)")
     args = ap.parse_args()
+    if args.replay:
+        n, bad, redrawn, skipped, t0 = replay(args.replay)
+        print("fuzz vs reference (recorded, %s): %d cases, %d mismatches, %d with redraw rounds, %d skipped, %.0f s"
+              % (" ".join(os.path.basename(p) for p in args.replay), n, bad, redrawn, skipped, time.time() - t0))
+        return 1 if bad else 0
     rng = np.random.default_rng(args.seed)
     global adapt_lag_arm
     adapt_lag_arm = args.adapt_lag
     bad = 0; redrawn = 0; skipped = 0; t0 = time.time()
     devnull = open(os.devnull, "w")
+    kept = []
     for i in range(args.n):
         c = draw_tri_case(rng) if args.tri else (draw_pt_case(rng) if rng.random() < 0.1 else draw_case(rng))
         out = sys.stdout
         try:
             sys.stdout = devnull
-            r = run_case(c)
+            fx = capture(c)
+            kept.append(fx)
+            r = check(fx)
             redrawn += r > 0
             skipped += r < 0
         except Exception as ex:
@@ -185,7 +254,28 @@ def main():
             sys.stdout = out
     print("fuzz vs reference%s: %d cases, %d mismatches, %d with redraw rounds, %d skipped (a step of the reference took 64 or more redraw rounds: deviation D1), %.0f s (seed %d)"
           % (" (triangular arm: every case also with the factor U of the precision matrix)" if args.tri else "", args.n, bad, redrawn, skipped, time.time() - t0, args.seed))
+    if args.record:
+        if bad or len(kept) != args.n:
+            print("nothing recorded: every case must be captured and agree", flush=True)
+            return 1
+        for path in record(kept, args.record):
+            print("recorded", path, os.path.getsize(path), flush=True)
     return 1 if bad else 0
+
+
+def replay(paths):
+    """the oracle against every case of a recording -> (cases, mismatches, with redraw rounds, skipped, start time)"""
+    bad = redrawn = skipped = 0; t0 = time.time()
+    cases = recorded(paths)
+    for i, fx in enumerate(cases):
+        try:
+            r = check(fx)
+            redrawn += r > 0
+            skipped += r < 0
+        except Exception as ex:
+            bad += 1
+            print("MISMATCH #%d: %s" % (i, str(ex).strip().split("\n")[0][:300]), flush=True)
+    return len(cases), bad, redrawn, skipped, t0
 
 
 if __name__ == "__main__":

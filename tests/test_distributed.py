@@ -544,7 +544,7 @@ def test_bench_eight_rank_control_flow_on_one_gpu(tmp_path, transport):
     Proves the control flow the 8-GPU run takes: rendezvous, sharded engines, the convergence run with the
     sharded R-hat, timed blocks with the rank-maximum, one JSON line from rank 0 with whole-job throughput."""
     env = dict(os.environ, DZ_BENCH_DEVICE="0", DZ_BENCH_TRANSPORT=transport, HSA_ENABLE_IPC_MODE_LEGACY="0", DZ_PEER_TIMEOUT_S="120")
-    d = _launch_bench(8, ["--steps", "20", "--warmup", "5", "--chains-per-gpu", "128", "--rhat-max-generations", "400",
+    d = _launch_bench(8, ["--full", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "128", "--rhat-max-generations", "400",
                           "--rhat-min-generations", "200", "--rhat-chunk", "100", "--rhat-window", "200", "--min-timed-ms", "20",
                           "--no-cpu-baseline"], env, str(tmp_path))
     assert d["n_gpus"] == 8 and d["steps"] == 20 and d["scaling"] == "weak"
@@ -567,7 +567,7 @@ def test_bench_line_has_the_contracted_fields(tmp_path):
     on a bounded sample), the kernel instantiation that ran, and a launch duration the timed blocks allow."""
     import json
     import subprocess
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512",
                           "--rhat-max-generations", "600", "--rhat-min-generations", "300", "--rhat-chunk", "100", "--rhat-window", "200",
                           "--min-timed-ms", "5", "--cpu-chains", "128", "--cpu-seconds", "1", "--rccl-leg"],
                          cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
@@ -598,6 +598,93 @@ def test_bench_line_has_the_contracted_fields(tmp_path):
     assert "configs" not in d                      # (512 chains per GPU is not the default workload: no configs block)
 
 
+def _plain_bench(tmp_path, name, argv, env=None):
+    """`python bench.py <argv> --dump-outputs <dir>` (no --full) -> (its one JSON line, the dumped arrays by name)"""
+    import json
+    import subprocess
+    dump = tmp_path / name
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(dump)], cwd=str(tmp_path), env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-3000:]
+    ls = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(ls) == 1, res.stdout[-2000:]
+    return json.loads(ls[0]), {f[:-4]: np.load(str(dump / f)) for f in sorted(os.listdir(str(dump)))}
+
+
+def _assert_dump_is_the_oracles(argv, n_global, dump):
+    """The dump of a plain run against the oracle stepped through the same generations from bench.py's own set-up (W warm-up
+    generations, the 0..thin-1 that end the thin-cycle, K timed): the last generation's trace row of the run's first chains and the
+    archive's newest n_global rows, bit for bit."""
+    import bench
+    from oracle import oracle as O
+    segs = os.environ.get("DZ_MEGA_SEGS")
+    try:
+        a = bench.parse_args(argv)                        # (sets DZ_MEGA_SEGS for the GPU engine: put back what this process had)
+    finally:
+        if segs is None:
+            os.environ.pop("DZ_MEGA_SEGS", None)
+        else:
+            os.environ["DZ_MEGA_SEGS"] = segs
+    G = a.warmup + (-(a.warmup - 1)) % a.thin + a.steps
+    e = bench.setup_engine(O.Engine, a, n_global, n_global, 0, G, schedule=2, trace_capacity=64)
+    for g in range(0, G, 64):
+        e.trace_reset()
+        e.step(min(64, G - g))
+    tr = e.get_trace((G - 1) % 64, 1)
+    nl = dump["X"].shape[0]
+    for k in ("X", "logp", "moved", "try_idx", "cr_idx", "snooker"):
+        np.testing.assert_array_equal(dump[k], tr[k][0][:nl].astype(np.float64), err_msg=k)
+    np.testing.assert_array_equal(dump["history_tail"], e.get_history()[-n_global:])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the headline and nothing else -- EXACTLY K timed generations, timed as one
+    (ms_per_step = that time / K) --, and --dump-outputs writes what the last of them computed: the oracle's arrays after the same
+    generations; a second run with the same arguments writes the same arrays, bit for bit."""
+    argv = ["--gpus", "1", "--steps", "30", "--warmup", "7", "--chains-per-gpu", "512"]
+    (d, a), (_, b) = _plain_bench(tmp_path, "out0", argv), _plain_bench(tmp_path, "out1", argv)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "kernel_variant"):
+        assert key in d, key
+    for key in ("convergence", "rhat_max", "roofline", "kernel_times", "cpu_baseline", "configs", "dense_value", "value_history_lag0", "rccl_value"):
+        assert key not in d, key
+    assert d["steps"] == 30 and d["warmup"] == 7 and d["unit"] == "proposals/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["timing"]["timed_blocks"] == 1 and d["timing"]["block_generations"] == 30
+    assert abs(d["ms_per_step"] - d["timing"]["block_ms_median"] / 30) < 1e-9 * d["ms_per_step"]
+    assert abs(d["value"] - 512 * 5 * 30 / (d["ms_per_step"] * 30e-3)) < 1e-6 * d["value"]
+    assert set(a) == {"X", "logp", "moved", "try_idx", "cr_idx", "snooker", "history_tail"} and set(b) == set(a)
+    assert a["X"].shape == (512, 100) and a["X"].dtype == np.float64 and a["history_tail"].shape == (512, 100)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    _assert_dump_is_the_oracles(argv, 512, a)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["steps_below_thin", "steps_beyond_the_trace_buffer", "two_ranks"])
+def test_bench_plain_run_at_the_edges_dumps_what_the_oracle_computes(tmp_path, case):
+    """Plain runs the harness may choose: K and W below one thin-cycle (the alignment generations then outnumber them), K beyond the
+    plain trace buffer (the timed generations stepped in pieces), and two ranks (here both on device 0: DZ_BENCH_DEVICE; rank 0 dumps its
+    own chains) -- each times exactly K generations as one, and dumps what the oracle computes over the same generations."""
+    import bench
+    env = None
+    gpus, steps, warmup = 1, 3, 3
+    if case == "steps_beyond_the_trace_buffer":
+        steps = bench.PLAIN_TRACE_CAP + 3
+    elif case == "two_ranks":
+        gpus, steps, warmup = 2, 20, 5
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+        env.update(DZ_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", DZ_PEER_TIMEOUT_S="120")
+    argv = ["--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup), "--chains-per-gpu", "512"] + (["--transport", "peer"] if gpus > 1 else [])
+    d, dump = _plain_bench(tmp_path, "out", argv, env)
+    assert d["n_gpus"] == gpus and d["steps"] == steps and d["warmup"] == warmup
+    assert d["timing"]["timed_blocks"] == 1 and d["timing"]["block_generations"] == steps and "convergence" not in d
+    assert abs(d["value"] - gpus * 512 * 5 * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"]
+    if gpus > 1:
+        assert d["replicas_identical"] is True and "strong_scaling" not in d and "rccl_value" not in d
+    assert dump["X"].shape == (512, 100)
+    _assert_dump_is_the_oracles(argv, gpus * 512, dump)
+
+
 @pytest.mark.gpu
 def test_bench_default_line_carries_every_single_gpu_baseline_config(tmp_path):
     """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command; here with a short convergence run): the line's `configs` block
@@ -606,7 +693,7 @@ def test_bench_default_line_carries_every_single_gpu_baseline_config(tmp_path):
     instantiation that ran, its roofline fraction and the run-so-far R-hat."""
     import json
     import subprocess
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5",
                           "--rhat-max-generations", "600", "--rhat-min-generations", "300", "--rhat-chunk", "100", "--rhat-window", "200",
                           "--min-timed-ms", "5", "--no-cpu-baseline", "--no-dense", "--no-lag0"],
                          cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
@@ -649,7 +736,7 @@ def test_bench_two_ranks_with_crossover_adaptation_exchange_group_sums(tmp_path)
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DZ_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", DZ_PEER_TIMEOUT_S="120")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512", "--adapt",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512", "--adapt",
                           "--burnin-generations", "160", "--rhat-max-generations", "400", "--rhat-min-generations", "200", "--rhat-chunk", "100", "--rhat-window", "200",
                           "--min-timed-ms", "20", "--no-cpu-baseline", "--transport", "peer", "--no-rccl-leg"], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -669,7 +756,7 @@ def test_bench_with_crossover_adaptation_reports_the_burnin_rate(tmp_path):
     (`burnin_value`, persistent kernel with one generation per launch + the adaptation launches) and after it (`value`)."""
     import json
     import subprocess
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--target", "mix3", "--adapt",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--target", "mix3", "--adapt",
                           "--burnin-generations", "160", "--chains-per-gpu", "512", "--rhat-max-generations", "400", "--rhat-min-generations", "200",
                           "--rhat-chunk", "100", "--rhat-window", "200", "--min-timed-ms", "5", "--no-cpu-baseline"],
                          cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
@@ -691,7 +778,7 @@ def test_bench_gpus_2_as_one_command_starts_its_own_ranks(tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DZ_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", DZ_PEER_TIMEOUT_S="120")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--chains-per-gpu", "512",
                           "--rhat-max-generations", "400", "--rhat-min-generations", "200", "--rhat-chunk", "100", "--rhat-window", "200",
                           "--min-timed-ms", "20", "--no-cpu-baseline", "--transport", "peer"], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
