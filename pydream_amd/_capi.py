@@ -42,6 +42,11 @@ SYMBOLS = [
     "dz_profile_enable", "dz_profile_get", "dz_profile_reset", "dz_profile_get_list",
 ]
 
+# the environment switches the engine reads when it is made (dz_engine.hip read_switches): each forces or forbids a path, so every rank of a
+# sharded run must see the same values (distributed.attach_transport).  tests/test_capi_symbols.py checks this list against the engine's source.
+ENGINE_SWITCHES = ("DZ_MEGA", "DZ_MEGA_D2", "DZ_MEGA_SEGS", "DZ_MEGA_REDO", "DZ_MEGA_USER", "DZ_PROPOSE_SPLIT", "DZ_LOGP_GEMM", "DZ_QFIN",
+                   "DZ_STREAMS", "DZ_ADAPT_FUSED", "DZ_ADAPT_MULTI", "DZ_ADAPT_GROUPS")
+
 _lib = None
 
 

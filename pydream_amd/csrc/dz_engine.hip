@@ -37,6 +37,9 @@ int fail(const std::string& m) { g_err = m; return -1; }
     } while (0)
 #define DZCK(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 
+constexpr int RA_STRIDE = 32;             // host run-ahead: a marker every RA_STRIDE generations (dz_step)
+constexpr int MEGA_MAX_GEN = 1 << 20;     // generations per launch of the persistent kernels, at most
+
 enum { LK_NONE = 0, LK_MVN = 1, LK_MIX = 2, LK_HOST = 3, LK_MODULE = 4 };
 enum { PR_PROPOSE = 0, PR_LOGP = 1, PR_ACCEPT = 2, PR_ADAPT = 3, PR_EXCHANGE = 4, PR_GENERATIONS = 5, PR_EMPTY = 6, PR_COUNT = 7 };
 
@@ -114,13 +117,12 @@ struct dz_engine {
     // history appends the groups share nothing, so one group's likelihood (matrix pipe) overlaps another's
     // proposal generation (VALU) -- lane 0 is `stream`
     int nlanes = 1; hipStream_t lane_stream[8] = {nullptr}; hipEvent_t lane_ev[8] = {nullptr}; bool need_join = true;
-    // bounded host run-ahead: a marker every ra_stride generations, the host never gets more than 3 markers ahead
+    // bounded host run-ahead: a marker every RA_STRIDE generations, the host never gets more than 3 markers ahead
     dz::Params p_shadow; bool params_uploaded = false;    // what d_params holds
     void* h_pin = nullptr; hipEvent_t pin_ev[2] = {nullptr, nullptr};          // page-locked bounce buffer (two halves) for downloads into pageable memory (d2h_2d)
     double* d_bar = nullptr;                // dz_comm_barrier's all-gather buffer (one element per rank)
-    double* d_qpart = nullptr; size_t qpart_len = 0; bool force_big = false; bool logp_gemm = true; int logp_bm = 0;    // DZ_LOGP_GEMM=0: no LDS-tiled product; row-tile sums of the tiled large-d likelihood; DZ_LOGP_BIG=1: the one-wave-per-tile kernel
-    int logp_waves = 0;      // DZ_LOGP_WAVES: force the block size of k_logp_mvn_lds (tuning)
-    int ra_stride = 32; hipEvent_t ra_ev[4] = {nullptr}; bool ra_used[4] = {false, false, false, false}; int64_t ra_n = 0;
+    double* d_qpart = nullptr; size_t qpart_len = 0; bool logp_gemm = true;    // row-tile sums of the tiled large-d likelihood; DZ_LOGP_GEMM=0: no LDS-tiled product
+    hipEvent_t ra_ev[4] = {nullptr}; bool ra_used[4] = {false, false, false, false}; int64_t ra_n = 0;
     int nch = 1;
     int64_t M = 0, gen = 0, ntrace = 0, draws_gen = -1;
     int64_t napp = 0;               // appends made since the archive was set (dz_config.history_lag: the last `lag` of them are not sampleable yet)
@@ -157,7 +159,6 @@ struct dz_engine {
     double* d_binsum = nullptr;     // k_adapt_update's scratch: [strips of 64 chains][ncr + ngamma] sums, then the same shape of counts
     // lockstep adaptation, contract v3 (dz_kernels.h adapt_unit_sums): the units' sums [units][nq][ld] and counts [units][ncr + ngamma], their totals
     double *d_PR = nullptr, *d_PC = nullptr, *d_TOT = nullptr, *d_CNT = nullptr;
-    bool mega_mix_wide = true;      // the wave-per-chain kernels (mixture, a user's device function) also at 128 < d <= 256 (DZ_MEGA_MIX_WIDE=0: the multi-kernel path there)
     bool adapt_fused = true;        // the persistent kernels make their block's unit sums themselves (DZ_ADAPT_FUSED=0: k_adapt_partials does)
     // dz_config.adapt_lag = L >= 1 (round 6): d_TOT / d_CNT are rings of L + 1 slots (slot = generation mod (L + 1); d_CNT rows of ad_nbp), d_DOT
     // [L + 1][ad_nbp] the bins' dot products (k_adapt_dots), d_PR / d_PC rings as well when launches hold several burn-in generations (ad_multi).
@@ -168,10 +169,11 @@ struct dz_engine {
     // ... and for the kernels that do not make their blocks' unit sums (burnin_multi == 2): d_posring [L + 2][N][ld] the published positions of the last
     // L + 2 generations (slot = generation mod (L + 2); made on first use), posring_gen the last generation in it; d_PG [L + 1][ad_nbp] the probabilities
     // the last launch's generations decided with (k_adapt_partials_ring)
-    double *d_posring = nullptr, *d_PG = nullptr; int64_t posring_gen = -2; bool ad_ring = true;
+    double *d_posring = nullptr, *d_PG = nullptr; int64_t posring_gen = -2;
     // sharded crossover burn-in (round 5): a rank that owns whole groups of 256 chains exchanges its groups' sums (dz_kernels.h k_adapt_groups /
     // k_group_totals) instead of its positions.  d_GS[parity of the generation]: [world][gs_rec] records (two buffers: a peer may be one
     // generation ahead); d_shift[parity]: global chain 0's position after that generation (the shift of the next one's column sums)
+    bool adapt_groups_on = true, adapt_multi_on = true;      // DZ_ADAPT_GROUPS=0 / DZ_ADAPT_MULTI=0: neither the group sums nor several burn-in generations per launch
     bool adapt_groups = false; double* d_GS[2] = {nullptr, nullptr}; double* d_shift[2] = {nullptr, nullptr}; size_t gs_rec = 0; int gs_nbp = 0;
     int64_t gs_pushed = 0, gs_last_gen = -1, gs_launches = 0;
     int64_t bytes_z = 0, bytes_pos = 0, bytes_sums = 0;      // bytes this rank has sent to EACH other rank, by kind (dz_exchange_bytes)
@@ -181,24 +183,15 @@ struct dz_engine {
     std::vector<double> h_stage;     // host staging (callback likelihood / exchange)
     bool prof = false;
     int num_cu = 256;
-    int waves_per_block = 0;        // DZ_WPB
-    bool fuse = true;               // DZ_FUSE=0 disables the accept+propose fusion
-    bool fuse_stream = true;        // streamed generations: the Metropolis step rides in front of the next generation's proposal set (k_accept_propose; DZ_FUSE_STREAM=0: off)
     int64_t stream_prop_gen = -1;   // the generation whose proposal set k_accept_propose has already made
     bool q_defer = true;            // streamed generations: no k_q_finish launches, the proposal / Metropolis kernels add the row-tile sums (DZ_QFIN=0: off)
     double* last_qpart = nullptr;   // the scratch slice the last tiled likelihood launch wrote
-    bool stream_propose = true;     // ld > 256: the streaming proposal kernel (k_propose_stream); DZ_STREAM=0 keeps k_propose<4|8>
     bool mega = true;               // the persistent generation kernel serves every eligible configuration (mega_eligible); DZ_MEGA=0 forces the multi-kernel path
     bool mega_redo_on = true;       // redraw rounds (Dream.py:281-289) inside the persistent kernel; DZ_MEGA_REDO=0: such configurations take the multi-kernel path
     unsigned long long* d_redraw_count = nullptr;
-    bool mega_mix_pb = true;        // the mixture kernel's full-code instantiation (priors, boundaries, several pairs); DZ_MEGA_MIX_PB=0: multi-kernel path there
     int mega_d2 = 1;                // 128 < d <= 256: k_generations_d2 from 1025 chains on (DZ_MEGA_D2=0: the multi-kernel path there; 2: at any chain count)
-    bool mega_w4 = true;            // small populations (4 chains x 4 waves per block), lean, multitry 3..6: k_generations_w4 (DZ_MEGA_W4=0: k_generations<.., 4, 4, lean>)
-    bool mega_split = true;         // a remainder of chains beyond whole rounds of 16-chain blocks goes in a second launch of smaller blocks; DZ_MEGA_SPLIT=0: off
-    bool mega_burnin = true;        // ... the generations of the crossover burn-in too, one per launch (positions published by the kernel); DZ_MEGA_BURNIN=0: multi-kernel path there
-    int mega_max_gen = 1 << 20;     // DZ_MEGA_MAXGEN: generations per launch cap (measurement)
+    bool mega_user = true;          // a user's device function inside the persistent kernel when its code object has it; DZ_MEGA_USER=0: the batch kernel only
     int mega_segs = 1 << 20;        // DZ_MEGA_SEGS: history appends per launch cap (1: a launch ends with its append, as without a lag)
-    int mega_ch = 0;                // DZ_MEGA_CHAINS: force 16 / 8 / 4 chains per block (0: by chain count)
     bool tempering = false; double* d_Tc = nullptr; int32_t* d_tswap = nullptr;    // parallel tempering (dz_set_temperatures)
     // Dream.py:281-289: a proposal set whose tries are all impossible is drawn again (redo_possible / one_generation)
     uint8_t* d_redo = nullptr; int32_t* d_redo_list = nullptr; uint8_t* h_redo = nullptr; int32_t* h_redo_list = nullptr;     // (host side: page-locked)
@@ -212,7 +205,6 @@ struct dz_engine {
     const double* pending_qfin_r = nullptr;      // ... and with it the reference set's row-tile sums (Params::qfin_r), still in the scratch array
     int64_t pending_slot = -1;
     int propose_split = 0;          // waves per chain in k_propose (DZ_PROPOSE_SPLIT); 0 = by problem shape
-    int force_pt = 0;               // measurement switch: DZ_MFMA_PT=1|2 forces the point tiles per wave
     std::vector<hipEvent_t> ev_pool;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PR_COUNT];
     std::vector<void*> to_free;
@@ -352,19 +344,18 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
     // LDS kernel: matrix (packed triangle or square) + mean + at least 4 wave tiles must fit 160 KB
     // (the dense 128-D square does not: 131 KB + 66 KB; it runs on the register-operand MFMA kernel)
     const bool lds_fits = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld + (size_t)4 * 16 * (e->p.ld + 1)) <= (size_t)160 * 1024;
-    const bool one_kernel = e->lk == LK_MVN && !e->p.have_prior && nrt <= 8 && !e->force_pt && lds_fits;   // the LDS kernel alone: timed by the launch's own events
+    const bool one_kernel = e->lk == LK_MVN && !e->p.have_prior && nrt <= 8 && lds_fits;   // the LDS kernel alone: timed by the launch's own events
     ProfScope ps(e, PR_LOGP, st, !one_kernel);
     const dim3 grid((n + 3) / 4), block(256);
     if (e->lk == LK_MVN) {
         {
-            if (nrt <= 8 && !e->force_pt && lds_fits) {
+            if (nrt <= 8 && lds_fits) {
                 const int ntiles = (n + 15) / 16;
                 // one wave per point tile of the CU's share when LDS allows (4..8 waves): 1280 tiles on 256 CUs run as
                 // 5-wave blocks instead of 4-wave blocks of which a quarter does a second tile
                 const size_t lds_fixed = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld), lds_wave = sizeof(double) * (size_t)16 * (e->p.ld + 1);
                 int nwv = std::max(4, std::min(8, (ntiles + e->num_cu - 1) / e->num_cu));
                 while (nwv > 4 && lds_fixed + nwv * lds_wave > (size_t)160 * 1024) --nwv;
-                if (e->logp_waves) nwv = e->logp_waves;
                 const size_t lds = lds_fixed + nwv * lds_wave;
                 const dim3 gl((unsigned)std::min(e->num_cu, (ntiles + nwv - 1) / nwv)), bl(64 * nwv);
 #define DZ_LDS_CASE(NRT_)                                                                                                      \
@@ -379,7 +370,7 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
 #undef DZ_LDS_CASE
             } else if (nrt <= 8) {
                 const int ntiles = (n + 15) / 16;
-                const int pt = (e->force_pt ? e->force_pt : (ntiles > 1024 ? 2 : 1));   // 1024 SIMDs: share B operands between two point tiles once every SIMD has work
+                const int pt = ntiles > 1024 ? 2 : 1;   // 1024 SIMDs: share B operands between two point tiles once every SIMD has work
                 const dim3 g2((n + 64 * pt - 1) / (64 * pt));
 #define DZ_MFMA_CASE(NRT_)                                                                                                                     \
     case NRT_:                                                                                                                                 \
@@ -406,26 +397,21 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
                     e->qpart_len = need * e->nlanes;
                 }
                 double* qpart = e->d_qpart + (size_t)sl * (e->qpart_len / e->nlanes);
-                if (e->force_big) hipLaunchKernelGGL(dz::k_logp_mvn_mfma_big<8>, dim3((n + 63) / 64), block, 0, st, e->p, pts, n, prior, like);
-                else {
-                    if (e->logp_gemm && n >= 512) {            // enough points to fill the chip with 64 x 64 block tiles
-                        const int nbn = (nrtb * 16 + 63) / 64;
-                        const size_t ldsm = e->p.mu_zero ? 0 : sizeof(double) * (size_t)e->p.ld;
-                        // Points per block (128 / 64 / 32): the kernel is bound by how many blocks a CU has in flight (each one is a
-                        // chain of barrier -> LDS reads -> MFMAs -> LDS store), so the largest tile that still leaves five blocks per
-                        // CU: 2560 points x 1000 rows: 32 points 65 us, 64 points 70 us, 128 points 98 us per launch.
-                        int bmsel = e->logp_bm;
-                        if (bmsel != 32 && bmsel != 64 && bmsel != 128)
-                            bmsel = ((n + 127) / 128) * nbn >= 5 * e->num_cu ? 128 : ((n + 63) / 64) * nbn >= 5 * e->num_cu ? 64 : 32;
-                        const dim3 gridg(((n + bmsel - 1) / bmsel) * nbn);
-                        if (bmsel == 32) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<1>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                        else if (bmsel == 64) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<2>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                        else hipLaunchKernelGGL(dz::k_logp_mvn_gemm<4>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                    } else
+                if (e->logp_gemm && n >= 512) {            // enough points to fill the chip with 64 x 64 block tiles
+                    const int nbn = (nrtb * 16 + 63) / 64;
+                    const size_t ldsm = e->p.mu_zero ? 0 : sizeof(double) * (size_t)e->p.ld;
+                    // Points per block (128 / 64 / 32): the kernel is bound by how many blocks a CU has in flight (each one is a
+                    // chain of barrier -> LDS reads -> MFMAs -> LDS store), so the largest tile that still leaves five blocks per
+                    // CU: 2560 points x 1000 rows: 32 points 65 us, 64 points 70 us, 128 points 98 us per launch.
+                    const int bmsel = ((n + 127) / 128) * nbn >= 5 * e->num_cu ? 128 : ((n + 63) / 64) * nbn >= 5 * e->num_cu ? 64 : 32;
+                    const dim3 gridg(((n + bmsel - 1) / bmsel) * nbn);
+                    if (bmsel == 32) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<1>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
+                    else if (bmsel == 64) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<2>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
+                    else hipLaunchKernelGGL(dz::k_logp_mvn_gemm<4>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
+                } else
                     hipLaunchKernelGGL((dz::k_logp_mvn_mfma_tiled<PT, RTC>), dim3((npg * nrg + 3) / 4), block, 0, st, e->p, pts, n, qpart);
-                    e->last_qpart = qpart;
-                    if (!defer_finish) hipLaunchKernelGGL(dz::k_q_finish, dim3((n + 63) / 64), dim3(64), 0, st, e->p, (const double*)qpart, n, nrtb, prior, like);
-                }
+                e->last_qpart = qpart;
+                if (!defer_finish) hipLaunchKernelGGL(dz::k_q_finish, dim3((n + 63) / 64), dim3(64), 0, st, e->p, (const double*)qpart, n, nrtb, prior, like);
             }
             if (e->p.have_prior) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_only<NCH>, grid, block, 0, st, e->p, pts, n, prior));
         }
@@ -823,7 +809,7 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
         }
     }
     // waves per block: 16 (one block fills a CU's 4 SIMDs evenly) once there is at least one such block per CU
-    const int wpb = e->nch >= 4 ? 4 : (e->waves_per_block ? e->waves_per_block : ((nc / L) >= 16 * e->num_cu ? 16 : 4));    // (k_propose<NCH >= 4> is built for 4-wave blocks)
+    const int wpb = e->nch >= 4 ? 4 : ((nc / L) >= 16 * e->num_cu ? 16 : 4);    // (k_propose<NCH >= 4> is built for 4-wave blocks)
     // one wave per (chain, try) pays when a try is long and the chains are few: d > 512 (measured at 512 x 1000-D: +17%;
     // at d <= 200 the per-chain wave with its fused Metropolis step is faster)
     const int split = e->propose_split > 0 ? e->propose_split : (e->nch >= 8 ? k : 1);
@@ -832,17 +818,17 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
     // the Metropolis step of this generation can ride in front of the next generation's proposal kernel when
     // nothing shared changes in between (no history append, no published positions) and a generation follows
     // ld > 256, one DE pair, multi-try: one wave per (chain, try) streaming over the dimension chunks (dz_kernels.h)
-    const bool streamed = e->stream_propose && e->nch >= 4 && p.depairs == 1 && k >= 3 && !redo_possible(e);     // (redraw rounds go through k_propose)
+    const bool streamed = e->nch >= 4 && p.depairs == 1 && k >= 3 && !redo_possible(e);     // (redraw rounds go through k_propose)
     const bool redo = redo_possible(e);         // (then the proposal set's evaluation is followed by a check on the host: nothing is deferred)
     const bool have_prop = streamed && full && e->stream_prop_gen == (int64_t)g;
     e->stream_prop_gen = -1;
     // ... and the streamed form of the same: accept(g) + proposal set(g+1) in one launch (k_accept_propose)
-    const bool fuse_next = streamed && e->fuse_stream && full && more_follow && !append && !publish && !e->tempering && k <= 16;
-    const bool defer = full && e->fuse && more_follow && !append && !publish && split == 1 && e->lk != LK_HOST && !e->tempering && !streamed && !redo;
+    const bool fuse_next = streamed && full && more_follow && !append && !publish && !e->tempering && k <= 16;
+    const bool defer = full && more_follow && !append && !publish && split == 1 && e->lk != LK_HOST && !e->tempering && !streamed && !redo;
     const int64_t zbase = full ? e->M : e->M - (int64_t)(p.off + c0);
     // large d: the row-tile sums of the likelihood product are added by the kernels that use them (no k_q_finish launches)
     // (round 5: also the per-chain proposal kernels of 128 < d <= 256 -- the reference example's own d = 200 --: two launches of six fewer)
-    const bool qdefer = e->q_defer && e->lk == LK_MVN && p.ld / 16 > 8 && !e->force_big && (streamed || (full && k >= 3 && !redo_possible(e) && e->nch < 4 && e->nlanes == 1));
+    const bool qdefer = e->q_defer && e->lk == LK_MVN && p.ld / 16 > 8 && (streamed || (full && k >= 3 && !redo_possible(e) && e->nch < 4 && e->nlanes == 1));
     p.qfin_p = nullptr; p.qfin_r = nullptr; p.qfin_nrt = (p.d + 15) / 16;
     for (int s = 0; s < L; ++s) {
         const int lc0 = c0 + (int)((int64_t)nc * s / L), lc1 = c0 + (int)((int64_t)nc * (s + 1) / L), lnc = lc1 - lc0;
@@ -919,7 +905,6 @@ struct MegaPlan { int ch, split_c, ch_b; };
 MegaPlan mega_plan(const dz_engine* e)
 {
     const dz::Params& p = e->p;
-    if (e->mega_ch) return MegaPlan{e->mega_ch, p.nl, 0};
     // One block per CU is resident (LDS), so a launch takes ceil(blocks / CUs) rounds of a block's time; measured at 100-D a block of 12
     // chains needs 0.82 (round 6), one of 8 chains 0.67 and one of 4 chains (four waves per chain) 0.49 of the time of a block of 16.  The
     // smallest product wins, the larger block on a tie: 4096 chains -> 16, 3072 -> 12 (round 6: 256 blocks of 12 -- 677 M proposals/s; as
@@ -930,9 +915,8 @@ MegaPlan mega_plan(const dz_engine* e)
     // last blocks drain, worth about 0.12 of a 16-chain block's time (5000 chains: 16 + 8 measured 39.8 us per generation, modelled without
     // the overlap 46.4; 12 + 8: 40.0; 417 blocks of 12 in two rounds: 43.1).
     const int ncu = e->num_cu > 0 ? e->num_cu : 1;
-    static const double c12 = getenv("DZ_COST12") ? atof(getenv("DZ_COST12")) : 0.82;
     const int cand[4] = {16, 12, 8, 4};
-    const double cost[4] = {1.0, c12, 0.67, 0.49};
+    const double cost[4] = {1.0, 0.82, 0.67, 0.49};
     const bool need_x = p.hard || p.have_prior || p.depairs > 1;          // (the full-code instantiations keep the states in LDS)
     const bool k1 = p.k == 1;
     bool fits[4];
@@ -945,7 +929,7 @@ MegaPlan mega_plan(const dz_engine* e)
         const int ch = cand[i], blocks = (p.nl + ch - 1) / ch, rounds = (blocks + ncu - 1) / ncu;
         const double t = rounds * cost[i];
         if (tb < 0.0 || t < tb - 1e-9) { best = MegaPlan{ch, p.nl, 0}; tb = t; }
-        if (!e->mega_split || k1 || ch < 12 || blocks <= ncu || blocks % ncu == 0) continue;
+        if (k1 || ch < 12 || blocks <= ncu || blocks % ncu == 0) continue;
         const int full = (blocks / ncu) * ncu * ch, r = p.nl - full;
         for (int j = i + 1; j < 4; ++j) {
             if (!fits[j]) continue;
@@ -967,7 +951,7 @@ void mega_set_pb_lds(dz_engine* e)
     const bool pb = e->p.hard || e->p.have_prior || e->p.depairs > 1 || (redo_possible(e) && e->lk == LK_MVN && e->p.k > 1 && e->mega_redo_on);
     e->p.pb_lds = 0;
     {   // uniform / flat priors whose supports contain the hard boundaries' box: the log prior of every proposal is one constant
-        bool cst = e->p.have_prior && e->p.prior_nonormal && e->p.hard && !getenv("DZ_PRIOR_CONST_OFF");
+        bool cst = e->p.have_prior && e->p.prior_nonormal && e->p.hard;
         for (size_t j = 0; cst && j < e->h_pkind.size(); ++j)
             if (e->h_pkind[j] == 2 && !(j < e->h_mins.size() && e->h_mins[j] >= e->h_pa[j] && e->h_maxs[j] <= e->h_pa[j] + e->h_pb[j])) cst = false;
         e->p.prior_const = cst ? 1 : 0;
@@ -982,8 +966,8 @@ bool mega_mix_eligible(const dz_engine* e)
 {
     const dz::Params& p = e->p;
     const bool pbm = p.hard || p.have_prior || p.depairs > 1;
-    return e->mega && (e->lk == LK_MIX || (e->lk == LK_MODULE && e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)])) && !redo_possible(e) && (!pbm || e->mega_mix_pb) &&
-           p.ld <= (e->mega_mix_wide ? 256 : 128) && (p.k == 1 || p.k >= 3) && p.k <= dz::MAXK &&
+    return e->mega && (e->lk == LK_MIX || (e->lk == LK_MODULE && e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)])) && !redo_possible(e) &&
+           p.ld <= 256 && (p.k == 1 || p.k >= 3) && p.k <= dz::MAXK &&
            p.nslots <= 64 && p.J <= 32;
 }
 // redraw rounds inside the persistent kernel: the instantiations with the full proposal code, multi-try, device MVN likelihood
@@ -997,7 +981,7 @@ bool mega_redo(const dz_engine* e) { return redo_possible(e) && e->lk == LK_MVN 
 bool mega_d2_two_pass(const dz_engine* e, int ch = 16)
 {
     const dz::Params& p = e->p;
-    if (p.ld <= 128 || p.k < 3 || p.nslots > 64 || (getenv("DZ_MEGA_D2_SP") && atoi(getenv("DZ_MEGA_D2_SP")) == 0)) return false;
+    if (p.ld <= 128 || p.k < 3 || p.nslots > 64) return false;
     if (sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, ch, false, false, true).total <= (size_t)160 * 1024) return false;
     return sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, ch, false, false, true, 0, true).total <= (size_t)160 * 1024;
 }
@@ -1009,7 +993,7 @@ int mega_d2_chains(const dz_engine* e)
     // (round 6) more than 15 tries: a generation's draw slots exceed a wave's lanes, the classic kernels do not take them; this one keeps one phase's
     // slots at a time (k npt <= 64: up to 32 tries with one or two DE pairs)
     const bool bigk = p.nslots > 64;
-    if (bigk && (p.k * p.npt > 64 || p.k > dz::MAXK || (getenv("DZ_MEGA_BIGK") && atoi(getenv("DZ_MEGA_BIGK")) == 0))) return 0;
+    if (bigk && (p.k * p.npt > 64 || p.k > dz::MAXK)) return 0;
     if (p.ld <= 128 && !bigk) {      // d <= 128: only where the classic kernel's 16-chain layout (matrix in LDS) does not fit -- it then runs 8 chains per block (113..128
                             // dimensions at 5 tries, 100 dimensions at 8 or more)
         const bool pbx = p.hard || p.have_prior || p.depairs > 1;
@@ -1028,12 +1012,12 @@ int mega_d2_chains(const dz_engine* e)
         const bool pbx = p.hard || p.have_prior || p.depairs > 1;
         if (sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, pbx, 8, pbx && p.pb_lds != 0).total <= (size_t)160 * 1024) return 0;
     }
-    if (p.k >= 3 && !(getenv("DZ_MEGA_D2_W2") && atoi(getenv("DZ_MEGA_D2_W2")) == 0) &&
+    if (p.k >= 3 &&
         sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, 8, false, false, true).total <= (size_t)160 * 1024) return 8;
-    if (p.k >= 3 && !(getenv("DZ_MEGA_D2_W2") && atoi(getenv("DZ_MEGA_D2_W2")) == 0) && mega_d2_two_pass(e, 8)) return 8;      // 8 x 2 with the two-pass set (256 dimensions at 8 tries)
+    if (p.k >= 3 && mega_d2_two_pass(e, 8)) return 8;      // 8 x 2 with the two-pass set (256 dimensions at 8 tries)
     // ... and 4 chains x 4 waves where not even those fit (24..32 tries at 100 dimensions, 20..32 at 128, 8 at 256): four rounds of 1024 blocks at 4096
     // chains, still ahead of the multi-kernel path
-    if (p.k >= 4 && !(getenv("DZ_MEGA_D2_W4") && atoi(getenv("DZ_MEGA_D2_W4")) == 0) &&
+    if (p.k >= 4 &&
         sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, 4, false, false, true).total <= (size_t)160 * 1024) return 4;
     return 0;
 }
@@ -1095,10 +1079,10 @@ size_t mvn_multi_lds(const dz_engine* e)
 // published positions and ONE k_adapt_partials_ring launch behind it makes the sums of all its generations;  0: one burn-in generation per launch
 int burnin_multi(const dz_engine* e)
 {
-    if (!e->ad_multi || !e->mega_burnin || e->tempering) return 0;
+    if (!e->ad_multi || e->tempering) return 0;
     const dz::Params& p = e->p;
     const size_t tab = sizeof(double) * (size_t)e->ad_R1 * e->ad_nbp, cap = (size_t)160 * 1024;
-    const bool ring_ok = e->ad_ring && sizeof(double) * (size_t)(e->c.adapt_lag + 2) * p.N * p.ld <= ((size_t)8 << 30);
+    const bool ring_ok = sizeof(double) * (size_t)(e->c.adapt_lag + 2) * p.N * p.ld <= ((size_t)8 << 30);
     if (e->lk == LK_MIX || e->lk == LK_MODULE) {
         if (!mega_mix_eligible(e)) return 0;
         if (e->lk == LK_MIX && e->adapt_fused && p.k >= 3 && p.ld <= 128 && mix_multi_lds(e) <= cap) return 1;
@@ -1129,9 +1113,8 @@ int mega_segment(const dz_engine* e, uint32_t g, int64_t remaining)
     // (adapt_lag = L >= 1, one GPU, a kernel that makes its units' sums generation by generation: burnin_multi) up to L + 1 of them
     const bool pub0 = publishing(e, g);
     if (e->tempering) return remaining > 0 ? 1 : 0;       // parallel tempering: a temperature swap follows every generation (core.py:185-221)
-    if (pub0 && !burnin_multi(e)) return (e->mega_burnin && remaining > 0) ? 1 : 0;
-    if (pub0 && !e->mega_burnin) return 0;
-    const int maxg = pub0 ? std::min(e->c.adapt_lag + 1, e->mega_max_gen) : e->mega_max_gen;
+    if (pub0 && !burnin_multi(e)) return remaining > 0 ? 1 : 0;
+    const int maxg = pub0 ? e->c.adapt_lag + 1 : MEGA_MAX_GEN;      // (adapt_lag <= 1023: dz_create)
     // A launch ends with a history append -- unless the rows it writes are not sampleable yet anyway (history_lag >= 1, every lagged append
     // already made): the kernel then makes the append itself and runs on, up to mega_appends_per_launch of them (the generations behind the
     // j-th one sample j * N more rows: all of them written -- and, sharded, received -- before the launch).
@@ -1338,7 +1321,7 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
         // the instantiations live in one translation unit per row-tile count (dz_mega_tu.hip)
         dz::MegaLaunch ml;
         ml.tri = p.tri != 0; ml.xlds = pb ? true : xlds; ml.pb = pb; ml.k1 = k1; ml.ch = chp; ml.wpc = wpcp; ml.redo = mega_redo(e);
-        ml.ahead = e->mega_w4 && chp == 4 && wpcp == 4 && !pb && xlds && !k1 && p.k >= 3 && p.k <= 6;
+        ml.ahead = chp == 4 && wpcp == 4 && !pb && xlds && !k1 && p.k >= 3 && p.k <= 6;
         ml.multi = multi;
         ml.grid = dim3((c1 - c0 + chp - 1) / chp); ml.block = dim3(64 * chp * wpcp); ml.lds = ldsp; ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
         ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = (uint32_t)visible_rows(e); ml.slot0 = slot0; ml.zappend = append_last ? e->M : (int64_t)-1; ml.seg0 = seg0; ml.publish = &pp;
@@ -1363,6 +1346,24 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
     DZCK(after_launch());
     if (slot0 >= 0) e->ntrace += n;
     return 0;
+}
+
+// The engine's path switches: environment variables that force or forbid a path for the tests and measurements, read once when the engine is
+// made.  The selection logic reads only the fields set here.  _capi.ENGINE_SWITCHES lists the same names (every rank of a sharded run must agree).
+void read_switches(dz_engine* e)
+{
+    if (const char* kv = getenv("DZ_MEGA")) e->mega = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_MEGA_D2")) e->mega_d2 = atoi(kv);
+    if (const char* kv = getenv("DZ_MEGA_SEGS")) e->mega_segs = std::max(1, atoi(kv));
+    if (const char* kv = getenv("DZ_MEGA_REDO")) e->mega_redo_on = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_MEGA_USER")) e->mega_user = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_PROPOSE_SPLIT")) e->propose_split = atoi(kv);
+    if (const char* kv = getenv("DZ_LOGP_GEMM")) e->logp_gemm = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_QFIN")) e->q_defer = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_STREAMS")) e->nlanes = atoi(kv);      // (chain groups on separate streams: clamped in dz_create)
+    if (const char* kv = getenv("DZ_ADAPT_FUSED")) e->adapt_fused = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_ADAPT_MULTI")) e->adapt_multi_on = atoi(kv) != 0;
+    if (const char* kv = getenv("DZ_ADAPT_GROUPS")) e->adapt_groups_on = atoi(kv) != 0;
 }
 
 }  // namespace
@@ -1401,28 +1402,8 @@ int dz_create(const dz_config* cfg, dz_engine** out)
     dz_engine* e = new dz_engine();
     e->c = *cfg;
     e->gen_c.assign((size_t)cfg->nchains_local, 0);
-    if (const char* kv = getenv("DZ_FUSE")) e->fuse = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_STREAM")) e->stream_propose = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA")) e->mega = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_MAXGEN")) e->mega_max_gen = std::max(1, atoi(kv));
-    if (const char* kv = getenv("DZ_MEGA_SEGS")) e->mega_segs = std::max(1, atoi(kv));
-    if (const char* kv = getenv("DZ_MEGA_BURNIN")) e->mega_burnin = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_REDO")) e->mega_redo_on = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_ADAPT_FUSED")) e->adapt_fused = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_MIX_PB")) e->mega_mix_pb = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_SPLIT")) e->mega_split = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_ADAPT_RING")) e->ad_ring = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_MIX_WIDE")) e->mega_mix_wide = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_W4")) e->mega_w4 = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_MEGA_D2")) e->mega_d2 = atoi(kv);
     static_assert(dz::DZ_MAX_REDRAWS_DEV == DZ_MAX_REDRAWS && dz::DZ_REDRAW_KEY_STEP_DEV == DZ_REDRAW_KEY_STEP, "redraw constants");
-    if (const char* kv = getenv("DZ_QFIN")) e->q_defer = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_FUSE_STREAM")) e->fuse_stream = atoi(kv) != 0;
-    if (const char* kv = getenv("DZ_LOGP_BM")) e->logp_bm = atoi(kv);          // 64 / 128: points per block of k_logp_mvn_gemm (default: by size)
-    if (const char* kv = getenv("DZ_MEGA_CHAINS")) { const int v = atoi(kv); e->mega_ch = (v == 16 || v == 12 || v == 8 || v == 4) ? v : 0; }
-    if (const char* kv = getenv("DZ_WPB")) e->waves_per_block = atoi(kv);
-    if (const char* kv = getenv("DZ_PROPOSE_SPLIT")) e->propose_split = atoi(kv);
-    if (const char* kv = getenv("DZ_MFMA_PT")) e->force_pt = atoi(kv) == 2 ? 2 : atoi(kv) == 1 ? 1 : 0;
+    read_switches(e);
     dz::Params& p = e->p;
     p.N = cfg->nchains; p.nl = cfg->nchains_local; p.off = cfg->chain_offset; p.d = cfg->ndim;
     p.ld = (cfg->ndim + 15) / 16 * 16;
@@ -1443,25 +1424,14 @@ int dz_create(const dz_config* cfg, dz_engine** out)
     e->nch = chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 4 ? 4 : 8;
     e->adapt = cfg->adapt_crossover || cfg->adapt_gamma;
     e->world = cfg->nchains / cfg->nchains_local; e->rank = cfg->chain_offset / cfg->nchains_local;
-    if (const char* cm = (getenv("DZ_CUMASK") && *getenv("DZ_CUMASK")) ? getenv("DZ_CUMASK") : nullptr) {      // measurement switch: every kernel of the engine on the first DZ_CUMASK compute units of each XCD-interleaved numbering
-        const int ncu = std::max(1, atoi(cm));
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < ncu && i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
-        HIPCK(hipExtStreamCreateWithCUMask(&e->stream, 8, mask));
-    } else
     HIPCK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     {
-        int nl_req = 1;     // chain groups on separate streams; 2 gains ~3% at 4096 chains but shows occasional 2x-slow passes
-        if (const char* ev = getenv("DZ_STREAMS")) nl_req = atoi(ev);
-        e->nlanes = std::max(1, std::min(8, nl_req));
+        // chain groups on separate streams (DZ_STREAMS, default 1): 2 gains ~3% at 4096 chains but shows occasional 2x-slow passes
+        e->nlanes = std::max(1, std::min(8, e->nlanes));
         if (cfg->nchains_local < 64 * e->nlanes) e->nlanes = 1;
         e->lane_stream[0] = e->stream;
         for (int s = 1; s < e->nlanes; ++s) HIPCK(hipStreamCreateWithFlags(&e->lane_stream[s], hipStreamNonBlocking));
         for (int s = 0; s < e->nlanes; ++s) HIPCK(hipEventCreateWithFlags(&e->lane_ev[s], hipEventDisableTiming));
-        if (const char* ra = getenv("DZ_RUNAHEAD")) e->ra_stride = std::max(0, atoi(ra));
-        if (const char* fb = getenv("DZ_LOGP_BIG")) e->force_big = atoi(fb) != 0;
-        if (const char* fg = getenv("DZ_LOGP_GEMM")) e->logp_gemm = atoi(fg) != 0;
-        if (const char* lw = getenv("DZ_LOGP_WAVES")) e->logp_waves = std::max(4, std::min(8, atoi(lw)));
         for (int s = 0; s < 4; ++s) HIPCK(hipEventCreateWithFlags(&e->ra_ev[s], hipEventDisableTiming));
     }
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cu = prop.multiProcessorCount; }
@@ -1497,10 +1467,9 @@ int dz_create(const dz_config* cfg, dz_engine** out)
         // adapt_lag = L >= 1: rings of L + 1 generations (engine fields ad_*); several burn-in generations per launch on one GPU (ad_multi)
         e->ad_R1 = cfg->adapt_lag + 1; e->ad_nbp = (cfg->ncr + cfg->ngamma + 1) & ~1;
         // sharded, and this rank owns whole groups of 256 chains (then every rank does: equal shards): the burn-in exchanges group sums
-        const bool groups_on = !(getenv("DZ_ADAPT_GROUPS") && atoi(getenv("DZ_ADAPT_GROUPS")) == 0);
-        const bool groups = e->world > 1 && groups_on && p.off % 256 == 0 && p.nl % 256 == 0;
+        const bool groups = e->world > 1 && e->adapt_groups_on && p.off % 256 == 0 && p.nl % 256 == 0;
         // (several GPUs: only ranks that exchange group sums -- the records of a launch's generations travel in one exchange, adapt_finish_groups)
-        e->ad_multi = cfg->adapt_lag > 0 && (e->world == 1 || groups) && !(getenv("DZ_ADAPT_MULTI") && atoi(getenv("DZ_ADAPT_MULTI")) == 0);
+        e->ad_multi = cfg->adapt_lag > 0 && (e->world == 1 || groups) && e->adapt_multi_on;
         e->ad_tot_stride = cfg->adapt_lag > 0 ? nq * ld : 0;
         e->ad_pr_stride = units * nq * ld; e->ad_pc_stride = units * (size_t)(cfg->ncr + cfg->ngamma);
         const size_t prs = e->ad_multi ? (size_t)e->ad_R1 : 1;
@@ -1677,7 +1646,6 @@ int dz_set_prior(dz_engine* e, const int32_t* kind, const double* a, const doubl
         for (int j = 0; j < d; ++j) { c2[j] = kind[j] == 1 ? 1.0 / b[j] : (kind[j] == 2 ? a[j] + b[j] : 0.0); normal = normal || kind[j] == 1; }
         HIPCK(hipMemcpy(e->d_pc2, c2.data(), sizeof(double) * d, hipMemcpyHostToDevice));
         e->p.prior_nonormal = normal ? 0 : 1;
-        if (const char* kv = getenv("DZ_PRIOR_NONORMAL")) if (!atoi(kv)) e->p.prior_nonormal = 0;      // (measurement: the general butterfly form)
     }
     hipLaunchKernelGGL(dz::k_prior_consts, dim3((d + 127) / 128), dim3(128), 0, e->stream, (const double*)e->d_pb, d, e->d_plogb);
     DZCK(launch_check("k_prior_consts"));
@@ -1753,7 +1721,7 @@ int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const c
     if (hipModuleGetFunction(&gen[1], mod, "dz_user_generations_full_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[1] = nullptr; }
     if (hipModuleGetFunction(&gen[2], mod, "dz_user_generations_wide_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[2] = nullptr; }
     if (hipModuleGetFunction(&gen[3], mod, "dz_user_generations_wide_full_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[3] = nullptr; }
-    if (getenv("DZ_MEGA_USER") && atoi(getenv("DZ_MEGA_USER")) == 0) for (auto& gfn : gen) gfn = nullptr;
+    if (!e->mega_user) for (auto& gfn : gen) gfn = nullptr;
     // the new data block first, into a temporary: the engine's module, function and data change together, and only once every step has
     // succeeded -- a failure leaves the engine as it was (advisor, round 5)
     void* d_new = nullptr;
@@ -2083,10 +2051,10 @@ int dz_step(dz_engine* e, int64_t generations)
         const int n = mega ? mega_segment(e, (uint32_t)e->gen, generations - i) : 0;
         if (n > 0) { DZCK(run_mega_segment(e, (uint32_t)e->gen, n, i + n < generations && mega_segment(e, (uint32_t)e->gen + (uint32_t)n, 1) > 0)); i += n; }
         else { DZCK(one_generation(e, 0, e->p.nl, (uint32_t)e->gen, true, i + 1 < generations && !(mega && mega_segment(e, (uint32_t)e->gen + 1, 1) > 0))); i += 1; }
-        if (e->ra_stride > 0 && (++e->ra_n % e->ra_stride) == 0) {
+        if ((++e->ra_n % RA_STRIDE) == 0) {
             // keep the launch queue short: thousands of queued dispatches exhaust the runtime's kernarg/signal pools
             // and the whole pass then runs several times slower (measured; DESIGN.md "Host run-ahead")
-            const int slot = (int)((e->ra_n / e->ra_stride) & 3), oldest = (slot + 1) & 3;
+            const int slot = (int)((e->ra_n / RA_STRIDE) & 3), oldest = (slot + 1) & 3;
             HIPCK(hipEventRecord(e->ra_ev[slot], e->lane_stream[0]));
             e->ra_used[slot] = true;
             if (e->ra_used[oldest]) HIPCK(hipEventSynchronize(e->ra_ev[oldest]));

@@ -1315,63 +1315,6 @@ __global__ __launch_bounds__(512) void k_logp_mvn_lds(Params p, const double* __
     }
 }
 
-// any ld <= 1024: row tiles RTC at a time, operands fetched one k-step ahead
-template <int RTC>
-__global__ __launch_bounds__(256) void k_logp_mvn_mfma_big(Params p, const double* __restrict__ pts, int npts, double* prior_out, double* like_out)
-{
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int p0 = (blockIdx.x * 4 + wv) * 16;
-    if (p0 >= npts) return;
-    const int pi = l & 15, kq = l >> 4;
-    const int ld = p.ld, d = p.d;
-    const double* xrow = pts + (size_t)min(p0 + pi, npts - 1) * ld;
-    const int KS = (d + 3) >> 2, NRT = (d + 15) >> 4;
-    double Q = 0.0;
-    for (int rt0 = 0; rt0 < NRT; rt0 += RTC) {
-        dz_double4 acc[RTC];
-#pragma unroll
-        for (int t = 0; t < RTC; ++t) acc[t] = dz_double4{0.0, 0.0, 0.0, 0.0};
-        const int ks0 = p.tri ? 4 * rt0 : 0;
-        double a_n = xrow[4 * ks0 + kq] - p.mu[4 * ks0 + kq];
-        double b_n[RTC];
-#pragma unroll
-        for (int t = 0; t < RTC; ++t) b_n[t] = p.Mt[(size_t)(4 * ks0 + kq) * ld + 16 * min(rt0 + t, NRT - 1) + pi];
-        for (int ks = ks0; ks < KS; ++ks) {
-            const double a = a_n;
-            double b[RTC];
-#pragma unroll
-            for (int t = 0; t < RTC; ++t) b[t] = b_n[t];
-            if (ks + 1 < KS) {
-                const int c = 4 * (ks + 1) + kq;
-                a_n = xrow[c] - p.mu[c];
-#pragma unroll
-                for (int t = 0; t < RTC; ++t) b_n[t] = p.Mt[(size_t)c * ld + 16 * min(rt0 + t, NRT - 1) + pi];
-            }
-#pragma unroll
-            for (int t = 0; t < RTC; ++t) {
-                const int rt = rt0 + t;
-                if (rt < NRT && (!p.tri || ks >= 4 * rt)) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(b[t], a, acc[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < RTC; ++t) {
-            if (rt0 + t < NRT) {
-                double sv[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const int r = 16 * (rt0 + t) + kq + 4 * e; sv[e] = p.tri ? acc[t][e] : xrow[r] - p.mu[r]; }
-                Q = Q + tile_q(acc[t], sv, 16 * (rt0 + t) + kq, d);
-            }
-        }
-    }
-    {
-        const int pt = p0 + pi;
-        if (kq == 0 && pt < npts) {
-            like_out[pt] = nan_to_ninf(p.logF - 0.5 * Q);
-            if (!p.have_prior) prior_out[pt] = 0.0;
-        }
-    }
-}
-
 // Large d (ld > 128): the quadratic form as a tiled product.  One wave owns PT point tiles x RTC row tiles and walks k
 // once (B operands shared by the PT tiles, A operands by the RTC row tiles); the grid covers point-tile groups x
 // row-tile groups, so 2560 points x 63 row tiles give 1280 waves instead of the 160 of the one-wave-per-point-tile

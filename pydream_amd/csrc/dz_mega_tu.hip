@@ -115,9 +115,6 @@ static const char* launch_ch(const MegaLaunch& a)
             return TRI ? "k_generations_w4<" DZ_STR(DZ_TU_NRT) ",tri,xlds,%d,%d,lean,ahead>" : "k_generations_w4<" DZ_STR(DZ_TU_NRT) ",dense,xlds,%d,%d,lean,ahead>";
         }
     }
-#ifdef DZ_TU_W4ONLY    // (compile-time experiments on k_generations_w4 alone)
-    return nullptr;
-#else
 #ifdef DZ_TU_FAST      // experiment builds (tools/fastbuild.sh): multi-try only, 16 chains per block or 4 x 4 waves -- a third of the instantiations
     if (a.ch == 4) return launch_one<TRI, X, 4, 4, PB, false>(a);
     return launch_one<TRI, X, 16, 1, PB, false>(a);
@@ -131,7 +128,6 @@ static const char* launch_ch(const MegaLaunch& a)
     if (a.ch == 12) return launch_one<TRI, X, 12, 1, PB, false>(a);      // (round 6: 2049 .. 3072 chains on 256 CUs -- multi-try only)
     if (a.ch == 8) return launch_one<TRI, X, 8, 1, PB, false>(a);
     return launch_one<TRI, X, 4, 4, PB, false>(a);
-#endif
 }
 
 // (priors / boundaries / several pairs: only with the chain states in LDS -- mega_eligible -- which keeps the number of kernels down)

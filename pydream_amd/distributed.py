@@ -409,12 +409,12 @@ def attach_transport(engine, rank, world, transport="rccl", group=None):
     except Exception as ex:
         err = "%s" % ex
     # ... and (advisor, round 5) what decides WHAT the ranks exchange must be the same everywhere: the sampler's configuration, and the
-    # environment switches the engine read at dz_create (whether the burn-in exchanges group sums or positions, how many appends a launch
-    # holds) -- ranks that disagree would issue all-gathers of different sizes and kinds, which hangs or corrupts silently
+    # engine's path switches (_capi.ENGINE_SWITCHES: whether the burn-in exchanges group sums or positions, how many appends a launch holds,
+    # ...) -- ranks that disagree would issue all-gathers of different sizes and kinds, which hangs or corrupts silently
     cfg = getattr(engine, "cfg", None)
     sig = tuple(int(getattr(cfg, f)) for f in ("nchains", "nchains_local", "ndim", "multitry", "depairs", "ncr", "ngamma", "history_thin", "crossover_burnin",
                                                 "adapt_crossover", "adapt_gamma", "history_lag", "adapt_lag", "seed") if cfg is not None and hasattr(cfg, f)) + \
-        tuple(os.environ.get(v, "") for v in ("DZ_ADAPT_GROUPS", "DZ_ADAPT_FUSED", "DZ_MEGA", "DZ_MEGA_BURNIN"))
+        tuple(os.environ.get(v, "") for v in _capi.ENGINE_SWITCHES)
     got = _gather_objects((boot if not err else None, sig), group)
     boots = [g[0] for g in got]
     if not err and any(g[1] != sig for g in got):

@@ -45,3 +45,24 @@ def test_no_silent_cpu_fallback(lib):
         pytest.skip("a GPU is present")
     with pytest.raises(_capi.DreamZSError, match="no HIP device|no CPU fallback"):
         _capi.Engine(nchains=4, ndim=3, history_capacity=16)
+
+
+# the environment settings the engine reads that do not choose a path (time limits, the RCCL library, host threads): they may differ by rank
+OPERATIONAL_SETTINGS = {"DZ_PEER_TIMEOUT_S", "DZ_PEER_SELFTEST_S", "DZ_RCCL_LIB", "DZ_RCCL_ALLOW_MISMATCH", "DZ_PIN_THREADS"}
+
+
+def test_engine_switches_are_the_ones_the_engine_reads():
+    """Every getenv("DZ_...") in the engine's source is a path switch of _capi.ENGINE_SWITCHES -- which the ranks of a sharded run must agree
+    on -- or one of the operational settings; the path switches are read in read_switches (dz_engine.hip) and nowhere else."""
+    csrc = os.path.join(ROOT, "pydream_amd", "csrc")
+    found, outside = set(), set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        txt = open(os.path.join(csrc, f)).read()
+        found |= set(re.findall(r'getenv\("(DZ_\w+)"\)', txt))
+        body = re.search(r"\nvoid read_switches\(dz_engine\* e\)\n\{\n(.*?)\n\}\n", txt, flags=re.S)
+        outside |= set(re.findall(r'getenv\("(DZ_\w+)"\)', txt[:body.start()] + txt[body.end():] if body else txt))
+    assert len(_capi.ENGINE_SWITCHES) == len(set(_capi.ENGINE_SWITCHES))
+    assert found == set(_capi.ENGINE_SWITCHES) | OPERATIONAL_SETTINGS
+    assert outside == OPERATIONAL_SETTINGS

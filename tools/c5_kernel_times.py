@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel event times of the configs[4] shard (512 chains x 1000-D, multitry 5) over 100 generations -- with DZ_CUMASK=<n> every kernel of
-the engine runs on n compute units: what the likelihood product loses on 224 CUs and what the streamed proposal kernels need on 32 is the
-arithmetic behind running them side by side.  usage: [DZ_CUMASK=n] python tools/c5_kernel_times.py"""
+"""Per-kernel event times of the configs[4] shard (512 chains x 1000-D, multitry 5) over 100 generations.
+usage: python tools/c5_kernel_times.py"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -18,7 +17,7 @@ t0 = time.perf_counter(); e.step(gens); e.sync(); dt = time.perf_counter() - t0
 e.profile_enable(True, prealloc_pairs=16 * gens); e.profile_reset()
 e.step(gens); e.sync()
 e.profile_enable(False)
-print("DZ_CUMASK=%s  %.1f us per generation (%.2f M proposals/s)" % (os.environ.get("DZ_CUMASK", "-"), 1e6 * dt / gens, N * k * gens / dt / 1e6))
+print("%.1f us per generation (%.2f M proposals/s)" % (1e6 * dt / gens, N * k * gens / dt / 1e6))
 for name in ("propose", "logp", "accept"):
     each = 1e3 * e.profile_get_list(name)
     print("  %-8s %4d launches  median %.1f us  mean %.1f us" % (name, len(each), np.median(each), each.mean()))

@@ -2,7 +2,7 @@
 the quantisation by rounds of blocks (one block per CU is resident: 5000 chains are 313 blocks = two rounds)."""
 import os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from pydream_amd import _capi as G
 d, k = 100, 5
 i = np.arange(1, d + 1.0)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """4096 chains x 100-D three-component mixture with uniform priors + hard boundaries / normal priors / DEpairs = 3: the mixture kernel's
-full-code instantiation (DZ_MEGA_MIX_PB=0: the multi-kernel path these configurations took before round 4)."""
+full-code instantiation."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
