@@ -1,0 +1,404 @@
+// dz_ode.h -- the stiff solver behind likelihoods.MassActionODELogLike: one lane (or one host loop iteration) integrates one point's
+// mass-action network from t0 through every output time with an L-stable, stiffly accurate Rosenbrock pair (Rodas4, Hairer & Wanner,
+// "Solving ODEs II", IV.7) and adds each output time's Gaussian residuals as it lands on it.
+//
+// The network itself comes from generated code (likelihoods._ode_source): a struct with
+//     static constexpr int S, R, O;                                    species, reactions, observables (compile-time)
+//     static bool rates(const double* x, double* k);                   k[R] from the point; false if one is not finite
+//     static void rhs(const double* k, const double* y, double* f);    f = N v(y), straight-line code
+//     static void jac(const double* k, const double* y, double* J);    J[S*S] (row-major) = N dv/dy, every entry written
+//     static void obs(const double* y, double* o);                     o[O]
+// The same translation unit is compiled for gfx950 (hipcc --genco) and for the host (clang++ / g++), both with -ffp-contract=off. The
+// code uses only + - * /, explicit fma inside dexp / dlog below, comparisons and integer bit operations: no libm or ocml call, no sqrt
+// (the error norm's root is folded into the controller's exponent), so both builds give the same bits for every point.
+//
+// Data block (doubles), built by the Python class:
+//   [0] C = sum over the observed entries of (-log sd - log(2 pi) / 2)    [1] rtol   [2] atol   [3] max_steps   [4] t0   [5] T
+//   [6, 6+S) y0,   then t[T],   data[T*O] (time-major),   sd[T*O]   (an unobserved entry: data 0, sd +inf -- it adds exactly 0)
+//
+// Every loop is bounded: at most max_steps attempted steps per output interval, T intervals.
+#pragma once
+#if defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define DZO_HD __host__ __device__ __forceinline__
+#else
+#define DZO_HD inline
+#endif
+#include <stdint.h>
+#include <string.h>
+
+namespace dzode {
+
+// ---------------------------------------------------------------- elementary functions
+// The engine's dexp / dlog (dz_device.h) and the oracle's orc_exp / orc_log restated for host and device: the same operation sequence
+// (fma is correctly rounded on both sides), without dz_device.h's scalar-register constant tricks, which only change instruction selection.
+DZO_HD double bits2d(uint64_t b) { double d; memcpy(&d, &b, 8); return d; }
+DZO_HD uint64_t d2bits(double d) { uint64_t b; memcpy(&b, &d, 8); return b; }
+DZO_HD double dfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+DZO_HD double dfloor(double y)            // |y| < 2^62 (dexp's argument range): exact
+{
+    const double t = (double)(long long)y;
+    return t > y ? t - 1.0 : t;
+}
+
+DZO_HD double dexp(double x)
+{
+    if (x != x) return x;
+    if (x > 709.782712893384) return __builtin_huge_val();
+    if (x < -745.2) return 0.0;
+    const double kf = dfloor(x * 1.4426950408889634 + 0.5);
+    double r = dfma(-kf, 6.93147180369123816490e-01, x);
+    r = dfma(-kf, 1.90821492927058770002e-10, r);
+    double p = 1.0 / 6227020800.0;
+    p = dfma(p, r, 1.0 / 479001600.0);
+    p = dfma(p, r, 1.0 / 39916800.0);
+    p = dfma(p, r, 1.0 / 3628800.0);
+    p = dfma(p, r, 1.0 / 362880.0);
+    p = dfma(p, r, 1.0 / 40320.0);
+    p = dfma(p, r, 1.0 / 5040.0);
+    p = dfma(p, r, 1.0 / 720.0);
+    p = dfma(p, r, 1.0 / 120.0);
+    p = dfma(p, r, 1.0 / 24.0);
+    p = dfma(p, r, 1.0 / 6.0);
+    p = dfma(p, r, 0.5);
+    p = dfma(p, r, 1.0);
+    p = dfma(p, r, 1.0);
+    int k = (int)kf;
+    if (k < -1000) { p = p * bits2d((uint64_t)(1023 - 1000) << 52); k += 1000; }
+    return p * bits2d((uint64_t)(k + 1023) << 52);
+}
+
+DZO_HD double dlog(double x)
+{
+    if (x != x) return x;
+    if (x < 0.0) return __builtin_nan("");
+    if (x == 0.0) return -__builtin_huge_val();
+    if (x == __builtin_huge_val()) return x;
+    int e = 0;
+    uint64_t b = d2bits(x);
+    if ((b >> 52) == 0) { x = x * 18014398509481984.0; e = -54; b = d2bits(x); }
+    e += (int)(b >> 52) - 1023;
+    double m = bits2d((b & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+    if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
+    const double f = m - 1.0;
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    double p = 1.0 / 23.0;
+    p = dfma(p, z, 1.0 / 21.0);
+    p = dfma(p, z, 1.0 / 19.0);
+    p = dfma(p, z, 1.0 / 17.0);
+    p = dfma(p, z, 1.0 / 15.0);
+    p = dfma(p, z, 1.0 / 13.0);
+    p = dfma(p, z, 1.0 / 11.0);
+    p = dfma(p, z, 1.0 / 9.0);
+    p = dfma(p, z, 1.0 / 7.0);
+    p = dfma(p, z, 1.0 / 5.0);
+    p = dfma(p, z, 1.0 / 3.0);
+    const double t = 2.0 * s;
+    const double lm = dfma(t * z, p, t);
+    const double ef = (double)e;
+    return dfma(ef, 6.93147180369123816490e-01, dfma(ef, 1.90821492927058770002e-10, lm));
+}
+
+DZO_HD bool finite(double x) { return x - x == 0.0; }
+DZO_HD double dabs(double x) { return x < 0.0 ? -x : x; }
+DZO_HD double dmax(double a, double b) { return a > b ? a : b; }
+DZO_HD double dmin(double a, double b) { return a < b ? a : b; }
+
+// ---------------------------------------------------------------- dense LU with partial pivoting, unrolled at compile-time S
+// a[S*S] row-major, factored in place; the diagonal holds the pivots' reciprocals.  Rows are exchanged with selects over every
+// candidate row, so every array index is a constant after unrolling: the matrix lives in registers.  False if a pivot is zero.
+template <int S>
+DZO_HD bool lu_factor(double* a, int* piv)
+{
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        int p = k;
+        double best = dabs(a[k * S + k]);
+#pragma unroll
+        for (int r = k + 1; r < S; ++r) {
+            const double v = dabs(a[r * S + k]);
+            if (v > best) { best = v; p = r; }
+        }
+        piv[k] = p;
+#pragma unroll
+        for (int r = k + 1; r < S; ++r) {
+            const bool sw = p == r;
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                const double u = a[k * S + c], w = a[r * S + c];
+                a[k * S + c] = sw ? w : u;
+                a[r * S + c] = sw ? u : w;
+            }
+        }
+        ok = ok && best != 0.0;
+        const double inv = 1.0 / a[k * S + k];
+        a[k * S + k] = inv;
+#pragma unroll
+        for (int r = k + 1; r < S; ++r) {
+            const double l = a[r * S + k] * inv;
+            a[r * S + k] = l;
+#pragma unroll
+            for (int c = k + 1; c < S; ++c) a[r * S + c] = a[r * S + c] - l * a[k * S + c];
+        }
+    }
+    return ok;
+}
+
+template <int S>
+DZO_HD void lu_solve(const double* a, const int* piv, double* b)
+{
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < S; ++r) {
+            const bool sw = piv[k] == r;
+            const double u = b[k], w = b[r];
+            b[k] = sw ? w : u;
+            b[r] = sw ? u : w;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < S; ++r) b[r] = b[r] - a[r * S + k] * b[k];
+    }
+#pragma unroll
+    for (int k = S - 1; k >= 0; --k) {
+        double s = b[k];
+#pragma unroll
+        for (int c = k + 1; c < S; ++c) s = s - a[k * S + c] * b[c];
+        b[k] = s * a[k * S + k];
+    }
+}
+
+// ---------------------------------------------------------------- Rodas4
+// Hairer & Wanner's RODAS coefficients (METH = 1), for an autonomous system (mass action: no explicit t, so the d_i terms vanish).
+// Stages: W k_i = f(y + sum_j a_ij k_j) + (1/h) sum_j c_ij k_j, W = I / (h gamma) - J.  y5 + k5 is the embedded (order 3) solution,
+// y5 + k5 + k6 the order-4 one; both stiffly accurate.  k6 is the error estimate.
+struct Rodas4 {
+    static constexpr double gamma = 0.25;
+    static constexpr double a21 = 1.544, a31 = 0.9466785280815826, a32 = 0.2557011698983284;
+    static constexpr double a41 = 3.314825187068521, a42 = 2.896124015972201, a43 = 0.9986419139977817;
+    static constexpr double a51 = 1.221224509226641, a52 = 6.019134481288629, a53 = 12.53708332932087, a54 = -0.687886036105895;
+    static constexpr double c21 = -5.6688, c31 = -2.430093356833875, c32 = -0.2063599157091915;
+    static constexpr double c41 = -0.1073529058151375, c42 = -9.594562251023355, c43 = -20.47028614809616;
+    static constexpr double c51 = 7.496443313967647, c52 = -10.24680431464352, c53 = -33.99990352819905, c54 = 11.7089089320616;
+    static constexpr double c61 = 8.083246795921522, c62 = -7.981132988064893, c63 = -31.52159432874371, c64 = 16.31930543123136,
+                            c65 = -6.058818238834054;
+};
+
+// One step of size h from y: ynew (order 4), yemb (order 3; may alias nothing) and err2, the mean over species of
+// (k6 / (atol + rtol max(|y|, |ynew|)))^2.  False if the iteration matrix is singular.
+template <class Net>
+DZO_HD bool rodas4_step(const double* k, const double* y, double h, double rtol, double atol, double* ynew, double* yemb, double& err2)
+{
+    constexpr int S = Net::S;
+    typedef Rodas4 M;
+    double w[S * S];
+    int piv[S];
+    Net::jac(k, y, w);
+    const double fac = 1.0 / (h * M::gamma), ih = 1.0 / h;
+#pragma unroll
+    for (int i = 0; i < S * S; ++i) w[i] = -w[i];
+#pragma unroll
+    for (int s = 0; s < S; ++s) w[s * S + s] = w[s * S + s] + fac;
+    const bool ok = lu_factor<S>(w, piv);
+    double k1[S], k2[S], k3[S], k4[S], k5[S], k6[S], u[S];
+    Net::rhs(k, y, k1);
+    lu_solve<S>(w, piv, k1);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = y[s] + M::a21 * k1[s];
+    Net::rhs(k, u, k2);
+#pragma unroll
+    for (int s = 0; s < S; ++s) k2[s] = k2[s] + (M::c21 * k1[s]) * ih;
+    lu_solve<S>(w, piv, k2);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = y[s] + M::a31 * k1[s] + M::a32 * k2[s];
+    Net::rhs(k, u, k3);
+#pragma unroll
+    for (int s = 0; s < S; ++s) k3[s] = k3[s] + (M::c31 * k1[s] + M::c32 * k2[s]) * ih;
+    lu_solve<S>(w, piv, k3);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = y[s] + M::a41 * k1[s] + M::a42 * k2[s] + M::a43 * k3[s];
+    Net::rhs(k, u, k4);
+#pragma unroll
+    for (int s = 0; s < S; ++s) k4[s] = k4[s] + (M::c41 * k1[s] + M::c42 * k2[s] + M::c43 * k3[s]) * ih;
+    lu_solve<S>(w, piv, k4);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = y[s] + M::a51 * k1[s] + M::a52 * k2[s] + M::a53 * k3[s] + M::a54 * k4[s];
+    Net::rhs(k, u, k5);
+#pragma unroll
+    for (int s = 0; s < S; ++s) k5[s] = k5[s] + (M::c51 * k1[s] + M::c52 * k2[s] + M::c53 * k3[s] + M::c54 * k4[s]) * ih;
+    lu_solve<S>(w, piv, k5);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = u[s] + k5[s];
+    Net::rhs(k, u, k6);
+#pragma unroll
+    for (int s = 0; s < S; ++s) k6[s] = k6[s] + (M::c61 * k1[s] + M::c62 * k2[s] + M::c63 * k3[s] + M::c64 * k4[s] + M::c65 * k5[s]) * ih;
+    lu_solve<S>(w, piv, k6);
+    double e2 = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        yemb[s] = u[s];
+        ynew[s] = u[s] + k6[s];
+        const double sk = atol + rtol * dmax(dabs(y[s]), dabs(ynew[s]));
+        const double q = k6[s] / sk;
+        e2 = e2 + q * q;
+    }
+    err2 = e2 * (1.0 / S);
+    return ok;
+}
+
+template <int S>
+DZO_HD double wnorm2(const double* v, const double* y, double rtol, double atol)      // mean of (v / (atol + rtol |y|))^2
+{
+    double e2 = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const double q = v[s] / (atol + rtol * dabs(y[s]));
+        e2 = e2 + q * q;
+    }
+    return e2 * (1.0 / S);
+}
+
+// Hairer, Norsett & Wanner I, II.4 starting step, with the norms' roots folded into dexp / dlog; at most span.
+template <class Net>
+DZO_HD double start_step(const double* k, const double* y, double rtol, double atol, double span)
+{
+    constexpr int S = Net::S;
+    double f0[S], y1[S], f1[S];
+    Net::rhs(k, y, f0);
+    const double d0 = wnorm2<S>(y, y, rtol, atol), d1 = wnorm2<S>(f0, y, rtol, atol);
+    const double h0 = (d0 < 1e-10 || d1 < 1e-10) ? 1e-6 : dmin(0.01 * dexp(0.5 * (dlog(d0) - dlog(d1))), span);
+#pragma unroll
+    for (int s = 0; s < S; ++s) y1[s] = y[s] + h0 * f0[s];
+    Net::rhs(k, y1, f1);
+#pragma unroll
+    for (int s = 0; s < S; ++s) f1[s] = f1[s] - f0[s];
+    const double m = dmax(d1, wnorm2<S>(f1, y, rtol, atol) / (h0 * h0));       // max(d1, d2)^2
+    const double h1 = m <= 1e-30 ? dmax(1e-6, h0 * 1e-3) : dexp((dlog(0.01) - 0.5 * dlog(m)) * 0.2);
+    return dmin(dmin(100.0 * h0, h1), span);
+}
+
+// The log-likelihood of one point (and, with sim != nullptr, the observables at every output time, [T][O]).  -inf when a rate constant
+// or the state is not finite, the iteration matrix is singular, a step underflows or an output interval needs more than max_steps steps.
+template <class Net>
+DZO_HD double integrate(const double* x, const double* blk, double* sim, int* nsteps_out)
+{
+    constexpr int S = Net::S, O = Net::O;
+    const double rtol = blk[1], atol = blk[2], t0 = blk[4];
+    const int max_steps = (int)blk[3], T = (int)blk[5];
+    const double* tt = blk + 6 + S;
+    const double* dat = tt + T;
+    const double* sd = dat + (long long)T * O;
+    const double ninf = -__builtin_huge_val();
+    double k[Net::R > 0 ? Net::R : 1];
+    double y[S], yn[S], ye[S], o[O];
+    if (!Net::rates(x, k)) return ninf;
+#pragma unroll
+    for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+    double t = t0, acc = 0.0;
+    double h = start_step<Net>(k, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300));
+    bool ok = finite(h) && h > 0.0, rejected = false;
+    int nsteps = 0;
+    for (int j = 0; ok && j < T; ++j) {
+        const double tout = tt[j];
+        for (int n = 0; t < tout; ++n) {
+            const bool clip = t + h >= tout;
+            const double hs = clip ? tout - t : h;
+            if (n >= max_steps || t + hs == t) { ok = false; break; }
+            double err2;
+            const bool nonsing = rodas4_step<Net>(k, y, hs, rtol, atol, yn, ye, err2);
+            bool fin = nonsing && finite(err2);
+#pragma unroll
+            for (int s = 0; s < S; ++s) fin = fin && finite(yn[s]);
+            if (!fin) { ok = false; break; }
+            ++nsteps;
+            // err = sqrt(err2); h_new = h * clamp(0.9 err^(-1/4), 0.2, 6), no growth right after a rejection
+            double fac = err2 > 0.0 ? 0.9 * dexp(-0.125 * dlog(err2)) : 6.0;
+            fac = dmin(6.0, dmax(0.2, fac));
+            // amounts are non-negative: a step that takes one below -(atol + rtol |y|) is rejected like a failed error test (CVODE's
+            // inequality constraints).  Left in, such an undershoot of a species with a second-order loss grows without bound.
+            bool neg = false;
+#pragma unroll
+            for (int s = 0; s < S; ++s) neg = neg || yn[s] < -(atol + rtol * dabs(y[s]));
+            if (neg) fac = dmin(fac, 0.25);
+            if (err2 <= 1.0 && !neg) {
+                if (rejected) fac = dmin(fac, 1.0);
+#pragma unroll
+                for (int s = 0; s < S; ++s) y[s] = yn[s];
+                t = clip ? tout : t + hs;
+                h = clip ? dmax(h, hs * fac) : hs * fac;       // (a step clipped to the output time leaves the controller's size alone)
+                rejected = false;
+            } else {
+                h = hs * fac;
+                rejected = true;
+            }
+        }
+        if (!ok) break;
+        Net::obs(y, o);
+#pragma unroll
+        for (int q = 0; q < O; ++q) {
+            const double r = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
+            acc = acc - 0.5 * r * r;
+            if (sim) sim[(long long)j * O + q] = o[q];
+        }
+    }
+    if (nsteps_out) *nsteps_out = nsteps;
+    return ok ? blk[0] + acc : ninf;
+}
+
+// Fixed steps (the order test only): nsteps steps of (t1 - t0) / nsteps from y0, propagating the order-4 solution (which = 0) or the
+// embedded order-3 one (which = 1).  The final state in y; false if a step failed.
+template <class Net>
+DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)
+{
+    constexpr int S = Net::S;
+    double k[Net::R > 0 ? Net::R : 1], yn[S], ye[S];
+    if (!Net::rates(x, k)) return false;
+#pragma unroll
+    for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+    const double h = (t1 - blk[4]) / nsteps;
+    bool ok = true;
+    for (int n = 0; n < nsteps; ++n) {
+        double err2;
+        ok = rodas4_step<Net>(k, y, h, blk[1], blk[2], yn, ye, err2) && ok;
+#pragma unroll
+        for (int s = 0; s < S; ++s) y[s] = which ? ye[s] : yn[s];
+    }
+    return ok;
+}
+
+}  // namespace dzode
+
+// The entry points around a generated network struct NET: the batch kernel the engine's multi-kernel path launches (one thread per
+// point, 256 threads per block: dz_set_likelihood_module with lanes_per_point 1) and the host build's C functions.
+#if defined(__HIP__)
+#define DZODE_ENTRIES(NET)                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_batch(const double* X, long long n, int d, int ld, double* like,           \
+                                                                  const void* data)                                                    \
+    {                                                                                                                                    \
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
+        if (i >= n) return;                                                                                                              \
+        like[i] = dzode::integrate<NET>(X + i * ld, (const double*)data, nullptr, nullptr);                                             \
+    }
+#else
+#define DZODE_ENTRIES(NET)                                                                                                              \
+    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate<NET>(X + i * ld, blk, nullptr, nsteps ? nsteps + i : nullptr);     \
+    }                                                                                                                                    \
+    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* like)                 \
+    {                                                                                                                                    \
+        const long long per = (long long)(int)blk[5] * NET::O;                                                                           \
+        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate<NET>(X + i * ld, blk, sim + i * per, nullptr);                     \
+    }                                                                                                                                    \
+    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
+    {                                                                                                                                    \
+        return dzode::integrate_fixed<NET>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
+    }                                                                                                                                    \
+    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
+    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+#endif

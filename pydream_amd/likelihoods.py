@@ -59,55 +59,115 @@ class GaussianMixtureLogLike:
 KERNEL_SIGNATURE = 'extern "C" __global__ void NAME(const double* X, long long n, int d, int ld, double* like, const void* data)'
 
 
-def compile_device_kernel(source, out_path=None, extra_flags=(), arch="gfx950"):
-    """HIP source text -> a code object (.hsaco) for DeviceKernelLogLike: `hipcc --offload-arch=<arch> --genco` (arch: the engine is built
-    for gfx950, the MI355X; the argument is there so that an error names what was asked for).
-    -ffp-contract=off is on by default so that a density written with + and * rounds like the same expression in numpy (a host
-    likelihood and its device twin then make the same accept / reject decisions bit for bit); pass extra_flags=("-ffp-contract=fast",)
-    to let the compiler fuse.  Without out_path the code object is CACHED under a key of (source, flags, arch) in
-    $DREAMZS_KERNEL_CACHE (default ~/.cache/dreamzs_kernels, else the temporary directory): the same source is compiled once, by
-    whichever process or unpickled copy asks first (advisor, round 5: a fresh temporary directory and a fresh hipcc run per call).
-    Returns the path."""
+_COMPILER_VERSION = {}
+_FALLBACK_DIR = []
+
+
+def _hipcc():
+    import os
+    return next((c for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), "hipcc")
+
+
+def _compiler_version(cc):
+    """`cc --version` (memoised per process), part of the cache key: an object is only as current as the compiler that made it."""
+    import subprocess
+    if cc not in _COMPILER_VERSION:
+        try:
+            _COMPILER_VERSION[cc] = subprocess.run([cc, "--version"], capture_output=True, text=True).stdout
+        except OSError:
+            _COMPILER_VERSION[cc] = ""
+    return _COMPILER_VERSION[cc]
+
+
+def _private_dir(path):
+    """path is a directory (not a link) owned by this user and writable by nobody else."""
+    import os
+    import stat
+    try:
+        st = os.lstat(path)
+    except OSError:
+        return False
+    return stat.S_ISDIR(st.st_mode) and st.st_uid == os.getuid() and not (st.st_mode & (stat.S_IWGRP | stat.S_IWOTH))
+
+
+def kernel_cache_dir():
+    """Where compiled likelihood objects are kept: $DREAMZS_KERNEL_CACHE (default ~/.cache/dreamzs_kernels) if it can be written, else
+    <tmpdir>/dreamzs_kernels_<uid>.  The last one has a predictable name in a shared directory, so it is created with mode 0700 and
+    used only while it is a directory owned by this user and not group- or world-writable; otherwise a fresh private directory
+    (mkdtemp) serves this process.  Objects found in the cache are loaded and run, so nobody else may be able to write there."""
+    import os
+    import tempfile
+    cdir = os.environ.get("DREAMZS_KERNEL_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "dreamzs_kernels")
+    try:
+        os.makedirs(cdir, exist_ok=True)
+        if not os.access(cdir, os.W_OK):
+            raise OSError("not writable")
+        return cdir
+    except OSError:
+        pass
+    cdir = os.path.join(tempfile.gettempdir(), "dreamzs_kernels_%d" % os.getuid())
+    try:
+        os.mkdir(cdir, 0o700)
+    except OSError:
+        pass
+    if _private_dir(cdir):
+        return cdir
+    if not _FALLBACK_DIR or not _private_dir(_FALLBACK_DIR[0]):
+        _FALLBACK_DIR[:] = [tempfile.mkdtemp(prefix="dreamzs_kernels_")]
+    return _FALLBACK_DIR[0]
+
+
+def _build_cached(text, suffix, src_ext, cmd_for, what, cached_key_parts, out_path=None):
+    # what: (the compiler's name, what it was building) for the error messages
+    """Compile `text` with the command cmd_for(src, out) into out_path or, without one, into the kernel cache under a key of
+    (cached_key_parts, text).  Built beside the target under a name unique to the process and thread, then renamed into place:
+    concurrent builders never see half a file."""
     import hashlib
     import os
     import subprocess
-    import tempfile
-    text = source if "hip_runtime.h" in source else "#include <hip/hip_runtime.h>\n" + source
-    flags = ["--offload-arch=%s" % arch, "--genco", "--no-gpu-bundle-output", "-O3", "-std=c++17", "-ffp-contract=off"] + list(extra_flags)
+    import threading
     cached = out_path is None
     if cached:
-        key = hashlib.sha256(("\0".join(flags) + "\0" + text).encode()).hexdigest()[:32]
-        cdir = os.environ.get("DREAMZS_KERNEL_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "dreamzs_kernels")
-        try:
-            os.makedirs(cdir, exist_ok=True)
-            if not os.access(cdir, os.W_OK):
-                raise OSError("not writable")
-        except OSError:
-            cdir = os.path.join(tempfile.gettempdir(), "dreamzs_kernels_%d" % os.getuid())
-            os.makedirs(cdir, exist_ok=True)
-        out_path = os.path.join(cdir, key + ".hsaco")
+        key = hashlib.sha256(("\0".join(cached_key_parts) + "\0" + text).encode()).hexdigest()[:32]
+        out_path = os.path.join(kernel_cache_dir(), key + suffix)
         if os.path.exists(out_path) and os.path.getsize(out_path) > 0:
             return out_path
-    tmp = "%s.%d.tmp" % (out_path, os.getpid())          # (built beside the target, renamed into place: concurrent builders never see half a file)
-    src = tmp + ".hip"
+    tmp = "%s.%d.%d.tmp" % (out_path, os.getpid(), threading.get_ident())
+    src = tmp + src_ext
     with open(src, "w") as f:
         f.write(text)
-    hipcc = next((c for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), "hipcc")
+    cmd = cmd_for(src, tmp)
     try:
-        res = subprocess.run([hipcc] + flags + ["-o", tmp, src], capture_output=True, text=True)
+        res = subprocess.run(cmd, capture_output=True, text=True)
     except OSError as ex:          # (no compiler on this machine: say so -- a code object built elsewhere can be given by path)
         os.remove(src)
-        raise Exception("hipcc failed for the device likelihood: cannot run %r (%s); set HIPCC, or build the code object where ROCm is installed and pass its path" % (hipcc, ex))
+        raise Exception("%s failed%s: cannot run %r (%s); set HIPCC, or build the code object where ROCm is installed and pass its path" % (what + (cmd[0], ex)))
     try:
-        os.remove(src) if cached else os.replace(src, out_path + ".hip")
+        os.remove(src) if cached else os.replace(src, out_path + src_ext)
     except OSError:
         pass
     if res.returncode != 0:
         if os.path.exists(tmp):
             os.remove(tmp)
-        raise Exception("hipcc failed for the device likelihood (--offload-arch=%s):\n%s" % (arch, res.stderr[-4000:]))
+        raise Exception("%s failed%s:\n%s" % (what + (res.stderr[-4000:],)))
     os.replace(tmp, out_path)
     return out_path
+
+
+def compile_device_kernel(source, out_path=None, extra_flags=(), arch="gfx950"):
+    """HIP source text -> a code object (.hsaco) for DeviceKernelLogLike: `hipcc --offload-arch=<arch> --genco` (arch: the engine is built
+    for gfx950, the MI355X; the argument is there so that an error names what was asked for).
+    -ffp-contract=off is on by default so that a density written with + and * rounds like the same expression in numpy (a host
+    likelihood and its device twin then make the same accept / reject decisions bit for bit); pass extra_flags=("-ffp-contract=fast",)
+    to let the compiler fuse.  Without out_path the code object is CACHED under a key of (source, flags, arch, `hipcc --version`) in
+    kernel_cache_dir(): the same source is compiled once, by whichever process or unpickled copy asks first (advisor, round 5: a fresh
+    temporary directory and a fresh hipcc run per call).  Returns the path."""
+    text = source if "hip_runtime.h" in source else "#include <hip/hip_runtime.h>\n" + source
+    flags = ["--offload-arch=%s" % arch, "--genco", "--no-gpu-bundle-output", "-O3", "-std=c++17", "-ffp-contract=off"] + list(extra_flags)
+    hipcc = _hipcc()
+    key = flags + ([_compiler_version(hipcc)] if out_path is None else [])
+    return _build_cached(text, ".hsaco", ".hip", lambda src, out: [hipcc] + flags + ["-o", out, src],
+                         ("hipcc", " for the device likelihood (--offload-arch=%s)" % arch), key, out_path)
 
 
 FUNCTION_SIGNATURE = '__device__ double NAME(const double* x, int d, const void* data, int lane)'
@@ -282,4 +342,259 @@ class DeviceKernelLogLike:
 
     def __getstate__(self):                      # (the evaluation engine is a device handle: not part of the object's value)
         st = dict(self.__dict__); st["_eval_engine"] = None
+        return st
+
+
+# ---------------------------------------------------------------------------------------------------- mass-action ODE models
+ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
+_LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
+
+
+def _hexlit(v):
+    """A C++17 hexadecimal floating literal: the double exactly."""
+    v = float(v)
+    return "(%s)" % v.hex() if np.isfinite(v) else ("(__builtin_huge_val())" if v > 0 else "(-__builtin_huge_val())")
+
+
+def _ode_source(S, reactions, observables, log10):
+    """The generated network struct (see csrc/dz_ode.h): rate constants, right-hand side, analytic Jacobian and observables as
+    straight-line code with constant indices; powers as repeated products."""
+    R, O = len(reactions), len(observables)
+    N = np.zeros((S, R), dtype=np.int64)
+    for r, (reac, prod, _) in enumerate(reactions):
+        for s, c in reac.items():
+            N[s, r] -= c
+        for s, c in prod.items():
+            N[s, r] += c
+
+    def product(factors):
+        return " * ".join(factors) if factors else "1.0"
+
+    def rate_factors(reac, skip=None):
+        out = []
+        for s, c in sorted(reac.items()):
+            out += ["y[%d]" % s] * (c - (1 if s == skip else 0))
+        return out
+
+    def combine(terms):                     # [(integer coefficient, expression)] -> a sum in this order
+        out = ""
+        for c, e in terms:
+            t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
+            out += ("-" if c < 0 else "") + t if not out else (" - " if c < 0 else " + ") + t
+        return out or "0.0"
+
+    L = ["struct Net {",
+         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
+         "    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    for r, (_, _, rate) in enumerate(reactions):
+        if isinstance(rate, (int, np.integer)):
+            L.append("        k[%d] = %s;" % (r, ("dzode::dexp(x[%d] * 2.302585092994046)" % rate) if log10 else "x[%d]" % rate))
+        else:
+            L.append("        k[%d] = %s;" % (r, _hexlit(rate)))
+    used = sorted({rate for _, _, rate in reactions if isinstance(rate, (int, np.integer))})      # (10**-inf is a finite 0: test x itself)
+    L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)]))
+    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
+    for r, (reac, _, _) in enumerate(reactions):
+        L.append("        const double v%d = %s;" % (r, product(["k[%d]" % r] + rate_factors(reac))))
+    for s in range(S):
+        L.append("        f[%d] = %s;" % (s, combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
+    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
+    for r, (reac, _, _) in enumerate(reactions):        # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
+        for q, c in sorted(reac.items()):
+            L.append("        const double d%d_%d = %s;" % (r, q, product(["k[%d]" % r] + (["%d.0" % c] if c > 1 else []) + rate_factors(reac, skip=q))))
+    for s in range(S):
+        for q in range(S):
+            terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
+            L.append("        J[%d] = %s;" % (s * S + q, combine(terms)))
+    L += ["    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
+    for o, row in enumerate(observables):
+        terms = ["y[%d]" % s if row[s] == 1.0 else "%s * y[%d]" % (_hexlit(row[s]), s) for s in range(S) if row[s] != 0.0]
+        L.append("        o[%d] = %s;" % (o, " + ".join(terms) if terms else "0.0"))
+    L += ["    }", "};", "DZODE_ENTRIES(Net)", ""]
+    return '#include "dz_ode.h"\n' + "\n".join(L)
+
+
+class MassActionODELogLike:
+    """A mass-action reaction network with Gaussian data as the likelihood, integrated ON THE DEVICE by a stiff Rosenbrock solver (Rodas4,
+    csrc/dz_ode.h), one lane per point -- robertson_nopysb/example_sample_robertson_nopysb_with_dream.py:43-95 written as
+
+        like = MassActionODELogLike(
+            n_species=3,
+            reactions=[({0: 1}, {1: 1}, 0),               # A -> B          k = 10**theta[0]
+                       ({1: 2}, {1: 1, 2: 1}, 1),         # 2B -> B + C     k = 10**theta[1]
+                       ({1: 1, 2: 1}, {0: 1, 2: 1}, 2)],  # B + C -> A + C  k = 10**theta[2]
+            y0=[1.0, 0.0, 0.0], t=np.linspace(0, 40),     # integration starts at t0 = 0 (an output at t0 is y0)
+            observables=[[0, 0, 1]],                      # O x S linear combinations of species
+            data=exp_data_ctot[None, :], sd=exp_data_sd_ctot[None, :], rate_scale="log10")
+
+    A reaction is (reactants {species: coefficient}, products {species: coefficient}, rate), rate a parameter index (the rate constant is
+    10**x[index] for rate_scale "log10", x[index] for "linear") or a float (the rate constant itself).  Its rate is k prod y_s^nu_s (no
+    combinatorial factor), dy/dt = N v with N = products - reactants.  The log-likelihood is sum norm(data, sd).logpdf(sim) over the
+    finite data entries (NaN data: not observed), sim the observables at the output times t (data and sd are O x T).  rtol, atol: as
+    odeint's defaults; max_steps: per output interval, as odeint's mxstep.  A failed integration (more than max_steps steps in an interval,
+    a step that underflows, a state or rate that is not finite) is -inf.  Amounts are non-negative: y0 >= 0, and a step that takes a species
+    below -(atol + rtol |y|) is rejected and retried smaller.
+
+    The device build runs on the engine's multi-kernel path (dz_set_likelihood_module, one thread per point) with the redraw rounds on.
+    A call on the host -- __call__, simulate, the host path of run_dream -- goes through the same generated source compiled for the host
+    (ROCm's clang++, else g++), which gives the same bits.  path: a code object built beforehand (`.code_object()`)."""
+
+    def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
+                 max_steps=500, ndim=None, path=None):
+        S = int(n_species)
+        if not 1 <= S <= ODE_LIMITS["species"]:
+            raise ValueError("MassActionODELogLike: n_species must be 1..%d (got %d)" % (ODE_LIMITS["species"], S))
+        if not 1 <= len(reactions) <= ODE_LIMITS["reactions"]:
+            raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (ODE_LIMITS["reactions"], len(reactions)))
+        if rate_scale not in ("log10", "linear"):
+            raise ValueError('MassActionODELogLike: rate_scale must be "log10" or "linear"')
+        rx = []
+        for r, reaction in enumerate(reactions):
+            if len(reaction) != 3:
+                raise ValueError("MassActionODELogLike: reaction %d must be (reactants, products, rate)" % r)
+            reac, prod, rate = reaction
+            for side in (reac, prod):
+                for s, c in dict(side).items():
+                    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < S:
+                        raise ValueError("MassActionODELogLike: reaction %d names species %r (0..%d)" % (r, s, S - 1))
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
+                        raise ValueError("MassActionODELogLike: reaction %d: stoichiometric coefficients must be non-negative integers (got %r)" % (r, c))
+            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating)):
+                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int) or a fixed rate constant (float)" % r)
+            if isinstance(rate, (int, np.integer)):
+                if rate < 0:
+                    raise ValueError("MassActionODELogLike: reaction %d: parameter index %d is negative" % (r, rate))
+                rate = int(rate)
+            elif not np.isfinite(rate):
+                raise ValueError("MassActionODELogLike: reaction %d: the fixed rate constant must be finite" % r)
+            else:
+                rate = float(rate)
+            rx.append(({int(s): int(c) for s, c in dict(reac).items() if c}, {int(s): int(c) for s, c in dict(prod).items() if c}, rate))
+        idx = [r[2] for r in rx if isinstance(r[2], int)]
+        self.d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
+        if idx and max(idx) >= self.d:
+            raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), self.d))
+        y0 = np.asarray(y0, dtype=float).reshape(-1)
+        if y0.shape != (S,) or not np.all(np.isfinite(y0)) or np.any(y0 < 0):
+            raise ValueError("MassActionODELogLike: y0 must hold %d finite, non-negative amounts" % S)
+        t = np.asarray(t, dtype=float).reshape(-1)
+        if not 1 <= len(t) <= ODE_LIMITS["times"]:
+            raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (ODE_LIMITS["times"], len(t)))
+        if not np.isfinite(t0) or not np.all(np.isfinite(t)) or np.any(np.diff(t) < 0) or t[0] < t0:
+            raise ValueError("MassActionODELogLike: output times must be finite, sorted and >= t0 = %r" % t0)
+        obs = np.atleast_2d(np.asarray(observables, dtype=float))
+        if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= ODE_LIMITS["observables"] or not np.all(np.isfinite(obs)):
+            raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, ODE_LIMITS["observables"]))
+        O, T = len(obs), len(t)
+        data = np.asarray(data, dtype=float)
+        sd = np.broadcast_to(np.asarray(sd, dtype=float), data.shape) if data.shape == (O, T) else np.asarray(sd, dtype=float)
+        if data.shape != (O, T) or sd.shape != (O, T):
+            raise ValueError("MassActionODELogLike: data and sd must be O x T = %d x %d" % (O, T))
+        seen = np.isfinite(data)
+        if np.any(np.isinf(data)) or not np.all(np.isfinite(sd[seen]) & (sd[seen] > 0)):
+            raise ValueError("MassActionODELogLike: data must be finite or NaN (not observed), and sd finite and > 0 where data is observed")
+        if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
+            raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
+        self.n_species, self.reactions, self.observables, self.log10 = S, rx, obs, rate_scale == "log10"
+        self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
+        self.data, self.sd = data, np.array(sd)
+        self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
+        self.path = path
+        self._host = None
+
+    # ---- the data block (csrc/dz_ode.h) and the generated source
+    def data_block(self):
+        seen = np.isfinite(self.data)
+        C = float(np.sum(-np.log(self.sd[seen]) - _LOG_2PI_HALF))
+        dat = np.where(seen, self.data, 0.0).T.reshape(-1)          # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
+        sd = np.where(seen, self.sd, np.inf).T.reshape(-1)
+        return np.concatenate([[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], self.y0, self.t, dat, sd])
+
+    def source(self):
+        return _ode_source(self.n_species, self.reactions, self.observables, self.log10)
+
+    @staticmethod
+    def _header_hash():
+        import hashlib
+        import os
+        with open(os.path.join(csrc_dir(), "dz_ode.h"), "rb") as fh:
+            return hashlib.sha256(fh.read()).hexdigest()
+
+    def code_object(self):
+        """The gfx950 code object (kernel dz_ode_batch), compiled with hipcc on first use and cached; the key includes csrc/dz_ode.h."""
+        if self.path is None:
+            text = self.source() + "\n// dz_ode.h " + self._header_hash() + "\n"
+            self.path = compile_device_kernel(text, extra_flags=("-I" + csrc_dir(),))
+        return self.path
+
+    def _dz_apply(self, engine):
+        engine.set_likelihood_module(self.code_object(), "dz_ode_batch", 1, self.data_block(), False)
+
+    # ---- the host build
+    def host_library(self):
+        """The same generated source compiled for the host (x86-64 SSE2 doubles, -O2 -ffp-contract=off), loaded with ctypes; cached."""
+        if self._host is None:
+            import ctypes as C
+            import os
+            cc = "/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else "g++"
+            flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-I" + csrc_dir()]
+            text = self.source() + "\n// dz_ode.h " + self._header_hash() + "\n"
+            so = _build_cached(text, ".so", ".cpp", lambda src, out: [cc] + flags + ["-o", out, src, "-lm"],
+                               (os.path.basename(cc), " for the host build of the ODE likelihood"), [cc, _compiler_version(cc)] + flags)
+            L = C.CDLL(so)
+            P, I64, D, I = C.POINTER(C.c_double), C.c_longlong, C.c_double, C.c_int
+            L.dzode_loglike.argtypes = [P, I64, I, P, P, C.POINTER(C.c_int)]
+            L.dzode_simulate.argtypes = [P, I64, I, P, P, P]
+            L.dzode_fixed.argtypes = [P, P, D, I, I, P]
+            L.dzode_fixed.restype = I
+            L.dzode_exp.argtypes = L.dzode_log.argtypes = [D]
+            L.dzode_exp.restype = L.dzode_log.restype = D
+            self._host = L
+        return self._host
+
+    def _rows(self, X):
+        X = np.ascontiguousarray(np.asarray(X, dtype=float))
+        X = X.reshape(-1, X.shape[-1] if X.ndim else 1)
+        if X.shape[1] < self.d:
+            raise ValueError("MassActionODELogLike: points have %d coordinates, the model reads %d" % (X.shape[1], self.d))
+        return X
+
+    def batch(self, X, return_steps=False):
+        """Host-build log-likelihoods of the rows of X (and the accepted steps of each integration)."""
+        import ctypes as C
+        X = self._rows(X)
+        blk = self.data_block()
+        out, st = np.zeros(len(X)), np.zeros(len(X), dtype=np.int32)
+        P = C.POINTER(C.c_double)
+        self.host_library().dzode_loglike(X.ctypes.data_as(P), len(X), X.shape[1], blk.ctypes.data_as(P), out.ctypes.data_as(P),
+                                          st.ctypes.data_as(C.POINTER(C.c_int)))
+        return (out, st) if return_steps else out
+
+    def __call__(self, x):
+        return float(self.batch(np.asarray(x, dtype=float).reshape(1, -1))[0])
+
+    def simulate(self, X):
+        """The observables at the output times, [n, T, O] (NaN where the integration failed), from the host build."""
+        import ctypes as C
+        X = self._rows(X)
+        blk = self.data_block()
+        T, O = len(self.t), len(self.observables)
+        sim, like = np.full((len(X), T, O), np.nan), np.zeros(len(X))
+        P = C.POINTER(C.c_double)
+        self.host_library().dzode_simulate(X.ctypes.data_as(P), len(X), X.shape[1], blk.ctypes.data_as(P), sim.ctypes.data_as(P), like.ctypes.data_as(P))
+        sim[like == -np.inf] = np.nan
+        return sim
+
+    def fixed_steps(self, x, t1, nsteps, embedded=False):
+        """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test)."""
+        import ctypes as C
+        x = np.ascontiguousarray(np.asarray(x, dtype=float).reshape(-1))
+        blk = self.data_block()
+        y = np.zeros(self.n_species)
+        P = C.POINTER(C.c_double)
+        ok = self.host_library().dzode_fixed(x.ctypes.data_as(P), blk.ctypes.data_as(P), float(t1), int(nsteps), int(bool(embedded)), y.ctypes.data_as(P))
+        return y if ok else np.full(self.n_species, np.nan)
+
+    def __getstate__(self):                      # (the host library is a handle of this process: loaded again on first use)
+        st = dict(self.__dict__); st["_host"] = None
         return st
