@@ -116,7 +116,10 @@ int dz_set_likelihood_host(dz_engine* e, dz_logp_cb cb, void* user);
  * treated as -inf); data: a copy on the device of the `data_bytes` bytes at `data` (model constants, observations; NULL if none).  The
  * engine launches it once per batch where its own k_logp_* kernels run, with 256 threads per block and
  *     lanes_per_point = 1:  thread blockIdx.x * 256 + threadIdx.x evaluates point i (grid = ceil(n / 256));
+ *     lanes_per_point = 16 or 32: the L lanes [i * L, (i + 1) * L) of the grid evaluate point i together, 256 / L points per block
+ *                           (grid = ceil(n * L / 256)); a group lies inside one wave, and the groups of the last block with i >= n run too;
  *     lanes_per_point = 64: wave (blockIdx.x * 4 + threadIdx.x / 64) evaluates point i with its 64 lanes (grid = ceil(n / 4)).
+ * No dynamic LDS is given to the launch (the kernel may declare static __shared__).
  * Priors given by dz_set_prior are added by the engine.  Generations with such a likelihood run the multi-kernel path -- unless the code
  * object also exports the persistent generation kernel instantiated around the same density (round 6):
  *     dz_user_generations_v<N>, dz_user_generations_full_v<N>      (N = DZ_USER_ABI of csrc/dz_kernels.h: the layout generation of the

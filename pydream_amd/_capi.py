@@ -270,7 +270,8 @@ class Engine:
 
     def set_likelihood_module(self, code_object_path, kernel_name, lanes_per_point=1, data=None, always_finite=False):
         """A user-built gfx950 code object's kernel as the likelihood (include/dreamzs.h dz_set_likelihood_module); data: bytes / a numpy
-        array copied to the device and handed to the kernel."""
+        array copied to the device and handed to the kernel.  lanes_per_point: 1 (a thread per point), 16 or 32 (a lane group per
+        point) or 64 (a wave per point); 256 threads per block."""
         blob = b"" if data is None else (data if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).tobytes())
         buf = C.create_string_buffer(bytes(blob), len(blob)) if blob else None
         self._chk(self.L.dz_set_likelihood_module(self.h, os.fsencode(code_object_path), kernel_name.encode(), int(lanes_per_point),

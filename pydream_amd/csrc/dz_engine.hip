@@ -424,7 +424,7 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
         size_t asz = sizeof(a);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
         HIPCK(hipMemsetAsync(prior, 0, sizeof(double) * (size_t)n, st));
-        const unsigned per_block = e->lk_lanes == 64 ? 4u : 256u;      // one thread or one wave per point, 256 threads per block
+        const unsigned per_block = 256u / (unsigned)e->lk_lanes;      // 1, 16, 32 or 64 lanes per point, 256 threads per block
         HIPCK(hipModuleLaunchKernel(e->lk_fn, ((unsigned)n + per_block - 1) / per_block, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
         NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, grid, block, 0, st, e->p, pts, n, prior, like));
     } else if (e->lk == LK_HOST) {
@@ -1707,7 +1707,8 @@ int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const c
                              const void* data, int64_t data_bytes)
 {
     if (!e || !code_object_path || !kernel_name) return fail("null argument");
-    if (lanes_per_point != 1 && lanes_per_point != 64) return fail("dz_set_likelihood_module: lanes_per_point must be 1 (a thread per point) or 64 (a wave per point)");
+    if (lanes_per_point != 1 && lanes_per_point != 16 && lanes_per_point != 32 && lanes_per_point != 64)
+        return fail("dz_set_likelihood_module: lanes_per_point must be 1 (a thread per point), 16 or 32 (a lane group per point) or 64 (a wave per point)");
     if (data_bytes < 0 || (data_bytes > 0 && !data)) return fail("dz_set_likelihood_module: bad data block");
     HIPCK(hipSetDevice(e->c.device));
     DZCK(sync_all(e));

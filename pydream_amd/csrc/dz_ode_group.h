@@ -1,0 +1,588 @@
+// dz_ode_group.h -- dz_ode.h's solver for networks of 9..32 species: a GROUP of L = 16 or 32 lanes integrates one point together
+// (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32)).  The method is dz_ode.h's, unchanged: Rodas4 with the same
+// coefficients, step controller, start step, negativity rule, max_steps per output interval, exact landing on the output times and -inf
+// on any failure; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
+//     row r of W = I / (h gamma) - J in registers (S doubles, constant column indices after unrolling),
+//     entry r of y, of the stage argument u and of k1..k6,
+//     one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled by S group broadcasts per stage);
+// lanes r >= S idle: they carry zeros, never pivot, and are masked out of every reduction.  The rate constants (up to 128) are computed
+// once per point, reaction j by lane j % L, and kept in static LDS (256 / L points x (R + 1) doubles per block).
+//
+// Linear algebra over the group (ds_bpermute through __shfl / __shfl_xor with width L; no LDS round trip, no MFMA: a pivoted f64 LU of
+// S <= 32 is a chain of S dependent column steps, latency- and not throughput-bound):
+//   LU, implicit partial pivoting: per column k a butterfly arg-max of |w[k]| over the lanes that have not pivoted yet (equal maxima:
+//     the lowest row; a NaN counts as +inf), the pivot's reciprocal and its row right of k broadcast, one multiplier and one rank-1 row
+//     update per remaining lane.  Rows do not move: piv[k] is the row that pivoted in column k, pos the column a row pivoted in.
+//   Solves, column-oriented: forward, k ascending: b[piv[k]] broadcast, rows with pos > k subtract their multiple; backward, k descending:
+//     x_k = b[piv[k]] / pivot broadcast, rows with pos < k subtract their multiple, lane k keeps x_k.
+//   Sums (error norm, start step norms): the xor butterfly, i.e. the pairwise tree ((v0 + v1) + (v2 + v3)) + ... over L entries, idle
+//     lanes adding 0.  neg / finite predicates: a ballot restricted to the group's lanes.
+// Control flow is uniform per group (every lane of a group computes h, t, err2, ... from the same broadcast values and so holds the same
+// bits); the groups of a wave may diverge from each other, so nothing inside a step loop is wider than a group.
+//
+// The host twin (HostGroup below) is a plain loop over rows that performs the same floating-point operations in the same order: the same
+// generated rhs_row / jac_entry, the same pivot rule, the same column-oriented solves, the same summation tree.  It does not give the
+// bits of dz_ode.h on a network both can run (lu_solve's row-oriented back substitution sums in the other direction).
+//
+// The network comes from generated code (likelihoods._ode_group_source): a struct with
+//     static constexpr int S, R, O;  static constexpr bool LOG10;
+//     static int rate_index(int j);       the parameter index of reaction j's rate constant, -1 for a fixed one
+//     static double rate_fixed(int j);    the fixed rate constant of reaction j
+//     static double rhs_row(int r, const double* k, const double* y);              f[r] = sum over reactions j, ascending, of N[r][j] v_j(y),
+//                                                                                  N[r][j] a select over constants: no branch on r
+//     static double jac_entry(int r, int q, const double* k, const double* y);     J[r][q], same order (0 where no reaction links them)
+//     static void obs(const double* y, double* o);
+// Data block: dz_ode.h's.
+#pragma once
+#include "dz_ode.h"
+
+// Inside a generated sum, every four terms: on the device the partial sum v, the row index r and an offset z (always 0) added to the
+// rate constants' index pass through an empty asm statement together, so the next terms' LDS reads and stoichiometric selects depend on the previous terms' sum and
+// cannot be issued ahead of it.  Values and order of operations are unchanged; what it bounds is the registers a sum of R terms holds
+// at once (without it the compiler starts all R reads and selects up front, and R = 128 does not fit the register file).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DZODE_SUM_FENCE(v, r, z) asm volatile("" : "+v"(v), "+v"(r), "+v"(z))
+#else
+#define DZODE_SUM_FENCE(v, r, z) ((void)0)
+#endif
+
+namespace dzode {
+
+// The stage arguments and the (1/h) sum c_ij k_j terms of dz_ode.h's rodas4_step, entry by entry, shared by both builds.
+// stage 5's argument is stage 4's plus k5 (u: the previous stage's argument).
+DZO_HD double stage_arg(int st, double y, double u, double k1, double k2, double k3, double k4, double k5)
+{
+    typedef Rodas4 M;
+    switch (st) {
+    case 0: return y;
+    case 1: return y + M::a21 * k1;
+    case 2: return y + M::a31 * k1 + M::a32 * k2;
+    case 3: return y + M::a41 * k1 + M::a42 * k2 + M::a43 * k3;
+    case 4: return y + M::a51 * k1 + M::a52 * k2 + M::a53 * k3 + M::a54 * k4;
+    default: return u + k5;
+    }
+}
+
+DZO_HD double stage_add(int st, double ih, double k1, double k2, double k3, double k4, double k5)
+{
+    typedef Rodas4 M;
+    switch (st) {
+    case 1: return (M::c21 * k1) * ih;
+    case 2: return (M::c31 * k1 + M::c32 * k2) * ih;
+    case 3: return (M::c41 * k1 + M::c42 * k2 + M::c43 * k3) * ih;
+    case 4: return (M::c51 * k1 + M::c52 * k2 + M::c53 * k3 + M::c54 * k4) * ih;
+    default: return (M::c61 * k1 + M::c62 * k2 + M::c63 * k3 + M::c64 * k4 + M::c65 * k5) * ih;
+    }
+}
+
+DZO_HD double pivot_key(double a)          // |a|, a NaN as +inf: the arg-max is then over a total order
+{
+    const double v = dabs(a);
+    return v == v ? v : __builtin_huge_val();
+}
+
+// the step controller of dz_ode.h's integrate: the factor from the error, before the negativity and rejection caps
+DZO_HD double step_factor(double err2)
+{
+    const double fac = err2 > 0.0 ? 0.9 * dexp(-0.125 * dlog(err2)) : 6.0;
+    return dmin(6.0, dmax(0.2, fac));
+}
+
+DZO_HD double start_h0(double d0, double d1, double span)
+{
+    return (d0 < 1e-10 || d1 < 1e-10) ? 1e-6 : dmin(0.01 * dexp(0.5 * (dlog(d0) - dlog(d1))), span);
+}
+
+DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h: the norm of f1 - f0, still to be divided by h0^2
+{
+    const double m = dmax(d1, d2h / (h0 * h0));
+    const double h1 = m <= 1e-30 ? dmax(1e-6, h0 * 1e-3) : dexp((dlog(0.01) - 0.5 * dlog(m)) * 0.2);
+    return dmin(dmin(100.0 * h0, h1), span);
+}
+
+template <class Net>
+DZO_HD double rate_constant(int j, const double* x, bool& good)
+{
+    const int pi = Net::rate_index(j);
+    if (pi < 0) {
+        const double kv = Net::rate_fixed(j);
+        good = finite(kv);
+        return kv;
+    }
+    const double xv = x[pi];
+    const double kv = Net::LOG10 ? dexp(xv * 2.302585092994046) : xv;
+    good = finite(xv) && finite(kv);          // (10**-inf is a finite 0: test x itself)
+    return kv;
+}
+
+#if defined(__HIP__)
+// ---------------------------------------------------------------- the device side: one lane's share
+// The lane's row index as the network's functions see it: the same value, but one the compiler cannot trace back to threadIdx.  The
+// stoichiometric selects of rhs_row / jac_entry depend on r alone; hoisted out of the step loop they would be hundreds of live registers.
+__device__ __forceinline__ int row_index(int r)
+{
+    asm volatile("" : "+v"(r));
+    return r;
+}
+
+template <int L>
+struct Lanes {
+    static_assert(L == 16 || L == 32, "a group is 16 or 32 lanes");
+    __device__ __forceinline__ static double from(double v, int src) { return __shfl(v, src, L); }        // lane src of this group
+    __device__ __forceinline__ static int from(int v, int src) { return __shfl(v, src, L); }
+    __device__ __forceinline__ static double sum(double v)
+    {
+#pragma unroll
+        for (int m = 1; m < L; m <<= 1) v = v + __shfl_xor(v, m, L);
+        return v;
+    }
+    __device__ __forceinline__ static bool any(bool p)
+    {
+        const unsigned long long mask = (L == 32 ? 0xffffffffull : 0xffffull) << ((threadIdx.x & 63) & ~(L - 1));
+        return (__ballot(p) & mask) != 0;
+    }
+    template <int S>
+    __device__ __forceinline__ static void gather(double own, double* all)
+    {
+#pragma unroll
+        for (int q = 0; q < S; ++q) all[q] = from(own, q);
+    }
+};
+
+template <class Net, int L>
+__device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
+{
+    bool good = true;
+    for (int j = r; j < Net::R; j += L) {
+        bool g;
+        ks[j] = rate_constant<Net>(j, x, g);
+        good = good && g;
+    }
+    return !Lanes<L>::any(!good);
+}
+
+// piv: the row that pivoted in column k, four columns to an int
+__device__ __forceinline__ int pivot_row(const int* piv, int k) { return (piv[k >> 2] >> (8 * (k & 3))) & 0xff; }
+
+template <int S, int L>
+__device__ __forceinline__ bool group_lu_factor(double* w, int* piv, int& pos, int r)
+{
+    bool ok = true, done = r >= S;
+    pos = -1;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        double key = done ? -1.0 : pivot_key(w[k]);
+        int p = r;
+#pragma unroll
+        for (int m = 1; m < L; m <<= 1) {
+            const double okey = __shfl_xor(key, m, L);
+            const int op = __shfl_xor(p, m, L);
+            const bool take = (okey > key) | ((okey == key) & (op < p));
+            key = take ? okey : key;
+            p = take ? op : p;
+        }
+        piv[k >> 2] = (k & 3) ? piv[k >> 2] | (p << (8 * (k & 3))) : p;
+        ok = ok && key != 0.0;
+        const bool me = p == r, upd = !done && !me;
+        const double inv = Lanes<L>::from(1.0 / w[k], p);
+        const double l = w[k] * inv;
+        w[k] = me ? inv : (upd ? l : w[k]);
+#pragma unroll
+        for (int c = k + 1; c < S; ++c) {
+            const double pc = Lanes<L>::from(w[c], p);
+            w[c] = upd ? w[c] - l * pc : w[c];
+        }
+        done = done || me;
+        pos = me ? k : pos;
+    }
+    return ok;
+}
+
+template <int S, int L>
+__device__ __forceinline__ double group_lu_solve(const double* w, const int* pivp, int pos, int r, double b)
+{
+    int piv[(S + 3) / 4];          // (opaque copies: the S broadcast addresses and 3 S lane masks the compiler would otherwise carry from
+#pragma unroll                     //  the factorisation through all six solves are rebuilt here from these few registers)
+    for (int i = 0; i < (S + 3) / 4; ++i) piv[i] = row_index(pivp[i]);
+    pos = row_index(pos);
+    r = row_index(r);
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const double bk = Lanes<L>::from(b, pivot_row(piv, k));
+        b = pos > k ? b - w[k] * bk : b;
+    }
+    double x = 0.0;
+#pragma unroll
+    for (int k = S - 1; k >= 0; --k) {
+        const double xk = Lanes<L>::from(b * w[k], pivot_row(piv, k));
+        b = (pos >= 0 && pos < k) ? b - w[k] * xk : b;
+        x = r == k ? xk : x;
+    }
+    return x;
+}
+
+// w[0..Q) = row r of I / (h gamma) - J, column by column.  A recursion over the column and not a loop: every column index must be a
+// constant (w lives in registers), and a loop around the whole generated switch is too long for the compiler to unroll on its own.
+// zk is an offset (always 0) into the rate constants: R of them are read from LDS where they are used, not kept in registers across steps.
+template <class Net, int Q>
+struct JacobianRow {
+    __device__ __forceinline__ static void fill(double* w, int& rj, int& zk, const double* ks, const double* yr, int r, double fac)
+    {
+        JacobianRow<Net, Q - 1>::fill(w, rj, zk, ks, yr, r, fac);
+        double m = -Net::jac_entry(rj, Q - 1, ks + zk, yr);
+        DZODE_SUM_FENCE(m, rj, zk);             // (column by column, for the same reason as inside a sum)
+        w[Q - 1] = Q - 1 == r ? m + fac : m;
+    }
+};
+template <class Net>
+struct JacobianRow<Net, 0> {
+    __device__ __forceinline__ static void fill(double*, int&, int&, const double*, const double*, int, double) {}
+};
+
+// One step of size h: this lane's entry of the order-4 solution and the group's err2.  False if the iteration matrix is singular.
+template <class Net, int L>
+__device__ __forceinline__ bool group_step(const double* ks, double y, double h, double rtol, double atol, int r, double& ynew, double& err2)
+{
+    constexpr int S = Net::S;
+    double yr[S], w[S];
+    int piv[(S + 3) / 4], pos;
+    const double fac = 1.0 / (h * Rodas4::gamma), ih = 1.0 / h;
+    Lanes<L>::template gather<S>(y, yr);
+    int rj = row_index(r), zk = row_index(0);
+    JacobianRow<Net, S>::fill(w, rj, zk, ks, yr, r, fac);
+    const bool ok = group_lu_factor<S, L>(w, piv, pos, r);
+    double k1 = 0.0, k2 = 0.0, k3 = 0.0, k4 = 0.0, k5 = 0.0, f = 0.0, arg = y;
+#pragma unroll 1
+    for (int st = 0; st < 6; ++st) {          // (one copy of the right-hand side and of the solve in the code object, not six)
+        arg = stage_arg(st, y, arg, k1, k2, k3, k4, k5);
+        Lanes<L>::template gather<S>(arg, yr);          // (also at stage 0: the copy the Jacobian used is not kept alive across the LU)
+        f = Net::rhs_row(row_index(r), ks + row_index(0), yr);
+        if (st > 0) f = f + stage_add(st, ih, k1, k2, k3, k4, k5);
+        f = group_lu_solve<S, L>(w, piv, pos, r, f);
+        k1 = st == 0 ? f : k1;
+        k2 = st == 1 ? f : k2;
+        k3 = st == 2 ? f : k3;
+        k4 = st == 3 ? f : k4;
+        k5 = st == 4 ? f : k5;
+    }
+    ynew = arg + f;                            // arg: y5 + k5, f: k6
+    const double sk = atol + rtol * dmax(dabs(y), dabs(ynew));
+    const double q = f / sk;
+    err2 = Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
+    return ok;
+}
+
+template <int S, int L>
+__device__ __forceinline__ double group_wnorm2(double v, double y, double rtol, double atol, int r)
+{
+    const double q = v / (atol + rtol * dabs(y));
+    return Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
+}
+
+template <class Net, int L>
+__device__ __forceinline__ double group_start_step(const double* ks, double y, double rtol, double atol, double span, int r)
+{
+    constexpr int S = Net::S;
+    double yr[S];
+    Lanes<L>::template gather<S>(y, yr);
+    const double f0 = Net::rhs_row(row_index(r), ks, yr);
+    const double d0 = group_wnorm2<S, L>(y, y, rtol, atol, r), d1 = group_wnorm2<S, L>(f0, y, rtol, atol, r);
+    const double h0 = start_h0(d0, d1, span);
+    Lanes<L>::template gather<S>(y + h0 * f0, yr);
+    const double f1 = Net::rhs_row(row_index(r), ks, yr) - f0;
+    return start_h(h0, d1, group_wnorm2<S, L>(f1, y, rtol, atol, r), span);
+}
+
+// The log-likelihood of the group's point, the same value in every lane.  live = false (a point past the batch's end, or a rate constant
+// that is not finite): no step is taken, -inf.
+template <class Net, int L>
+__device__ __forceinline__ double group_integrate(const double* ks, const double* blk, int r, bool live)
+{
+    constexpr int S = Net::S, O = Net::O;
+    const double rtol = blk[1], atol = blk[2], t0 = blk[4];
+    const int max_steps = (int)blk[3], T = (int)blk[5];
+    const double* tt = blk + 6 + S;
+    const double* dat = tt + T;
+    const double* sd = dat + (long long)T * O;
+    const bool act = r < S;
+    double y = act ? blk[6 + r] : 0.0;
+    double t = t0, acc = 0.0;
+    double h = live ? group_start_step<Net, L>(ks, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300), r) : 0.0;
+    bool ok = live && finite(h) && h > 0.0, rejected = false;
+    for (int j = 0; ok && j < T; ++j) {
+        const double tout = tt[j];
+        for (int n = 0; t < tout; ++n) {
+            const bool clip = t + h >= tout;
+            const double hs = clip ? tout - t : h;
+            if (n >= max_steps || t + hs == t) { ok = false; break; }
+            double yn, err2;
+            const bool nonsing = group_step<Net, L>(ks, y, hs, rtol, atol, r, yn, err2);
+            if (!nonsing || !finite(err2) || Lanes<L>::any(!finite(yn))) { ok = false; break; }
+            double fac = step_factor(err2);
+            const bool neg = Lanes<L>::any(yn < -(atol + rtol * dabs(y)));
+            if (neg) fac = dmin(fac, 0.25);
+            if (err2 <= 1.0 && !neg) {
+                if (rejected) fac = dmin(fac, 1.0);
+                y = yn;
+                t = clip ? tout : t + hs;
+                h = clip ? dmax(h, hs * fac) : hs * fac;
+                rejected = false;
+            } else {
+                h = hs * fac;
+                rejected = true;
+            }
+        }
+        if (!ok) break;
+        double yr[S], o[O];
+        Lanes<L>::template gather<S>(y, yr);
+        Net::obs(yr, o);
+#pragma unroll
+        for (int q = 0; q < O; ++q) {
+            const double res = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
+            acc = acc - 0.5 * res * res;
+        }
+    }
+    return ok ? blk[0] + acc : -__builtin_huge_val();
+}
+#endif
+
+#if !defined(__HIP__)
+// ---------------------------------------------------------------- the host twin: the same operations, row by row
+template <class Net, int L>
+struct HostGroup {
+    static constexpr int S = Net::S, O = Net::O, R = Net::R;
+    static_assert(S <= L, "a lane per species");
+
+    static double sum(double* a)               // a[L], overwritten: the butterfly's tree as lane 0 sees it
+    {
+        for (int m = 1; m < L; m <<= 1)
+            for (int i = 0; i < L; i += 2 * m) a[i] = a[i] + a[i + m];
+        return a[0];
+    }
+
+    static bool rates(const double* x, double* k)
+    {
+        bool good = true;
+        for (int j = 0; j < R; ++j) {
+            bool g;
+            k[j] = rate_constant<Net>(j, x, g);
+            good = good && g;
+        }
+        return good;
+    }
+
+    static bool lu_factor(double* w, int* piv, int* pos)
+    {
+        bool ok = true, done[S];
+        for (int r = 0; r < S; ++r) { done[r] = false; pos[r] = -1; }
+        for (int k = 0; k < S; ++k) {
+            double best = -1.0;
+            int p = -1;
+            for (int r = 0; r < S; ++r) {
+                if (done[r]) continue;
+                const double v = pivot_key(w[r * S + k]);
+                if (v > best) { best = v; p = r; }
+            }
+            piv[k] = p;
+            ok = ok && best != 0.0;
+            const double inv = 1.0 / w[p * S + k];
+            for (int r = 0; r < S; ++r) {
+                if (done[r] || r == p) continue;
+                const double l = w[r * S + k] * inv;
+                w[r * S + k] = l;
+                for (int c = k + 1; c < S; ++c) w[r * S + c] = w[r * S + c] - l * w[p * S + c];
+            }
+            w[p * S + k] = inv;
+            done[p] = true;
+            pos[p] = k;
+        }
+        return ok;
+    }
+
+    static void lu_solve(const double* w, const int* piv, const int* pos, double* b)       // b: the right-hand side in, the solution out
+    {
+        double x[S];
+        for (int k = 0; k < S; ++k) {
+            const double bk = b[piv[k]];
+            for (int r = 0; r < S; ++r)
+                if (pos[r] > k) b[r] = b[r] - w[r * S + k] * bk;
+        }
+        for (int k = S - 1; k >= 0; --k) {
+            const double xk = b[piv[k]] * w[piv[k] * S + k];
+            for (int r = 0; r < S; ++r)
+                if (pos[r] < k) b[r] = b[r] - w[r * S + k] * xk;
+            x[k] = xk;
+        }
+        for (int s = 0; s < S; ++s) b[s] = x[s];
+    }
+
+    static bool step(const double* k, const double* y, double h, double rtol, double atol, double* ynew, double* yemb, double& err2)
+    {
+        double w[S * S], kk[5][S], f[S], arg[S], e[L];
+        int piv[S], pos[S];
+        const double fac = 1.0 / (h * Rodas4::gamma), ih = 1.0 / h;
+        for (int r = 0; r < S; ++r)
+            for (int q = 0; q < S; ++q) {
+                const double m = -Net::jac_entry(r, q, k, y);
+                w[r * S + q] = q == r ? m + fac : m;
+            }
+        const bool ok = lu_factor(w, piv, pos);
+        for (int i = 0; i < 5; ++i)
+            for (int s = 0; s < S; ++s) kk[i][s] = 0.0;
+        for (int s = 0; s < S; ++s) arg[s] = y[s];
+        for (int st = 0; st < 6; ++st) {
+            for (int s = 0; s < S; ++s) arg[s] = stage_arg(st, y[s], arg[s], kk[0][s], kk[1][s], kk[2][s], kk[3][s], kk[4][s]);
+            for (int s = 0; s < S; ++s) {
+                f[s] = Net::rhs_row(s, k, arg);
+                if (st > 0) f[s] = f[s] + stage_add(st, ih, kk[0][s], kk[1][s], kk[2][s], kk[3][s], kk[4][s]);
+            }
+            lu_solve(w, piv, pos, f);
+            if (st < 5)
+                for (int s = 0; s < S; ++s) kk[st][s] = f[s];
+        }
+        for (int i = 0; i < L; ++i) e[i] = 0.0;
+        for (int s = 0; s < S; ++s) {
+            yemb[s] = arg[s];
+            ynew[s] = arg[s] + f[s];
+            const double sk = atol + rtol * dmax(dabs(y[s]), dabs(ynew[s]));
+            const double q = f[s] / sk;
+            e[s] = q * q;
+        }
+        err2 = sum(e) * (1.0 / S);
+        return ok;
+    }
+
+    static double wnorm2(const double* v, const double* y, double rtol, double atol)
+    {
+        double e[L];
+        for (int i = 0; i < L; ++i) e[i] = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double q = v[s] / (atol + rtol * dabs(y[s]));
+            e[s] = q * q;
+        }
+        return sum(e) * (1.0 / S);
+    }
+
+    static double start_step(const double* k, const double* y, double rtol, double atol, double span)
+    {
+        double f0[S], y1[S], f1[S];
+        for (int s = 0; s < S; ++s) f0[s] = Net::rhs_row(s, k, y);
+        const double d0 = wnorm2(y, y, rtol, atol), d1 = wnorm2(f0, y, rtol, atol);
+        const double h0 = start_h0(d0, d1, span);
+        for (int s = 0; s < S; ++s) y1[s] = y[s] + h0 * f0[s];
+        for (int s = 0; s < S; ++s) f1[s] = Net::rhs_row(s, k, y1) - f0[s];
+        return start_h(h0, d1, wnorm2(f1, y, rtol, atol), span);
+    }
+
+    static double integrate(const double* x, const double* blk, double* sim, int* nsteps_out)
+    {
+        const double rtol = blk[1], atol = blk[2], t0 = blk[4];
+        const int max_steps = (int)blk[3], T = (int)blk[5];
+        const double* tt = blk + 6 + S;
+        const double* dat = tt + T;
+        const double* sd = dat + (long long)T * O;
+        const double ninf = -__builtin_huge_val();
+        double k[R > 0 ? R : 1], y[S], yn[S], ye[S], o[O];
+        if (nsteps_out) *nsteps_out = 0;
+        if (!rates(x, k)) return ninf;
+        for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+        double t = t0, acc = 0.0;
+        double h = start_step(k, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300));
+        bool ok = finite(h) && h > 0.0, rejected = false;
+        int nsteps = 0;
+        for (int j = 0; ok && j < T; ++j) {
+            const double tout = tt[j];
+            for (int n = 0; t < tout; ++n) {
+                const bool clip = t + h >= tout;
+                const double hs = clip ? tout - t : h;
+                if (n >= max_steps || t + hs == t) { ok = false; break; }
+                double err2;
+                const bool nonsing = step(k, y, hs, rtol, atol, yn, ye, err2);
+                bool fin = nonsing && finite(err2);
+                for (int s = 0; s < S; ++s) fin = fin && finite(yn[s]);
+                if (!fin) { ok = false; break; }
+                ++nsteps;
+                double fac = step_factor(err2);
+                bool neg = false;
+                for (int s = 0; s < S; ++s) neg = neg || yn[s] < -(atol + rtol * dabs(y[s]));
+                if (neg) fac = dmin(fac, 0.25);
+                if (err2 <= 1.0 && !neg) {
+                    if (rejected) fac = dmin(fac, 1.0);
+                    for (int s = 0; s < S; ++s) y[s] = yn[s];
+                    t = clip ? tout : t + hs;
+                    h = clip ? dmax(h, hs * fac) : hs * fac;
+                    rejected = false;
+                } else {
+                    h = hs * fac;
+                    rejected = true;
+                }
+            }
+            if (!ok) break;
+            Net::obs(y, o);
+            for (int q = 0; q < O; ++q) {
+                const double res = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
+                acc = acc - 0.5 * res * res;
+                if (sim) sim[(long long)j * O + q] = o[q];
+            }
+        }
+        if (nsteps_out) *nsteps_out = nsteps;
+        return ok ? blk[0] + acc : ninf;
+    }
+
+    static bool integrate_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)
+    {
+        double k[R > 0 ? R : 1], yn[S], ye[S];
+        if (!rates(x, k)) return false;
+        for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+        const double h = (t1 - blk[4]) / nsteps;
+        bool ok = true;
+        for (int n = 0; n < nsteps; ++n) {
+            double err2;
+            ok = step(k, y, h, blk[1], blk[2], yn, ye, err2) && ok;
+            for (int s = 0; s < S; ++s) y[s] = which ? ye[s] : yn[s];
+        }
+        return ok;
+    }
+};
+#endif
+
+}  // namespace dzode
+
+// The entry points around a generated network struct NET for groups of LANES lanes: the batch kernel the engine's multi-kernel path
+// launches (dz_set_likelihood_module with lanes_per_point LANES: 256 threads per block, point i on lanes [i * LANES, (i + 1) * LANES) of
+// the grid) and the host build's C functions under dz_ode.h's names.  A group whose point index is >= n reads the last point's row,
+// takes no step and stores nothing: it stays with its wave through every cross-lane operation.
+#if defined(__HIP__)
+#define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_group_batch(const double* X, long long n, int d, int ld, double* like,     \
+                                                                        const void* data)                                              \
+    {                                                                                                                                    \
+        static_assert(NET::S <= LANES, "a lane per species");                                                                            \
+        __shared__ double ks[256 / LANES][NET::R + 1];         /* (+ 1: the groups of a wave read the same j from different banks) */    \
+        const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
+        const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
+        const bool valid = i < n;                                                                                                        \
+        const bool good = dzode::group_rates<NET, LANES>(X + (valid ? i : n - 1) * ld, ks[g], r);                                        \
+        __syncthreads();                                       /* (before any loop a group can leave early) */                           \
+        const double v = dzode::group_integrate<NET, LANES>(ks[g], (const double*)data, r, valid && good);                              \
+        if (valid && r == 0) like[i] = v;                                                                                                \
+    }
+#else
+#define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
+    typedef dzode::HostGroup<NET, LANES> DzodeHostGroup;                                                                                 \
+    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) like[i] = DzodeHostGroup::integrate(X + i * ld, blk, nullptr, nsteps ? nsteps + i : nullptr); \
+    }                                                                                                                                    \
+    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* like)                 \
+    {                                                                                                                                    \
+        const long long per = (long long)(int)blk[5] * NET::O;                                                                           \
+        for (long long i = 0; i < n; ++i) like[i] = DzodeHostGroup::integrate(X + i * ld, blk, sim + i * per, nullptr);                 \
+    }                                                                                                                                    \
+    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
+    {                                                                                                                                    \
+        return DzodeHostGroup::integrate_fixed(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                   \
+    }                                                                                                                                    \
+    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
+    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+#endif

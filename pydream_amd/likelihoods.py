@@ -311,7 +311,9 @@ class DeviceKernelLogLike:
 
     The kernel's signature is KERNEL_SIGNATURE: point i is the row X + i * ld, like[i] receives its log likelihood (-inf allowed); `data`
     is the device copy of the `data` array.  lanes_per_point=1: one thread per point; 64: one wave per point (coalesced row reads, the
-    kernel reduces over its lanes itself).  always_finite=True promises the density is finite wherever the priors are (skips the
+    kernel reduces over its lanes itself); 16 or 32: a group of that many lanes per point, point i on lanes [i * L, (i + 1) * L) of the
+    grid, 256 / L points per block -- the groups of the last block whose point index is >= n run too, so the kernel predicates them
+    instead of returning in front of a cross-lane operation.  always_finite=True promises the density is finite wherever the priors are (skips the
     per-generation "every try impossible?" check of Dream.py:281-289).  host: an optional Python twin f(x[d]) -> float used when the
     object is called on the host (Model.total_logp); without it a call evaluates the point on the device."""
 
@@ -347,6 +349,7 @@ class DeviceKernelLogLike:
 
 # ---------------------------------------------------------------------------------------------------- mass-action ODE models
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
+ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32))      # lanes_per_point=16 | 32: species <= lanes
 _LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
 
 
@@ -356,33 +359,48 @@ def _hexlit(v):
     return "(%s)" % v.hex() if np.isfinite(v) else ("(__builtin_huge_val())" if v > 0 else "(-__builtin_huge_val())")
 
 
-def _ode_source(S, reactions, observables, log10):
-    """The generated network struct (see csrc/dz_ode.h): rate constants, right-hand side, analytic Jacobian and observables as
-    straight-line code with constant indices; powers as repeated products."""
-    R, O = len(reactions), len(observables)
-    N = np.zeros((S, R), dtype=np.int64)
+def _stoichiometry(S, reactions):
+    N = np.zeros((S, len(reactions)), dtype=np.int64)
     for r, (reac, prod, _) in enumerate(reactions):
         for s, c in reac.items():
             N[s, r] -= c
         for s, c in prod.items():
             N[s, r] += c
+    return N
 
-    def product(factors):
-        return " * ".join(factors) if factors else "1.0"
 
-    def rate_factors(reac, skip=None):
-        out = []
-        for s, c in sorted(reac.items()):
-            out += ["y[%d]" % s] * (c - (1 if s == skip else 0))
-        return out
+def _product(factors):
+    return " * ".join(factors) if factors else "1.0"
 
-    def combine(terms):                     # [(integer coefficient, expression)] -> a sum in this order
-        out = ""
-        for c, e in terms:
-            t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
-            out += ("-" if c < 0 else "") + t if not out else (" - " if c < 0 else " + ") + t
-        return out or "0.0"
 
+def _rate_factors(reac, skip=None):
+    out = []
+    for s, c in sorted(reac.items()):
+        out += ["y[%d]" % s] * (c - (1 if s == skip else 0))
+    return out
+
+
+def _combine(terms):                        # [(integer coefficient, expression)] -> a sum in this order
+    out = ""
+    for c, e in terms:
+        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
+        out += ("-" if c < 0 else "") + t if not out else (" - " if c < 0 else " + ") + t
+    return out or "0.0"
+
+
+def _obs_lines(S, observables):
+    L = []
+    for o, row in enumerate(observables):
+        terms = ["y[%d]" % s if row[s] == 1.0 else "%s * y[%d]" % (_hexlit(row[s]), s) for s in range(S) if row[s] != 0.0]
+        L.append("        o[%d] = %s;" % (o, " + ".join(terms) if terms else "0.0"))
+    return L
+
+
+def _ode_source(S, reactions, observables, log10):
+    """The generated network struct (see csrc/dz_ode.h): rate constants, right-hand side, analytic Jacobian and observables as
+    straight-line code with constant indices; powers as repeated products."""
+    R, O = len(reactions), len(observables)
+    N = _stoichiometry(S, reactions)
     L = ["struct Net {",
          "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
          "    DZO_HD static bool rates(const double* x, double* k)", "    {"]
@@ -395,23 +413,67 @@ def _ode_source(S, reactions, observables, log10):
     L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)]))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     for r, (reac, _, _) in enumerate(reactions):
-        L.append("        const double v%d = %s;" % (r, product(["k[%d]" % r] + rate_factors(reac))))
+        L.append("        const double v%d = %s;" % (r, _product(["k[%d]" % r] + _rate_factors(reac))))
     for s in range(S):
-        L.append("        f[%d] = %s;" % (s, combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
+        L.append("        f[%d] = %s;" % (s, _combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
     L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
     for r, (reac, _, _) in enumerate(reactions):        # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
         for q, c in sorted(reac.items()):
-            L.append("        const double d%d_%d = %s;" % (r, q, product(["k[%d]" % r] + (["%d.0" % c] if c > 1 else []) + rate_factors(reac, skip=q))))
+            L.append("        const double d%d_%d = %s;" % (r, q, _product(["k[%d]" % r] + (["%d.0" % c] if c > 1 else []) + _rate_factors(reac, skip=q))))
     for s in range(S):
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
-            L.append("        J[%d] = %s;" % (s * S + q, combine(terms)))
+            L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
     L += ["    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
-    for o, row in enumerate(observables):
-        terms = ["y[%d]" % s if row[s] == 1.0 else "%s * y[%d]" % (_hexlit(row[s]), s) for s in range(S) if row[s] != 0.0]
-        L.append("        o[%d] = %s;" % (o, " + ".join(terms) if terms else "0.0"))
+    L += _obs_lines(S, observables)
     L += ["    }", "};", "DZODE_ENTRIES(Net)", ""]
     return '#include "dz_ode.h"\n' + "\n".join(L)
+
+
+def _ode_group_source(S, reactions, observables, log10, lanes):
+    """The generated network struct for the lane-group solver (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
+    its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
+    stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
+    diverge inside the right-hand side.  Every f[r] and J[r][q] is the sum over the reactions (for J: those with q among the reactants)
+    in ascending reaction index of coefficient(r) * (k[j] * (nu) * y...) -- written here once, compiled for both sides."""
+    R, O = len(reactions), len(observables)
+    N = _stoichiometry(S, reactions)
+
+    def coefficient(j):                     # N[r][j] as a function of r
+        out = "0.0"
+        for s in reversed([s for s in range(S) if N[s, j] != 0]):
+            out = "r == %d ? %d.0 : %s" % (s, N[s, j], out)
+        return "(%s)" % out
+
+    def weighted_sum(terms, indent):        # [(j, expression)] -> statements that leave the sum in v
+        if not terms:
+            return [indent + "return 0.0;"]
+        out = [indent + "int z = 0;", indent + "double v = %s * (%s);" % (coefficient(terms[0][0]), terms[0][1])]
+        for t, (j, e) in enumerate(terms[1:], 1):
+            if t % 4 == 0:                  # (a long sum in groups of four terms: see DZODE_SUM_FENCE in csrc/dz_ode_group.h)
+                out.append(indent + "DZODE_SUM_FENCE(v, r, z);")
+            out.append(indent + "v = v + %s * (%s);" % (coefficient(j), e))
+        return out + [indent + "return v;"]
+
+    L = ["struct Net {",
+         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
+         "    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
+         "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
+    L += ["        case %d: return %d;" % (j, rate) for j, (_, _, rate) in enumerate(reactions) if isinstance(rate, (int, np.integer))]
+    L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
+    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, (_, _, rate) in enumerate(reactions) if not isinstance(rate, (int, np.integer))]
+    L += ["        default: return 0.0;", "        }", "    }",
+          "    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
+    L += weighted_sum([(j, _product(["k[z + %d]" % j] + _rate_factors(reactions[j][0]))) for j in range(R) if np.any(N[:, j] != 0)], "        ")
+    L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
+    for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
+        terms = [(j, _product(["k[z + %d]" % j] + (["%d.0" % reactions[j][0][q]] if reactions[j][0][q] > 1 else []) + _rate_factors(reactions[j][0], skip=q)))
+                 for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
+        L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
+    L += ["        default: return 0.0;", "        }", "    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
+    L += _obs_lines(S, observables)
+    L += ["    }", "};", "DZODE_GROUP_ENTRIES(Net, %d)" % lanes, ""]
+    return '#include "dz_ode_group.h"\n' + "\n".join(L)
 
 
 class MassActionODELogLike:
@@ -437,15 +499,26 @@ class MassActionODELogLike:
 
     The device build runs on the engine's multi-kernel path (dz_set_likelihood_module, one thread per point) with the redraw rounds on.
     A call on the host -- __call__, simulate, the host path of run_dream -- goes through the same generated source compiled for the host
-    (ROCm's clang++, else g++), which gives the same bits.  path: a code object built beforehand (`.code_object()`)."""
+    (ROCm's clang++, else g++), which gives the same bits.  path: a code object built beforehand (`.code_object()`).
+
+    lanes_per_point=1 (the default) keeps a point's whole S x S iteration matrix in one lane's registers: up to 8 species, 64 reactions,
+    8 observables.  lanes_per_point=16 or 32 integrates a point with a GROUP of that many lanes, one matrix row per lane
+    (csrc/dz_ode_group.h: pivoted LU, triangular solves and the error norm over the group's lanes): n_species <= lanes_per_point, up to
+    128 reactions and 16 observables (ODE_GROUP_LIMITS).  Same method, same data block, same host-build contract (the host twin of the
+    group solver gives the device's bits); the two shapes round differently, so their values on a network both can run agree to the
+    integration tolerance, not to the bit."""
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
-                 max_steps=500, ndim=None, path=None):
+                 max_steps=500, ndim=None, path=None, lanes_per_point=1):
         S = int(n_species)
-        if not 1 <= S <= ODE_LIMITS["species"]:
-            raise ValueError("MassActionODELogLike: n_species must be 1..%d (got %d)" % (ODE_LIMITS["species"], S))
-        if not 1 <= len(reactions) <= ODE_LIMITS["reactions"]:
-            raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (ODE_LIMITS["reactions"], len(reactions)))
+        lanes = int(lanes_per_point)
+        if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"]:
+            raise ValueError("MassActionODELogLike: lanes_per_point must be 1, 16 or 32 (got %r)" % (lanes_per_point,))
+        lim = ODE_LIMITS if lanes == 1 else dict(ODE_GROUP_LIMITS, species=lanes)
+        if not 1 <= S <= lim["species"]:
+            raise ValueError("MassActionODELogLike: n_species must be 1..%d (got %d)" % (lim["species"], S))
+        if not 1 <= len(reactions) <= lim["reactions"]:
+            raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (lim["reactions"], len(reactions)))
         if rate_scale not in ("log10", "linear"):
             raise ValueError('MassActionODELogLike: rate_scale must be "log10" or "linear"')
         rx = []
@@ -478,13 +551,13 @@ class MassActionODELogLike:
         if y0.shape != (S,) or not np.all(np.isfinite(y0)) or np.any(y0 < 0):
             raise ValueError("MassActionODELogLike: y0 must hold %d finite, non-negative amounts" % S)
         t = np.asarray(t, dtype=float).reshape(-1)
-        if not 1 <= len(t) <= ODE_LIMITS["times"]:
-            raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (ODE_LIMITS["times"], len(t)))
+        if not 1 <= len(t) <= lim["times"]:
+            raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (lim["times"], len(t)))
         if not np.isfinite(t0) or not np.all(np.isfinite(t)) or np.any(np.diff(t) < 0) or t[0] < t0:
             raise ValueError("MassActionODELogLike: output times must be finite, sorted and >= t0 = %r" % t0)
         obs = np.atleast_2d(np.asarray(observables, dtype=float))
-        if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= ODE_LIMITS["observables"] or not np.all(np.isfinite(obs)):
-            raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, ODE_LIMITS["observables"]))
+        if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= lim["observables"] or not np.all(np.isfinite(obs)):
+            raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, lim["observables"]))
         O, T = len(obs), len(t)
         data = np.asarray(data, dtype=float)
         sd = np.broadcast_to(np.asarray(sd, dtype=float), data.shape) if data.shape == (O, T) else np.asarray(sd, dtype=float)
@@ -499,7 +572,7 @@ class MassActionODELogLike:
         self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
         self.data, self.sd = data, np.array(sd)
         self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
-        self.path = path
+        self.path, self.lanes_per_point = path, lanes
         self._host = None
 
     # ---- the data block (csrc/dz_ode.h) and the generated source
@@ -511,24 +584,34 @@ class MassActionODELogLike:
         return np.concatenate([[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], self.y0, self.t, dat, sd])
 
     def source(self):
-        return _ode_source(self.n_species, self.reactions, self.observables, self.log10)
+        if self.lanes_per_point == 1:
+            return _ode_source(self.n_species, self.reactions, self.observables, self.log10)
+        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point)
 
     @staticmethod
-    def _header_hash():
+    def _header_hash(name="dz_ode.h"):
         import hashlib
         import os
-        with open(os.path.join(csrc_dir(), "dz_ode.h"), "rb") as fh:
+        with open(os.path.join(csrc_dir(), name), "rb") as fh:
             return hashlib.sha256(fh.read()).hexdigest()
 
+    def _unit(self):
+        """The translation unit both builds compile: the generated source and the hashes of the headers it includes (the cache key)."""
+        text = self.source() + "\n// dz_ode.h " + self._header_hash() + "\n"
+        if self.lanes_per_point != 1:
+            text += "// dz_ode_group.h " + self._header_hash("dz_ode_group.h") + "\n"
+        return text
+
     def code_object(self):
-        """The gfx950 code object (kernel dz_ode_batch), compiled with hipcc on first use and cached; the key includes csrc/dz_ode.h."""
+        """The gfx950 code object (kernel dz_ode_batch, or dz_ode_group_batch for a lane group), compiled with hipcc on first use and
+        cached; the key includes csrc/dz_ode.h (and csrc/dz_ode_group.h)."""
         if self.path is None:
-            text = self.source() + "\n// dz_ode.h " + self._header_hash() + "\n"
-            self.path = compile_device_kernel(text, extra_flags=("-I" + csrc_dir(),))
+            self.path = compile_device_kernel(self._unit(), extra_flags=("-I" + csrc_dir(),))
         return self.path
 
     def _dz_apply(self, engine):
-        engine.set_likelihood_module(self.code_object(), "dz_ode_batch", 1, self.data_block(), False)
+        kernel = "dz_ode_batch" if self.lanes_per_point == 1 else "dz_ode_group_batch"
+        engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False)
 
     # ---- the host build
     def host_library(self):
@@ -538,8 +621,7 @@ class MassActionODELogLike:
             import os
             cc = "/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else "g++"
             flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-I" + csrc_dir()]
-            text = self.source() + "\n// dz_ode.h " + self._header_hash() + "\n"
-            so = _build_cached(text, ".so", ".cpp", lambda src, out: [cc] + flags + ["-o", out, src, "-lm"],
+            so = _build_cached(self._unit(), ".so", ".cpp", lambda src, out: [cc] + flags + ["-o", out, src, "-lm"],
                                (os.path.basename(cc), " for the host build of the ODE likelihood"), [cc, _compiler_version(cc)] + flags)
             L = C.CDLL(so)
             P, I64, D, I = C.POINTER(C.c_double), C.c_longlong, C.c_double, C.c_int

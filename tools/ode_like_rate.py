@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""Rate of the device ODE likelihood (pydream_amd.likelihoods.MassActionODELogLike, csrc/dz_ode.h) on the Robertson network at
-4096 chains x 5 tries over the example's prior box (nominal log10 rate constants +- 3):
+"""Rate of the device ODE likelihood (pydream_amd.likelihoods.MassActionODELogLike, csrc/dz_ode.h and csrc/dz_ode_group.h) at
+4096 chains x 5 tries over a prior box around the nominal log10 rate constants (Robertson: +- 3, the example's; the others: +- 1):
 
   * the likelihood kernel alone: eval_logp on the 20 480 points of one generation -- us per launch, points/s;
   * steps per point (attempted Rodas4 steps, rejections included; from the host build, which takes the same steps) and lane efficiency,
-    sum of steps / (64 x the wave's maximum) over the kernel's waves of 64 consecutive points;
+    sum of steps / (points per wave x the wave's maximum) over the kernel's waves: 64 consecutive points with one lane per point,
+    64 / lanes with a lane group per point;
   * run_dream generations/s with the likelihood on the device against the host path with 16 worker processes
-    (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and for the reference example's odeint likelihood.
+    (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
-    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only]
+    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|chain8|enzyme13|chain32] [--lanes 1|16|32]
+
+chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
+scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
+enzyme13: pydream_amd/examples/enzyme.  --lanes defaults to the fewest lanes the network fits in.
 """
 import json
 import os
@@ -48,14 +53,32 @@ def odeint_like(logk):
     return lp if np.isfinite(lp) else -np.inf
 
 
-def gens_per_s(like, N, k, G, host_workers=None):
+def network(name, lanes):
+    """(likelihood, nominal, half width of the prior box)"""
+    if name == "robertson":
+        assert lanes in (None, 1), "robertson is the one-lane example"
+        return ROB.make_likelihood(), ROB.NOMINAL, 3.0
+    if name == "enzyme13":
+        from pydream_amd.examples.enzyme import enzyme_device as ENZ
+        return ENZ.make_likelihood(lanes_per_point=lanes or 16), ENZ.NOMINAL, 1.0
+    from tests import ode_wide_networks as W
+    S = dict(chain8=8, chain32=32)[name]
+    if (lanes or (1 if S == 8 else 32)) == 1:                   # the same network and data through the one-lane kernel
+        from pydream_amd.likelihoods import MassActionODELogLike
+        grp = W.chain(S, 16)
+        rx, y0, obs = W.chain_network(S)
+        return MassActionODELogLike(S, rx, y0, W.CHAIN_T, obs, grp.data, grp.sd), W.CHAIN_NOMINAL, 1.0
+    return W.chain(S, lanes or 32), W.CHAIN_NOMINAL, 1.0
+
+
+def gens_per_s(like, N, k, G, host_workers=None, nominal=ROB.NOMINAL, width=3.0):
     """generations/s of run_dream from the difference of a G-generation and a 2G-generation run (setup and compilation cancel)"""
     from scipy.stats import uniform
     from pydream_amd.core import run_dream
     from pydream_amd.parameters import SampledParam
-    params = [SampledParam(uniform, loc=ROB.NOMINAL - 3, scale=6)]
+    params = [SampledParam(uniform, loc=nominal - width, scale=2 * width)]
     rng = np.random.default_rng(3)
-    starts = [ROB.NOMINAL + 0.3 * rng.uniform(-1, 1, 3) for _ in range(N)]
+    starts = [nominal + 0.1 * width * rng.uniform(-1, 1, len(nominal)) for _ in range(N)]
     if host_workers is not None:
         os.environ["DREAMZS_HOST_WORKERS"] = str(host_workers)
     try:
@@ -70,13 +93,13 @@ def gens_per_s(like, N, k, G, host_workers=None):
     return G / max(t[1] - t[0], 1e-9)
 
 
-def main(N=4096, k=5, G=20, kernel_only=False):
+def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
     from pydream_amd import _capi
-    like = ROB.make_likelihood()
-    n = N * k
-    X = ROB.NOMINAL - 3 + 6 * np.random.default_rng(11).uniform(size=(n, 3))
-    eng = _capi.Engine(nchains=N, ndim=3, multitry=k, history_capacity=8)
-    eng.set_prior(np.full(3, 2, dtype=np.int32), ROB.NOMINAL - 3, np.full(3, 6.0))
+    like, nominal, width = network(name, lanes)
+    n, d = N * k, len(nominal)
+    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
+    eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
+    eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
     like._dz_apply(eng)
     for _ in range(3):
         eng.eval_logp(X)
@@ -86,23 +109,33 @@ def main(N=4096, k=5, G=20, kernel_only=False):
     us = (time.perf_counter() - t0) / reps * 1e6
     host, steps = like.batch(X, return_steps=True)
     assert lk.tobytes() == host.tobytes(), "device and host builds differ"
-    w = steps[: n // 64 * 64].reshape(-1, 64)
-    out = dict(chains=N, tries=k, points=n, us_per_launch=round(us, 1), points_per_s=round(n / us * 1e6),
-               steps_median=float(np.median(steps)), steps_max=int(steps.max()), lane_efficiency=round(float(w.sum() / (64 * w.max(axis=1)).sum()), 3),
-               failed_points=int(np.sum(lk == -np.inf)))
+    per_wave = 64 // like.lanes_per_point
+    w = steps[: n // per_wave * per_wave].reshape(-1, per_wave)
+    out = dict(network=name, lanes=like.lanes_per_point, chains=N, tries=k, points=n, us_per_launch=round(us, 1), points_per_s=round(n / us * 1e6),
+               steps_median=float(np.median(steps)), steps_max=int(steps.max()),
+               lane_efficiency=round(float(w.sum() / (per_wave * w.max(axis=1)).sum()), 3), failed_points=int(np.sum(lk == -np.inf)))
     print(json.dumps(out), flush=True)
     if kernel_only:
         return out
-    out["device_gens_per_s"] = round(gens_per_s(like, N, k, G), 2)
+    out["device_gens_per_s"] = round(gens_per_s(like, N, k, G, nominal=nominal, width=width), 2)
     print(json.dumps(out), flush=True)
-    out["host_build_16w_gens_per_s"] = round(gens_per_s(HostOnly(like), N, k, 2, host_workers=16), 3)
-    print(json.dumps(out), flush=True)
-    out["odeint_16w_gens_per_s"] = round(gens_per_s(odeint_like, N, k, 1, host_workers=16), 3)
+    out["host_build_16w_gens_per_s"] = round(gens_per_s(HostOnly(like), N, k, 2, host_workers=16, nominal=nominal, width=width), 3)
     out["speedup_vs_host_build"] = round(out["device_gens_per_s"] / out["host_build_16w_gens_per_s"], 1)
-    out["speedup_vs_odeint"] = round(out["device_gens_per_s"] / out["odeint_16w_gens_per_s"], 1)
     print(json.dumps(out), flush=True)
+    if name == "robertson":
+        out["odeint_16w_gens_per_s"] = round(gens_per_s(odeint_like, N, k, 1, host_workers=16), 3)
+        out["speedup_vs_odeint"] = round(out["device_gens_per_s"] / out["odeint_16w_gens_per_s"], 1)
+        print(json.dumps(out), flush=True)
     return out
 
 
 if __name__ == "__main__":
-    main(*(int(a) for a in sys.argv[1:4] if not a.startswith("--")), kernel_only="--kernel-only" in sys.argv)
+    argv = sys.argv[1:]
+    opt = {}
+    for flag in ("--network", "--lanes"):
+        if flag in argv:
+            i = argv.index(flag)
+            opt[flag] = argv[i + 1]
+            del argv[i:i + 2]
+    main(*(int(a) for a in argv[:3] if not a.startswith("--")), kernel_only="--kernel-only" in argv, name=opt.get("--network", "robertson"),
+         lanes=int(opt["--lanes"]) if "--lanes" in opt else None)
