@@ -27,6 +27,15 @@
 #include <stdint.h>
 #include <string.h>
 
+// Between the reactions of a long generated sum (likelihoods._ode_long_source, more than 16 reactions): on the device the partial sum
+// passes through an empty asm statement, so the compiler keeps the reactions in the order written and holds one rate at a time, not all
+// R of them.  Values and order of operations are unchanged.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DZODE_FENCE(v) asm volatile("" : "+v"(v))
+#else
+#define DZODE_FENCE(v) ((void)0)
+#endif
+
 namespace dzode {
 
 // ---------------------------------------------------------------- elementary functions

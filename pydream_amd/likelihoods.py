@@ -396,10 +396,65 @@ def _obs_lines(S, observables):
     return L
 
 
+_ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
+
+
+def _ode_long_source(S, reactions, observables, log10):
+    """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
+    order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
+    reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
+    used, not one per reaction, and a fixed rate constant is a literal where it is used: what stays in registers through the
+    integration is the number of distinct parameters."""
+    R, O = len(reactions), len(observables)
+    N = _stoichiometry(S, reactions)
+    used = sorted({rate for _, _, rate in reactions if isinstance(rate, (int, np.integer))})
+    kname = ["k[%d]" % used.index(rate) if isinstance(rate, (int, np.integer)) else _hexlit(rate) for _, _, rate in reactions]
+
+    def add(target, started, c, e):
+        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
+        if target in started:
+            return "        %s = %s %s %s;" % (target, target, "-" if c < 0 else "+", t)
+        started.add(target)
+        return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
+
+    L = ["struct Net {",
+         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
+         "    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L += ["        k[%d] = %s;" % (i, ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p) for i, p in enumerate(used)]
+    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in used] + ["dzode::finite(k[%d])" % i for i in range(len(used))]) or "true"))
+    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
+    started = set()
+    for r, (reac, _, _) in enumerate(reactions):
+        rows = [s for s in range(S) if N[s, r] != 0]
+        if not rows:
+            continue
+        L.append("        const double v%d = %s;" % (r, _product([kname[r]] + _rate_factors(reac))))
+        L += [add("f[%d]" % s, started, int(N[s, r]), "v%d" % r) for s in rows]
+        L.append("        " + " ".join("DZODE_FENCE(f[%d]);" % s for s in rows))
+    L += ["        f[%d] = 0.0;" % s for s in range(S) if "f[%d]" % s not in started]
+    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
+    started = set()
+    for r, (reac, _, _) in enumerate(reactions):        # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
+        rows = [s for s in range(S) if N[s, r] != 0]
+        for q, c in sorted(reac.items()):
+            if not rows:
+                continue
+            L.append("        const double d%d_%d = %s;" % (r, q, _product([kname[r]] + (["%d.0" % c] if c > 1 else []) + _rate_factors(reac, skip=q))))
+            L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
+            L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
+    L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
+    L += ["    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
+    L += _obs_lines(S, observables)
+    L += ["    }", "};", "DZODE_ENTRIES(Net)", ""]
+    return '#include "dz_ode.h"\n' + "\n".join(L)
+
+
 def _ode_source(S, reactions, observables, log10):
     """The generated network struct (see csrc/dz_ode.h): rate constants, right-hand side, analytic Jacobian and observables as
     straight-line code with constant indices; powers as repeated products."""
     R, O = len(reactions), len(observables)
+    if R > _ODE_WHOLE_SUMS:
+        return _ode_long_source(S, reactions, observables, log10)
     N = _stoichiometry(S, reactions)
     L = ["struct Net {",
          "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
@@ -502,7 +557,9 @@ class MassActionODELogLike:
     (ROCm's clang++, else g++), which gives the same bits.  path: a code object built beforehand (`.code_object()`).
 
     lanes_per_point=1 (the default) keeps a point's whole S x S iteration matrix in one lane's registers: up to 8 species, 64 reactions,
-    8 observables.  lanes_per_point=16 or 32 integrates a point with a GROUP of that many lanes, one matrix row per lane
+    8 observables.  Without scratch memory as measured at 8 species: up to 64 reactions over at most 32 distinct parameters, or 40
+    reactions with a parameter each; more distinct parameters than that spill 90..280 bytes per lane (same values, slower; see
+    DESIGN.md).  lanes_per_point=16 or 32 integrates a point with a GROUP of that many lanes, one matrix row per lane
     (csrc/dz_ode_group.h: pivoted LU, triangular solves and the error norm over the group's lanes): n_species <= lanes_per_point, up to
     128 reactions and 16 observables (ODE_GROUP_LIMITS).  Same method, same data block, same host-build contract (the host twin of the
     group solver gives the device's bits); the two shapes round differently, so their values on a network both can run agree to the

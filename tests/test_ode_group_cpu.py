@@ -51,6 +51,19 @@ def test_networks_at_the_reaction_limit_compile_without_scratch(S, R, lanes, tmp
     assert n["scratch"] == 0
 
 
+@pytest.mark.parametrize("S,R,lanes", [(8, 64, 1), (8, 32, 1)])
+def test_one_lane_networks_at_the_reaction_limit_compile_without_scratch(S, R, lanes, tmp_path, monkeypatch):
+    """The one-lane build at its limits, 8 species and up to 64 reactions, on the same recipe (20 parameters): scratch 0.  Above 16
+    reactions its generated source builds every sum up reaction by reaction behind fences and keeps one rate constant per parameter
+    (likelihoods._ode_long_source); written like the short form these two took 512 registers and 796 / 84 bytes of scratch."""
+    monkeypatch.setenv("DREAMZS_KERNEL_CACHE", str(tmp_path))
+    like = W.dense_network(S, R, lanes)
+    assert "DZODE_FENCE" in like.source() and "dz_ode_group" not in like.source()
+    n = _notes(like.code_object())
+    print("dense S=%d R=%d @%d: %d VGPRs (%d of them AGPRs), scratch %d" % (S, R, lanes, n["vgpr"], n["agpr"], n["scratch"]))
+    assert n["scratch"] == 0
+
+
 def _max_rel_err(like, refs, X, rtol):
     """max over points, times and observables of |sim - ref| / (rtol |ref| + rtol)"""
     sim = like.simulate(X)

@@ -1,4 +1,5 @@
-"""MassActionODELogLike without a GPU: the generated solver cross-compiles for gfx950 without scratch, the host build of the same source
+"""MassActionODELogLike without a GPU: the generated solver cross-compiles for gfx950 without scratch on the networks here (the one-lane
+limit of 64 reactions: tests/test_ode_group_cpu.py; the measured boundary beyond it: DESIGN.md), the host build of the same source
 is accurate against scipy's Radau and has the Rosenbrock pair's orders, limits are checked at construction, and the kernel cache refuses
 a fallback directory that others could write to."""
 import os
