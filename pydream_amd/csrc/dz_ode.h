@@ -17,6 +17,9 @@
 //   [6, 6+S) y0,   then t[T],   data[T*O] (time-major),   sd[T*O]   (an unobserved entry: data 0, sd +inf -- it adds exactly 0)
 //
 // Every loop is bounded: at most max_steps attempted steps per output interval, T intervals.
+//
+// The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
+// this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -272,45 +275,58 @@ DZO_HD double wnorm2(const double* v, const double* y, double rtol, double atol)
     return e2 * (1.0 / S);
 }
 
-// Hairer, Norsett & Wanner I, II.4 starting step, with the norms' roots folded into dexp / dlog; at most span.
-template <class Net>
-DZO_HD double start_step(const double* k, const double* y, double rtol, double atol, double span)
+// ---------------------------------------------------------------- the controller's formulas, shared by every shape
+// the step controller: the factor from the error, before the negativity and rejection caps
+// err = sqrt(err2); h_new = h * clamp(0.9 err^(-1/4), 0.2, 6), no growth right after a rejection
+DZO_HD double step_factor(double err2)
 {
-    constexpr int S = Net::S;
-    double f0[S], y1[S], f1[S];
-    Net::rhs(k, y, f0);
-    const double d0 = wnorm2<S>(y, y, rtol, atol), d1 = wnorm2<S>(f0, y, rtol, atol);
-    const double h0 = (d0 < 1e-10 || d1 < 1e-10) ? 1e-6 : dmin(0.01 * dexp(0.5 * (dlog(d0) - dlog(d1))), span);
-#pragma unroll
-    for (int s = 0; s < S; ++s) y1[s] = y[s] + h0 * f0[s];
-    Net::rhs(k, y1, f1);
-#pragma unroll
-    for (int s = 0; s < S; ++s) f1[s] = f1[s] - f0[s];
-    const double m = dmax(d1, wnorm2<S>(f1, y, rtol, atol) / (h0 * h0));       // max(d1, d2)^2
+    const double fac = err2 > 0.0 ? 0.9 * dexp(-0.125 * dlog(err2)) : 6.0;
+    return dmin(6.0, dmax(0.2, fac));
+}
+
+// Hairer, Norsett & Wanner I, II.4 starting step, with the norms' roots folded into dexp / dlog; at most span.
+DZO_HD double start_h0(double d0, double d1, double span)
+{
+    return (d0 < 1e-10 || d1 < 1e-10) ? 1e-6 : dmin(0.01 * dexp(0.5 * (dlog(d0) - dlog(d1))), span);
+}
+
+DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h: the norm of f1 - f0, still to be divided by h0^2
+{
+    const double m = dmax(d1, d2h / (h0 * h0));                            // max(d1, d2)^2
     const double h1 = m <= 1e-30 ? dmax(1e-6, h0 * 1e-3) : dexp((dlog(0.01) - 0.5 * dlog(m)) * 0.2);
     return dmin(dmin(100.0 * h0, h1), span);
 }
 
-// The log-likelihood of one point (and, with sim != nullptr, the observables at every output time, [T][O]).  -inf when a rate constant
-// or the state is not finite, the iteration matrix is singular, a step underflows or an output interval needs more than max_steps steps.
-template <class Net>
-DZO_HD double integrate(const double* x, const double* blk, double* sim, int* nsteps_out)
+// ---------------------------------------------------------------- the one stepping loop
+// The log-likelihood of one point (and, with sim != nullptr, the observables at every output time, [T][O]; with nsteps_out, the steps
+// that passed the finiteness test).  -inf when the point is not live (a rate constant that is not finite, a point past the batch's end),
+// the state is not finite, the iteration matrix is singular, a step underflows or an output interval needs more than max_steps steps.
+// Who holds the state is the SHAPE's business.  A shape sh supplies
+//     Shape::S, Shape::O, Shape::State                 (S doubles, or one double per lane of a group)
+//     sh.init(blk, y)                                  y0 from the data block
+//     sh.start_step(y, rtol, atol, span)               the starting step
+//     sh.step(y, h, rtol, atol, yn, err2)              one Rodas4 step: the order-4 solution and err2; false if W is singular
+//     sh.all_finite(yn, seed)                          seed && every amount of yn finite
+//     sh.any_negative(yn, y, rtol, atol)               an amount of yn below -(atol + rtol |y|)
+//     sh.observe(y, o)                                 o[O]
+// and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
+// Group<Net, L> (dz_ode_group.h: a group of L lanes per point, and its host twin).  A point that is not live keeps h = 0, ok = false and
+// takes no step, but does not return ahead of the loop: the lanes of a group stay with their wave.
+template <class Shape>
+DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* sim, int* nsteps_out)
 {
-    constexpr int S = Net::S, O = Net::O;
+    constexpr int S = Shape::S, O = Shape::O;
     const double rtol = blk[1], atol = blk[2], t0 = blk[4];
     const int max_steps = (int)blk[3], T = (int)blk[5];
     const double* tt = blk + 6 + S;
     const double* dat = tt + T;
     const double* sd = dat + (long long)T * O;
-    const double ninf = -__builtin_huge_val();
-    double k[Net::R > 0 ? Net::R : 1];
-    double y[S], yn[S], ye[S], o[O];
-    if (!Net::rates(x, k)) return ninf;
-#pragma unroll
-    for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+    typename Shape::State y, yn;
+    double o[O];
+    sh.init(blk, y);
     double t = t0, acc = 0.0;
-    double h = start_step<Net>(k, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300));
-    bool ok = finite(h) && h > 0.0, rejected = false;
+    double h = live ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
+    bool ok = live && finite(h) && h > 0.0, rejected = false;
     int nsteps = 0;
     for (int j = 0; ok && j < T; ++j) {
         const double tout = tt[j];
@@ -319,25 +335,17 @@ DZO_HD double integrate(const double* x, const double* blk, double* sim, int* ns
             const double hs = clip ? tout - t : h;
             if (n >= max_steps || t + hs == t) { ok = false; break; }
             double err2;
-            const bool nonsing = rodas4_step<Net>(k, y, hs, rtol, atol, yn, ye, err2);
-            bool fin = nonsing && finite(err2);
-#pragma unroll
-            for (int s = 0; s < S; ++s) fin = fin && finite(yn[s]);
-            if (!fin) { ok = false; break; }
+            const bool nonsing = sh.step(y, hs, rtol, atol, yn, err2);
+            if (!sh.all_finite(yn, nonsing && finite(err2))) { ok = false; break; }
             ++nsteps;
-            // err = sqrt(err2); h_new = h * clamp(0.9 err^(-1/4), 0.2, 6), no growth right after a rejection
-            double fac = err2 > 0.0 ? 0.9 * dexp(-0.125 * dlog(err2)) : 6.0;
-            fac = dmin(6.0, dmax(0.2, fac));
+            double fac = step_factor(err2);
             // amounts are non-negative: a step that takes one below -(atol + rtol |y|) is rejected like a failed error test (CVODE's
             // inequality constraints).  Left in, such an undershoot of a species with a second-order loss grows without bound.
-            bool neg = false;
-#pragma unroll
-            for (int s = 0; s < S; ++s) neg = neg || yn[s] < -(atol + rtol * dabs(y[s]));
+            const bool neg = sh.any_negative(yn, y, rtol, atol);
             if (neg) fac = dmin(fac, 0.25);
             if (err2 <= 1.0 && !neg) {
                 if (rejected) fac = dmin(fac, 1.0);
-#pragma unroll
-                for (int s = 0; s < S; ++s) y[s] = yn[s];
+                y = yn;
                 t = clip ? tout : t + hs;
                 h = clip ? dmax(h, hs * fac) : hs * fac;       // (a step clipped to the output time leaves the controller's size alone)
                 rejected = false;
@@ -347,7 +355,7 @@ DZO_HD double integrate(const double* x, const double* blk, double* sim, int* ns
             }
         }
         if (!ok) break;
-        Net::obs(y, o);
+        sh.observe(y, o);
 #pragma unroll
         for (int q = 0; q < O; ++q) {
             const double r = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
@@ -356,24 +364,99 @@ DZO_HD double integrate(const double* x, const double* blk, double* sim, int* ns
         }
     }
     if (nsteps_out) *nsteps_out = nsteps;
-    return ok ? blk[0] + acc : ninf;
+    return ok ? blk[0] + acc : -__builtin_huge_val();
+}
+
+// ---------------------------------------------------------------- the array shapes: the whole state in one place
+// An algebra ALG says how a step is computed on S doubles: ALG::Net, rates(x, k), rhs(k, y, f), wnorm2(v, y, rtol, atol) and
+// step(k, y, h, rtol, atol, ynew, yemb, err2).  OneLane is dz_ode.h's own (row-oriented LU, left-to-right norm), compiled for host and
+// device; HostGroup (dz_ode_group.h) mirrors the lane group's operation order.
+template <class NET>
+struct OneLane {
+    typedef NET Net;
+    static constexpr int S = Net::S;
+    DZO_HD static bool rates(const double* x, double* k) { return Net::rates(x, k); }
+    DZO_HD static void rhs(const double* k, const double* y, double* f) { Net::rhs(k, y, f); }
+    DZO_HD static double wnorm2(const double* v, const double* y, double rtol, double atol) { return dzode::wnorm2<S>(v, y, rtol, atol); }
+    DZO_HD static bool step(const double* k, const double* y, double h, double rtol, double atol, double* ynew, double* yemb, double& err2)
+    {
+        return rodas4_step<Net>(k, y, h, rtol, atol, ynew, yemb, err2);
+    }
+};
+
+template <class Alg>
+DZO_HD double start_step(const double* k, const double* y, double rtol, double atol, double span)
+{
+    constexpr int S = Alg::Net::S;
+    double f0[S], y1[S], f1[S];
+    Alg::rhs(k, y, f0);
+    const double d0 = Alg::wnorm2(y, y, rtol, atol), d1 = Alg::wnorm2(f0, y, rtol, atol);
+    const double h0 = start_h0(d0, d1, span);
+#pragma unroll
+    for (int s = 0; s < S; ++s) y1[s] = y[s] + h0 * f0[s];
+    Alg::rhs(k, y1, f1);
+#pragma unroll
+    for (int s = 0; s < S; ++s) f1[s] = f1[s] - f0[s];
+    return start_h(h0, d1, Alg::wnorm2(f1, y, rtol, atol), span);
+}
+
+template <class Alg>
+struct Array {
+    static constexpr int S = Alg::Net::S, O = Alg::Net::O;
+    struct State { double v[S]; };
+    const double* k;                                   // the rate constants
+    DZO_HD void init(const double* blk, State& y) const
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) y.v[s] = blk[6 + s];
+    }
+    DZO_HD double start_step(const State& y, double rtol, double atol, double span) const { return dzode::start_step<Alg>(k, y.v, rtol, atol, span); }
+    DZO_HD bool step(const State& y, double h, double rtol, double atol, State& yn, double& err2) const
+    {
+        double ye[S];
+        return Alg::step(k, y.v, h, rtol, atol, yn.v, ye, err2);
+    }
+    DZO_HD bool all_finite(const State& yn, bool fin) const
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) fin = fin && finite(yn.v[s]);
+        return fin;
+    }
+    DZO_HD bool any_negative(const State& yn, const State& y, double rtol, double atol) const
+    {
+        bool neg = false;
+#pragma unroll
+        for (int s = 0; s < S; ++s) neg = neg || yn.v[s] < -(atol + rtol * dabs(y.v[s]));
+        return neg;
+    }
+    DZO_HD void observe(const State& y, double* o) const { Alg::Net::obs(y.v, o); }
+};
+
+// One point through an array shape.  The rate constants are tested here, ahead of the loop, and the loop runs with live a constant.
+template <class Alg>
+DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out)
+{
+    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    if (nsteps_out) *nsteps_out = 0;
+    if (!Alg::rates(x, k)) return -__builtin_huge_val();
+    return integrate(Array<Alg>{k}, blk, true, sim, nsteps_out);
 }
 
 // Fixed steps (the order test only): nsteps steps of (t1 - t0) / nsteps from y0, propagating the order-4 solution (which = 0) or the
 // embedded order-3 one (which = 1).  The final state in y; false if a step failed.
-template <class Net>
+template <class Alg>
 DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)
 {
-    constexpr int S = Net::S;
-    double k[Net::R > 0 ? Net::R : 1], yn[S], ye[S];
-    if (!Net::rates(x, k)) return false;
+    constexpr int S = Alg::Net::S;
+    double k[Alg::Net::R > 0 ? Alg::Net::R : 1], yn[S], ye[S];
+    if (!Alg::rates(x, k)) return false;
 #pragma unroll
     for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
     const double h = (t1 - blk[4]) / nsteps;
     bool ok = true;
     for (int n = 0; n < nsteps; ++n) {
         double err2;
-        ok = rodas4_step<Net>(k, y, h, blk[1], blk[2], yn, ye, err2) && ok;
+        ok = Alg::step(k, y, h, blk[1], blk[2], yn, ye, err2) && ok;
 #pragma unroll
         for (int s = 0; s < S; ++s) y[s] = which ? ye[s] : yn[s];
     }
@@ -381,6 +464,24 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
 }
 
 }  // namespace dzode
+
+// The host build's C functions around an algebra ALG (a plain type name), for the one-lane and the lane-group source alike.
+#define DZODE_HOST_ENTRIES(ALG)                                                                                                         \
+    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate_point<ALG>(X + i * ld, blk, nullptr, nsteps ? nsteps + i : nullptr); \
+    }                                                                                                                                    \
+    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* like)                 \
+    {                                                                                                                                    \
+        const long long per = (long long)(int)blk[5] * ALG::Net::O;                                                                      \
+        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate_point<ALG>(X + i * ld, blk, sim + i * per, nullptr);               \
+    }                                                                                                                                    \
+    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
+    {                                                                                                                                    \
+        return dzode::integrate_fixed<ALG>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
+    }                                                                                                                                    \
+    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
+    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
 
 // The entry points around a generated network struct NET: the batch kernel the engine's multi-kernel path launches (one thread per
 // point, 256 threads per block: dz_set_likelihood_module with lanes_per_point 1) and the host build's C functions.
@@ -391,23 +492,10 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     {                                                                                                                                    \
         const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
         if (i >= n) return;                                                                                                              \
-        like[i] = dzode::integrate<NET>(X + i * ld, (const double*)data, nullptr, nullptr);                                             \
+        like[i] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, (const double*)data, nullptr, nullptr);                       \
     }
 #else
 #define DZODE_ENTRIES(NET)                                                                                                              \
-    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
-    {                                                                                                                                    \
-        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate<NET>(X + i * ld, blk, nullptr, nsteps ? nsteps + i : nullptr);     \
-    }                                                                                                                                    \
-    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* like)                 \
-    {                                                                                                                                    \
-        const long long per = (long long)(int)blk[5] * NET::O;                                                                           \
-        for (long long i = 0; i < n; ++i) like[i] = dzode::integrate<NET>(X + i * ld, blk, sim + i * per, nullptr);                     \
-    }                                                                                                                                    \
-    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
-    {                                                                                                                                    \
-        return dzode::integrate_fixed<NET>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
-    }                                                                                                                                    \
-    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
-    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+    typedef dzode::OneLane<NET> DzodeOneLane;                                                                                            \
+    DZODE_HOST_ENTRIES(DzodeOneLane)
 #endif

@@ -1,7 +1,7 @@
 // dz_ode_group.h -- dz_ode.h's solver for networks of 9..32 species: a GROUP of L = 16 or 32 lanes integrates one point together
-// (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32)).  The method is dz_ode.h's, unchanged: Rodas4 with the same
-// coefficients, step controller, start step, negativity rule, max_steps per output interval, exact landing on the output times and -inf
-// on any failure; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
+// (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32)).  The method is dz_ode.h's, and so is the code: its stepping loop
+// (dzode::integrate: step controller, negativity rule, max_steps per output interval, exact landing on the output times, -inf on any
+// failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
 //     row r of W = I / (h gamma) - J in registers (S doubles, constant column indices after unrolling),
 //     entry r of y, of the stage argument u and of k1..k6,
 //     one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled by S group broadcasts per stage);
@@ -21,7 +21,8 @@
 // bits); the groups of a wave may diverge from each other, so nothing inside a step loop is wider than a group.
 //
 // The host twin (HostGroup below) is a plain loop over rows that performs the same floating-point operations in the same order: the same
-// generated rhs_row / jac_entry, the same pivot rule, the same column-oriented solves, the same summation tree.  It does not give the
+// generated rhs_row / jac_entry, the same pivot rule, the same column-oriented solves, the same summation tree.  It holds only those
+// parts; loop, start step and fixed steps are dz_ode.h's, written on HostGroup's rhs, wnorm2 and step.  It does not give the
 // bits of dz_ode.h on a network both can run (lu_solve's row-oriented back substitution sums in the other direction).
 //
 // The network comes from generated code (likelihoods._ode_group_source): a struct with
@@ -79,25 +80,6 @@ DZO_HD double pivot_key(double a)          // |a|, a NaN as +inf: the arg-max is
 {
     const double v = dabs(a);
     return v == v ? v : __builtin_huge_val();
-}
-
-// the step controller of dz_ode.h's integrate: the factor from the error, before the negativity and rejection caps
-DZO_HD double step_factor(double err2)
-{
-    const double fac = err2 > 0.0 ? 0.9 * dexp(-0.125 * dlog(err2)) : 6.0;
-    return dmin(6.0, dmax(0.2, fac));
-}
-
-DZO_HD double start_h0(double d0, double d1, double span)
-{
-    return (d0 < 1e-10 || d1 < 1e-10) ? 1e-6 : dmin(0.01 * dexp(0.5 * (dlog(d0) - dlog(d1))), span);
-}
-
-DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h: the norm of f1 - f0, still to be divided by h0^2
-{
-    const double m = dmax(d1, d2h / (h0 * h0));
-    const double h1 = m <= 1e-30 ? dmax(1e-6, h0 * 1e-3) : dexp((dlog(0.01) - 0.5 * dlog(m)) * 0.2);
-    return dmin(dmin(100.0 * h0, h1), span);
 }
 
 template <class Net>
@@ -293,64 +275,43 @@ __device__ __forceinline__ double group_start_step(const double* ks, double y, d
     return start_h(h0, d1, group_wnorm2<S, L>(f1, y, rtol, atol, r), span);
 }
 
-// The log-likelihood of the group's point, the same value in every lane.  live = false (a point past the batch's end, or a rate constant
-// that is not finite): no step is taken, -inf.
+// The group's shape for dz_ode.h's integrate: lane r's entry of the state.  Every lane of the group returns the same value.  The caller's
+// live = false (a point past the batch's end, or a rate constant that is not finite): no step is taken, -inf.
 template <class Net, int L>
-__device__ __forceinline__ double group_integrate(const double* ks, const double* blk, int r, bool live)
-{
-    constexpr int S = Net::S, O = Net::O;
-    const double rtol = blk[1], atol = blk[2], t0 = blk[4];
-    const int max_steps = (int)blk[3], T = (int)blk[5];
-    const double* tt = blk + 6 + S;
-    const double* dat = tt + T;
-    const double* sd = dat + (long long)T * O;
-    const bool act = r < S;
-    double y = act ? blk[6 + r] : 0.0;
-    double t = t0, acc = 0.0;
-    double h = live ? group_start_step<Net, L>(ks, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300), r) : 0.0;
-    bool ok = live && finite(h) && h > 0.0, rejected = false;
-    for (int j = 0; ok && j < T; ++j) {
-        const double tout = tt[j];
-        for (int n = 0; t < tout; ++n) {
-            const bool clip = t + h >= tout;
-            const double hs = clip ? tout - t : h;
-            if (n >= max_steps || t + hs == t) { ok = false; break; }
-            double yn, err2;
-            const bool nonsing = group_step<Net, L>(ks, y, hs, rtol, atol, r, yn, err2);
-            if (!nonsing || !finite(err2) || Lanes<L>::any(!finite(yn))) { ok = false; break; }
-            double fac = step_factor(err2);
-            const bool neg = Lanes<L>::any(yn < -(atol + rtol * dabs(y)));
-            if (neg) fac = dmin(fac, 0.25);
-            if (err2 <= 1.0 && !neg) {
-                if (rejected) fac = dmin(fac, 1.0);
-                y = yn;
-                t = clip ? tout : t + hs;
-                h = clip ? dmax(h, hs * fac) : hs * fac;
-                rejected = false;
-            } else {
-                h = hs * fac;
-                rejected = true;
-            }
-        }
-        if (!ok) break;
-        double yr[S], o[O];
+struct Group {
+    static constexpr int S = Net::S, O = Net::O;
+    typedef double State;
+    const double* ks;                                  // the point's rate constants (LDS)
+    int r;
+    __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? blk[6 + r] : 0.0; }
+    __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
+    {
+        return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
+    }
+    __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
+    {
+        return group_step<Net, L>(ks, y, h, rtol, atol, r, yn, err2);
+    }
+    __device__ __forceinline__ bool all_finite(double yn, bool fin) const { return fin && !Lanes<L>::any(!finite(yn)); }
+    __device__ __forceinline__ bool any_negative(double yn, double y, double rtol, double atol) const
+    {
+        return Lanes<L>::any(yn < -(atol + rtol * dabs(y)));
+    }
+    __device__ __forceinline__ void observe(double y, double* o) const
+    {
+        double yr[S];
         Lanes<L>::template gather<S>(y, yr);
         Net::obs(yr, o);
-#pragma unroll
-        for (int q = 0; q < O; ++q) {
-            const double res = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
-            acc = acc - 0.5 * res * res;
-        }
     }
-    return ok ? blk[0] + acc : -__builtin_huge_val();
-}
+};
 #endif
 
 #if !defined(__HIP__)
 // ---------------------------------------------------------------- the host twin: the same operations, row by row
-template <class Net, int L>
+template <class NET, int L>
 struct HostGroup {
-    static constexpr int S = Net::S, O = Net::O, R = Net::R;
+    typedef NET Net;
+    static constexpr int S = Net::S, R = Net::R;
     static_assert(S <= L, "a lane per species");
 
     static double sum(double* a)               // a[L], overwritten: the butterfly's tree as lane 0 sees it
@@ -463,85 +424,9 @@ struct HostGroup {
         return sum(e) * (1.0 / S);
     }
 
-    static double start_step(const double* k, const double* y, double rtol, double atol, double span)
+    static void rhs(const double* k, const double* y, double* f)
     {
-        double f0[S], y1[S], f1[S];
-        for (int s = 0; s < S; ++s) f0[s] = Net::rhs_row(s, k, y);
-        const double d0 = wnorm2(y, y, rtol, atol), d1 = wnorm2(f0, y, rtol, atol);
-        const double h0 = start_h0(d0, d1, span);
-        for (int s = 0; s < S; ++s) y1[s] = y[s] + h0 * f0[s];
-        for (int s = 0; s < S; ++s) f1[s] = Net::rhs_row(s, k, y1) - f0[s];
-        return start_h(h0, d1, wnorm2(f1, y, rtol, atol), span);
-    }
-
-    static double integrate(const double* x, const double* blk, double* sim, int* nsteps_out)
-    {
-        const double rtol = blk[1], atol = blk[2], t0 = blk[4];
-        const int max_steps = (int)blk[3], T = (int)blk[5];
-        const double* tt = blk + 6 + S;
-        const double* dat = tt + T;
-        const double* sd = dat + (long long)T * O;
-        const double ninf = -__builtin_huge_val();
-        double k[R > 0 ? R : 1], y[S], yn[S], ye[S], o[O];
-        if (nsteps_out) *nsteps_out = 0;
-        if (!rates(x, k)) return ninf;
-        for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
-        double t = t0, acc = 0.0;
-        double h = start_step(k, y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300));
-        bool ok = finite(h) && h > 0.0, rejected = false;
-        int nsteps = 0;
-        for (int j = 0; ok && j < T; ++j) {
-            const double tout = tt[j];
-            for (int n = 0; t < tout; ++n) {
-                const bool clip = t + h >= tout;
-                const double hs = clip ? tout - t : h;
-                if (n >= max_steps || t + hs == t) { ok = false; break; }
-                double err2;
-                const bool nonsing = step(k, y, hs, rtol, atol, yn, ye, err2);
-                bool fin = nonsing && finite(err2);
-                for (int s = 0; s < S; ++s) fin = fin && finite(yn[s]);
-                if (!fin) { ok = false; break; }
-                ++nsteps;
-                double fac = step_factor(err2);
-                bool neg = false;
-                for (int s = 0; s < S; ++s) neg = neg || yn[s] < -(atol + rtol * dabs(y[s]));
-                if (neg) fac = dmin(fac, 0.25);
-                if (err2 <= 1.0 && !neg) {
-                    if (rejected) fac = dmin(fac, 1.0);
-                    for (int s = 0; s < S; ++s) y[s] = yn[s];
-                    t = clip ? tout : t + hs;
-                    h = clip ? dmax(h, hs * fac) : hs * fac;
-                    rejected = false;
-                } else {
-                    h = hs * fac;
-                    rejected = true;
-                }
-            }
-            if (!ok) break;
-            Net::obs(y, o);
-            for (int q = 0; q < O; ++q) {
-                const double res = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
-                acc = acc - 0.5 * res * res;
-                if (sim) sim[(long long)j * O + q] = o[q];
-            }
-        }
-        if (nsteps_out) *nsteps_out = nsteps;
-        return ok ? blk[0] + acc : ninf;
-    }
-
-    static bool integrate_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)
-    {
-        double k[R > 0 ? R : 1], yn[S], ye[S];
-        if (!rates(x, k)) return false;
-        for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
-        const double h = (t1 - blk[4]) / nsteps;
-        bool ok = true;
-        for (int n = 0; n < nsteps; ++n) {
-            double err2;
-            ok = step(k, y, h, blk[1], blk[2], yn, ye, err2) && ok;
-            for (int s = 0; s < S; ++s) y[s] = which ? ye[s] : yn[s];
-        }
-        return ok;
+        for (int s = 0; s < S; ++s) f[s] = Net::rhs_row(s, k, y);
     }
 };
 #endif
@@ -564,25 +449,11 @@ struct HostGroup {
         const bool valid = i < n;                                                                                                        \
         const bool good = dzode::group_rates<NET, LANES>(X + (valid ? i : n - 1) * ld, ks[g], r);                                        \
         __syncthreads();                                       /* (before any loop a group can leave early) */                           \
-        const double v = dzode::group_integrate<NET, LANES>(ks[g], (const double*)data, r, valid && good);                              \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r}, (const double*)data, valid && good, nullptr, nullptr);    \
         if (valid && r == 0) like[i] = v;                                                                                                \
     }
 #else
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
     typedef dzode::HostGroup<NET, LANES> DzodeHostGroup;                                                                                 \
-    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
-    {                                                                                                                                    \
-        for (long long i = 0; i < n; ++i) like[i] = DzodeHostGroup::integrate(X + i * ld, blk, nullptr, nsteps ? nsteps + i : nullptr); \
-    }                                                                                                                                    \
-    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* like)                 \
-    {                                                                                                                                    \
-        const long long per = (long long)(int)blk[5] * NET::O;                                                                           \
-        for (long long i = 0; i < n; ++i) like[i] = DzodeHostGroup::integrate(X + i * ld, blk, sim + i * per, nullptr);                 \
-    }                                                                                                                                    \
-    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
-    {                                                                                                                                    \
-        return DzodeHostGroup::integrate_fixed(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                   \
-    }                                                                                                                                    \
-    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
-    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+    DZODE_HOST_ENTRIES(DzodeHostGroup)
 #endif

@@ -396,6 +396,14 @@ def _obs_lines(S, observables):
     return L
 
 
+def _net_source(header, S, R, O, body, observables, entries):
+    """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
+    closing brace of the last one), the observables and the entry macro."""
+    L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O)] + body
+    L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(S, observables) + ["    }", "};", entries, ""]
+    return '#include "%s"\n' % header + "\n".join(L)
+
+
 _ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
 
 
@@ -417,9 +425,7 @@ def _ode_long_source(S, reactions, observables, log10):
         started.add(target)
         return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
 
-    L = ["struct Net {",
-         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
-         "    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     L += ["        k[%d] = %s;" % (i, ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p) for i, p in enumerate(used)]
     L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in used] + ["dzode::finite(k[%d])" % i for i in range(len(used))]) or "true"))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
@@ -443,22 +449,17 @@ def _ode_long_source(S, reactions, observables, log10):
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    L += ["    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
-    L += _obs_lines(S, observables)
-    L += ["    }", "};", "DZODE_ENTRIES(Net)", ""]
-    return '#include "dz_ode.h"\n' + "\n".join(L)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, "DZODE_ENTRIES(Net)")
 
 
 def _ode_source(S, reactions, observables, log10):
-    """The generated network struct (see csrc/dz_ode.h): rate constants, right-hand side, analytic Jacobian and observables as
+    """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
     straight-line code with constant indices; powers as repeated products."""
     R, O = len(reactions), len(observables)
     if R > _ODE_WHOLE_SUMS:
         return _ode_long_source(S, reactions, observables, log10)
     N = _stoichiometry(S, reactions)
-    L = ["struct Net {",
-         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
-         "    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     for r, (_, _, rate) in enumerate(reactions):
         if isinstance(rate, (int, np.integer)):
             L.append("        k[%d] = %s;" % (r, ("dzode::dexp(x[%d] * 2.302585092994046)" % rate) if log10 else "x[%d]" % rate))
@@ -479,10 +480,7 @@ def _ode_source(S, reactions, observables, log10):
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    L += ["    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
-    L += _obs_lines(S, observables)
-    L += ["    }", "};", "DZODE_ENTRIES(Net)", ""]
-    return '#include "dz_ode.h"\n' + "\n".join(L)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, "DZODE_ENTRIES(Net)")
 
 
 def _ode_group_source(S, reactions, observables, log10, lanes):
@@ -510,9 +508,7 @@ def _ode_group_source(S, reactions, observables, log10, lanes):
             out.append(indent + "v = v + %s * (%s);" % (coefficient(j), e))
         return out + [indent + "return v;"]
 
-    L = ["struct Net {",
-         "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O),
-         "    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
+    L = ["    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
          "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
     L += ["        case %d: return %d;" % (j, rate) for j, (_, _, rate) in enumerate(reactions) if isinstance(rate, (int, np.integer))]
     L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
@@ -525,10 +521,8 @@ def _ode_group_source(S, reactions, observables, log10, lanes):
         terms = [(j, _product(["k[z + %d]" % j] + (["%d.0" % reactions[j][0][q]] if reactions[j][0][q] > 1 else []) + _rate_factors(reactions[j][0], skip=q)))
                  for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
-    L += ["        default: return 0.0;", "        }", "    }", "    DZO_HD static void obs(const double* y, double* o)", "    {"]
-    L += _obs_lines(S, observables)
-    L += ["    }", "};", "DZODE_GROUP_ENTRIES(Net, %d)" % lanes, ""]
-    return '#include "dz_ode_group.h"\n' + "\n".join(L)
+    L += ["        default: return 0.0;", "        }", "    }"]
+    return _net_source("dz_ode_group.h", S, R, O, L, observables, "DZODE_GROUP_ENTRIES(Net, %d)" % lanes)
 
 
 class MassActionODELogLike:
@@ -561,9 +555,9 @@ class MassActionODELogLike:
     reactions with a parameter each; more distinct parameters than that spill 90..280 bytes per lane (same values, slower; see
     DESIGN.md).  lanes_per_point=16 or 32 integrates a point with a GROUP of that many lanes, one matrix row per lane
     (csrc/dz_ode_group.h: pivoted LU, triangular solves and the error norm over the group's lanes): n_species <= lanes_per_point, up to
-    128 reactions and 16 observables (ODE_GROUP_LIMITS).  Same method, same data block, same host-build contract (the host twin of the
-    group solver gives the device's bits); the two shapes round differently, so their values on a network both can run agree to the
-    integration tolerance, not to the bit."""
+    128 reactions and 16 observables (ODE_GROUP_LIMITS).  The same stepping loop (dzode::integrate in csrc/dz_ode.h, on another shape of
+    state), the same data block, the same host-build contract (the host twin of the group solver gives the device's bits); the two
+    shapes round differently, so their values on a network both can run agree to the integration tolerance, not to the bit."""
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1):
@@ -698,15 +692,17 @@ class MassActionODELogLike:
             raise ValueError("MassActionODELogLike: points have %d coordinates, the model reads %d" % (X.shape[1], self.d))
         return X
 
+    def _host_call(self, name, *args):
+        """The host build's function `name`: arrays go as pointers to their doubles (an int32 array: to its ints), the rest as it is."""
+        import ctypes as C
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int if a.dtype == np.int32 else C.c_double))      # noqa: E731
+        return getattr(self.host_library(), name)(*[ptr(a) if isinstance(a, np.ndarray) else a for a in args])
+
     def batch(self, X, return_steps=False):
         """Host-build log-likelihoods of the rows of X (and the accepted steps of each integration)."""
-        import ctypes as C
         X = self._rows(X)
-        blk = self.data_block()
         out, st = np.zeros(len(X)), np.zeros(len(X), dtype=np.int32)
-        P = C.POINTER(C.c_double)
-        self.host_library().dzode_loglike(X.ctypes.data_as(P), len(X), X.shape[1], blk.ctypes.data_as(P), out.ctypes.data_as(P),
-                                          st.ctypes.data_as(C.POINTER(C.c_int)))
+        self._host_call("dzode_loglike", X, len(X), X.shape[1], self.data_block(), out, st)
         return (out, st) if return_steps else out
 
     def __call__(self, x):
@@ -714,24 +710,17 @@ class MassActionODELogLike:
 
     def simulate(self, X):
         """The observables at the output times, [n, T, O] (NaN where the integration failed), from the host build."""
-        import ctypes as C
         X = self._rows(X)
-        blk = self.data_block()
-        T, O = len(self.t), len(self.observables)
-        sim, like = np.full((len(X), T, O), np.nan), np.zeros(len(X))
-        P = C.POINTER(C.c_double)
-        self.host_library().dzode_simulate(X.ctypes.data_as(P), len(X), X.shape[1], blk.ctypes.data_as(P), sim.ctypes.data_as(P), like.ctypes.data_as(P))
+        sim, like = np.full((len(X), len(self.t), len(self.observables)), np.nan), np.zeros(len(X))
+        self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), sim, like)
         sim[like == -np.inf] = np.nan
         return sim
 
     def fixed_steps(self, x, t1, nsteps, embedded=False):
         """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test)."""
-        import ctypes as C
         x = np.ascontiguousarray(np.asarray(x, dtype=float).reshape(-1))
-        blk = self.data_block()
         y = np.zeros(self.n_species)
-        P = C.POINTER(C.c_double)
-        ok = self.host_library().dzode_fixed(x.ctypes.data_as(P), blk.ctypes.data_as(P), float(t1), int(nsteps), int(bool(embedded)), y.ctypes.data_as(P))
+        ok = self._host_call("dzode_fixed", x, self.data_block(), float(t1), int(nsteps), int(bool(embedded)), y)
         return y if ok else np.full(self.n_species, np.nan)
 
     def __getstate__(self):                      # (the host library is a handle of this process: loaded again on first use)

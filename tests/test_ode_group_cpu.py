@@ -134,9 +134,13 @@ def _enzyme_kw(**over):
     return kw
 
 
-# sha256 of source() on the commit before the lanes_per_point keyword existed
+# sha256 of source() on the commit before the lanes_per_point keyword existed; the long one-lane form and the two group sources: on the
+# commit before the three generators shared their scaffolding
 PARENT_SOURCE_SHA256 = {"robertson": "c4fd92120c3b297f5ca95cc5badd01f82fb4e13702022f116b6aa3a583f6be0e",
-                        "chain8": "7c21c344e8c175a67e16fed278d7b683bdd838ae0231a090733fec458e45c951"}
+                        "chain8": "7c21c344e8c175a67e16fed278d7b683bdd838ae0231a090733fec458e45c951",
+                        "dense8x64@1": "13626834e185b0af64b9033f11ca543aaa69a2bb9f8d179186fda84ef67665f5",
+                        "enzyme13@16": "0aa13e4724688b1327784e38675d9c71e37520f6bfef3fb95eef62929af3b1f6",
+                        "chain32@32": "21746d67757913646ba884447bf66fb3a2f51064cd1323f94c2fcc26e9f3e804"}
 
 
 def test_construction_checks_defaults_unchanged_and_pickle():
@@ -161,6 +165,8 @@ def test_construction_checks_defaults_unchanged_and_pickle():
         like = make()
         assert like.lanes_per_point == 1 and "dz_ode_group" not in like.source()
         assert hashlib.sha256(like.source().encode()).hexdigest() == PARENT_SOURCE_SHA256[make.__name__]
+    for name, like in (("dense8x64@1", W.dense_network(8, 64, 1)), ("enzyme13@16", W.enzyme13()), ("chain32@32", W.chain(32, 32))):
+        assert hashlib.sha256(like.source().encode()).hexdigest() == PARENT_SOURCE_SHA256[name], name
     like = W.enzyme13()
     assert like.lanes_per_point == 16 and "DZODE_GROUP_ENTRIES(Net, 16)" in like.source()
     assert "DZODE_GROUP_ENTRIES(Net, 32)" in W.enzyme13(lanes=32).source()
@@ -184,3 +190,47 @@ def test_group_and_one_lane_builds_agree_to_the_tolerance_on_a_network_both_run(
     X = NW.box_points(W.CHAIN_NOMINAL, 50, 3, width=1.0)
     a, b = grp.simulate(X), one.simulate(X)
     assert np.max(np.abs(a - b)) < 1e-7
+
+
+# name -> (constructor(**kw), nominal, half width of the box, a max_steps that starves part of the box, whether fixed_steps goes in)
+HOST_CASES = {
+    "robertson": (NW.robertson, NW.ROB.NOMINAL, 3.0, 40, False),
+    "chain8": (NW.chain8, NW.CHAIN_NOMINAL, 1.0, 40, True),
+    "chain8@16": (lambda **kw: W.chain(8, 16, **kw), W.CHAIN_NOMINAL, 1.0, 40, True),
+    "enzyme13@16": (W.enzyme13, W.ENZ.NOMINAL, 1.0, 75, False),
+    "chain32@32": (lambda **kw: W.chain(32, 32, **kw), W.CHAIN_NOMINAL, 1.0, 40, False),
+}
+PARENT_HOST_SHA256 = {"robertson": "43c3380897edf22280ddfbd126007403115176acb4c01c336411825e6dbb9989",
+                      "chain8": "e980ecfea219174727f302d18ad2e759a79a2b6665b7e2e5ea41be1713594bc9",
+                      "chain8@16": "83a6094adeff4063d4b5999e54f29b6355a5a155b11e545e1a1d0426101f45c3",
+                      "enzyme13@16": "fc43c0735d58eee514f22772ac1011b7cb636912cd54dc082bf682cc5908c94e",
+                      "chain32@32": "00bf1a20cf3dc90bf581dd020cf15c916f0415bf99cc894e95be07343a0c265a"}
+
+
+def _six_decimals(like):
+    """The networks' data come from scipy's Radau, whose last bits may depend on the LAPACK build: pinned to six decimals, so that what
+    the digest sees is this project's arithmetic alone."""
+    like.data, like.sd = np.round(like.data, 6), np.round(like.sd, 6)
+    return like
+
+
+@pytest.mark.parametrize("name", list(HOST_CASES))
+def test_host_results_have_the_bits_of_the_commit_before_the_shared_stepping_loop(name):
+    """sha256 over batch (values and step counts) on 200 box points, simulate on the first 20, batch again under a step cap that starves
+    part of the box (the max_steps exit; -inf and the steps taken until then) and, for one network per shape, fixed_steps of both
+    orders.  PARENT_HOST_SHA256 was recorded by running exactly this code on the parent commit, where the one-lane loop, the lane
+    group's loop and the host twin's loop were three copies.  The host build uses + - * / and correctly rounded fma with contraction off,
+    so the digests do not depend on the compiler; the GPU tests require device bytes == host bytes, so this pins the device too."""
+    make, nominal, width, starved, fixed = HOST_CASES[name]
+    X = NW.box_points(nominal, 200, 17, width=width)
+    like = _six_decimals(make())
+    L, steps = like.batch(X, return_steps=True)
+    h = hashlib.sha256(L.tobytes() + steps.tobytes() + like.simulate(X[:20]).tobytes())
+    Ls, ss = _six_decimals(make(max_steps=starved)).batch(X, return_steps=True)
+    h.update(Ls.tobytes() + ss.tobytes())
+    if fixed:
+        for embedded in (False, True):
+            h.update(like.fixed_steps(X[0], 2.0, 10, embedded).tobytes())
+    print(name, "finite", int(np.isfinite(L).sum()), "finite when starved", int(np.isfinite(Ls).sum()), "steps", int(steps.sum()), h.hexdigest())
+    assert 0 < np.isfinite(Ls).sum() < len(X)
+    assert h.hexdigest() == PARENT_HOST_SHA256[name]
