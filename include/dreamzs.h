@@ -133,6 +133,15 @@ int dz_set_likelihood_host(dz_engine* e, dz_logp_cb cb, void* user);
 #define DZ_LIKE_ALWAYS_FINITE 1
 int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const char* kernel_name, int32_t lanes_per_point, int32_t flags,
                              const void* data, int64_t data_bytes);
+/* Several ITEMS per point for the kernel of dz_set_likelihood_module (a likelihood that is a sum of independent terms: one network measured
+ * under C experimental conditions, C data sets ...).  With items_per_point = C > 1 the engine launches the kernel over n * C items: its `n`
+ * is the ITEM count and its `like` an engine-owned array of n * C doubles; item w belongs to point w / C and is that point's term w % C, so
+ * the kernel reads row X + (w / C) * ld and writes like[w] (lanes_per_point then counts lanes per ITEM, same grid rules with items in the
+ * place of points).  A second kernel (k_sum_items, a thread per point) adds each point's C contiguous terms in ascending order with plain
+ * additions, ((l_0 + l_1) + l_2) + ..., into the point's log likelihood: a -inf term makes it -inf, nan becomes -inf as ever.  Valid after
+ * dz_set_likelihood_module, which resets it to 1; 1..DZ_MAX_LIKELIHOOD_ITEMS.  With C > 1 the generations run the multi-kernel path. */
+#define DZ_MAX_LIKELIHOOD_ITEMS 64
+int dz_set_likelihood_items(dz_engine* e, int32_t items_per_point);
 
 /* Multi-GPU: chains are sharded, Z / positions are replicated by an all-gather at the
  * end of appending generations (replaces the multiprocessing shared arrays,

@@ -134,6 +134,8 @@ struct dz_engine {
     dz_logp_cb cb = nullptr; void* cb_user = nullptr;
     // a user-supplied DEVICE likelihood (dz_set_likelihood_module): a kernel of a code object the user built, launched where k_logp_* run
     hipModule_t lk_module = nullptr; hipFunction_t lk_fn = nullptr; void* d_lk_data = nullptr; int lk_lanes = 1; bool lk_finite = false;
+    // dz_set_likelihood_items: the kernel writes lk_items values per point into d_items (a slice per chain-group stream, grown on demand), k_sum_items adds them
+    int lk_items = 1; double* d_items = nullptr; size_t items_len = 0;
     // ... and, when the code object has them, the persistent kernels with that density inlined (generations_wave_body<.., UserLike>): [0] lean, [1] full proposal code
     hipFunction_t lk_gen_fn[4] = {nullptr, nullptr, nullptr, nullptr};      // ([2], [3]: 128 < d <= 256)
     dz_exchange_cb xcb = nullptr; void* xcb_user = nullptr;
@@ -425,7 +427,31 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
         HIPCK(hipMemsetAsync(prior, 0, sizeof(double) * (size_t)n, st));
         const unsigned per_block = 256u / (unsigned)e->lk_lanes;      // 1, 16, 32 or 64 lanes per point, 256 threads per block
-        HIPCK(hipModuleLaunchKernel(e->lk_fn, ((unsigned)n + per_block - 1) / per_block, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+        if (e->lk_items == 1) {
+            HIPCK(hipModuleLaunchKernel(e->lk_fn, ((unsigned)n + per_block - 1) / per_block, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+        } else {
+            // several items per point (dz_set_likelihood_items): the kernel's n is the item count and its like the engine's scratch, item w
+            // of it belonging to point w / C; k_sum_items then leaves each point's sum where a one-item kernel would have written
+            const int C = e->lk_items;
+            const long long items = (long long)n * C, blocks = (items + per_block - 1) / per_block;
+            if (blocks > 0x7fffffffll) return fail("dz_set_likelihood_items: " + std::to_string(items) + " items are more than one launch's grid holds");
+            int sl = 0;
+            for (int s2 = 1; s2 < e->nlanes; ++s2) if (e->lane_stream[s2] == st) sl = s2;
+            if ((size_t)items * e->nlanes > e->items_len) {
+                DZCK(sync_all(e));
+                if (e->d_items) (void)hipFree(e->d_items);
+                e->d_items = nullptr; e->items_len = 0;
+                if (dalloc(&e->d_items, (size_t)items * e->nlanes)) {
+                    (void)hipGetLastError(); e->d_items = nullptr;
+                    return fail("dz_set_likelihood_items: cannot allocate the scratch for " + std::to_string(items) + " items x " + std::to_string(e->nlanes) + " streams: " + g_err);
+                }
+                e->items_len = (size_t)items * e->nlanes;
+            }
+            double* scratch = e->d_items + (size_t)sl * (e->items_len / e->nlanes);
+            a.n = items; a.like = scratch;
+            HIPCK(hipModuleLaunchKernel(e->lk_fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+            hipLaunchKernelGGL(dz::k_sum_items, dim3(((unsigned)n + 255) / 256), dim3(256), 0, st, (const double*)scratch, n, C, like);
+        }
         NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, grid, block, 0, st, e->p, pts, n, prior, like));
     } else if (e->lk == LK_HOST) {
         const int d = e->p.d;
@@ -966,7 +992,7 @@ bool mega_mix_eligible(const dz_engine* e)
 {
     const dz::Params& p = e->p;
     const bool pbm = p.hard || p.have_prior || p.depairs > 1;
-    return e->mega && (e->lk == LK_MIX || (e->lk == LK_MODULE && e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)])) && !redo_possible(e) &&
+    return e->mega && (e->lk == LK_MIX || (e->lk == LK_MODULE && e->lk_items == 1 && e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)])) && !redo_possible(e) &&
            p.ld <= 256 && (p.k == 1 || p.k >= 3) && p.k <= dz::MAXK &&
            p.nslots <= 64 && p.J <= 32;
 }
@@ -1542,6 +1568,7 @@ int dz_destroy(dz_engine* e)
     for (void* q : e->to_free) (void)hipFree(q);
     if (e->d_scratch) (void)hipFree(e->d_scratch);
     if (e->d_qpart) (void)hipFree(e->d_qpart);
+    if (e->d_items) (void)hipFree(e->d_items);
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     for (hipEvent_t x : e->pin_ev) if (x) (void)hipEventDestroy(x);
     if (e->h_redo) (void)hipHostFree(e->h_redo);
@@ -1743,6 +1770,17 @@ int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const c
     e->p.udata = d_new; e->p.J = 1;      // (J: the wave's scratch row in the persistent kernel's layout)
     e->lk_module = mod; e->lk_fn = fn; e->lk_lanes = lanes_per_point; e->lk_finite = (flags & DZ_LIKE_ALWAYS_FINITE) != 0;
     e->lk = LK_MODULE; e->have_logp = false;
+    e->lk_items = 1;
+    return 0;
+}
+
+int dz_set_likelihood_items(dz_engine* e, int32_t items_per_point)
+{
+    if (!e) return fail("null argument");
+    if (e->lk != LK_MODULE) return fail("dz_set_likelihood_items: call dz_set_likelihood_module first (the items are those of its kernel)");
+    if (items_per_point < 1 || items_per_point > DZ_MAX_LIKELIHOOD_ITEMS)
+        return fail("dz_set_likelihood_items: items_per_point must be 1.." DZ_USER_STR(DZ_MAX_LIKELIHOOD_ITEMS) " (got " + std::to_string(items_per_point) + ")");
+    e->lk_items = items_per_point; e->have_logp = false;
     return 0;
 }
 

@@ -1552,6 +1552,17 @@ __global__ void k_q_finish(Params p, const double* __restrict__ qpart, int npts,
     like_out[pt] = nan_to_ninf(p.logF - 0.5 * Q);
     if (!p.have_prior) prior_out[pt] = 0.0;
 }
+// a user likelihood with C items per point (dz_set_likelihood_items): like[i] = ((v[0] + v[1]) + v[2]) + ... over the point's C contiguous
+// items, ascending, plain additions -- the order a host loop over the items adds in.  A thread per point; C <= 64 doubles in a row.
+__global__ void k_sum_items(const double* __restrict__ items, int npts, int C, double* __restrict__ like)
+{
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= npts) return;
+    const double* v = items + (size_t)pt * C;
+    double s = v[0];
+    for (int c = 1; c < C; ++c) s = s + v[c];
+    like[pt] = s;
+}
 
 // prior only (wave per point), used beside the MFMA likelihood kernel when priors are not flat
 // log of the priors' scale parameters (scipy norm / uniform `scale`), evaluated once instead of per point and dimension

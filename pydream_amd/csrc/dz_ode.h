@@ -16,6 +16,10 @@
 //   [0] C = sum over the observed entries of (-log sd - log(2 pi) / 2)    [1] rtol   [2] atol   [3] max_steps   [4] t0   [5] T
 //   [6, 6+S) y0,   then t[T],   data[T*O] (time-major),   sd[T*O]   (an unobserved entry: data 0, sd +inf -- it adds exactly 0)
 //
+// With several experimental conditions (MassActionODELogLike(conditions=...)) the block is a two-double header [0] C  [1] stride followed
+// by C sub-blocks of stride doubles, each in the layout above (its own C_c, y0, data and sd; rtol .. T and t the same in all): the work
+// item w of the *_item_batch kernels is condition w % C of point w / C and integrates from sub-block w % C; see integrate_conditions.
+//
 // Every loop is bounded: at most max_steps attempted steps per output interval, T intervals.
 //
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
@@ -442,6 +446,29 @@ DZO_HD double integrate_point(const double* x, const double* blk, double* sim, i
     return integrate(Array<Alg>{k}, blk, true, sim, nsteps_out);
 }
 
+// The host build's point under C conditions (the data block with the [C, stride] header): the rate constants once, then condition by
+// condition in ascending order through the same integrate as a device item, the terms added as k_sum_items adds the items:
+// ((l_0 + l_1) + l_2) + ...  terms[C] (optional): the l_c; sim (optional): [C][T][O]; nsteps_out: the steps of all conditions.
+template <class Alg>
+DZO_HD double integrate_conditions(const double* x, const double* hdr, double* terms, double* sim, int* nsteps_out)
+{
+    const int C = (int)hdr[0];
+    const long long stride = (long long)hdr[1], per = (long long)(int)hdr[2 + 5] * Alg::Net::O;
+    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    const bool live = Alg::rates(x, k);
+    double total = 0.0;
+    int steps = 0;
+    for (int c = 0; c < C; ++c) {
+        int st = 0;
+        const double v = live ? integrate(Array<Alg>{k}, hdr + 2 + c * stride, true, sim ? sim + c * per : nullptr, &st) : -__builtin_huge_val();
+        if (terms) terms[c] = v;
+        total = c == 0 ? v : total + v;
+        steps += st;
+    }
+    if (nsteps_out) *nsteps_out = steps;
+    return total;
+}
+
 // Fixed steps (the order test only): nsteps steps of (t1 - t0) / nsteps from y0, propagating the order-4 solution (which = 0) or the
 // embedded order-3 one (which = 1).  The final state in y; false if a step failed.
 template <class Alg>
@@ -465,7 +492,17 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
 
 }  // namespace dzode
 
-// The host build's C functions around an algebra ALG (a plain type name), for the one-lane and the lane-group source alike.
+// The host build's C functions around an algebra ALG (a plain type name), for the one-lane and the lane-group source alike: those that do
+// not depend on the data block's form (dzode_fixed takes one experiment's block), ...
+#define DZODE_HOST_COMMON(ALG)                                                                                                          \
+    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
+    {                                                                                                                                    \
+        return dzode::integrate_fixed<ALG>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
+    }                                                                                                                                    \
+    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
+    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+
+// ... those of one experiment ...
 #define DZODE_HOST_ENTRIES(ALG)                                                                                                         \
     extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
     {                                                                                                                                    \
@@ -476,12 +513,22 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         const long long per = (long long)(int)blk[5] * ALG::Net::O;                                                                      \
         for (long long i = 0; i < n; ++i) like[i] = dzode::integrate_point<ALG>(X + i * ld, blk, sim + i * per, nullptr);               \
     }                                                                                                                                    \
-    extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
+    DZODE_HOST_COMMON(ALG)
+
+// ... and those of C conditions (blk: the block with the [C, stride] header): dzode_loglike gives the points' sums (nsteps: over the
+// conditions), dzode_simulate the terms [n][C] and, with sim, the observables [n][C][T][O].
+#define DZODE_HOST_ITEM_ENTRIES(ALG)                                                                                                    \
+    extern "C" void dzode_loglike(const double* X, long long n, int ld, const double* blk, double* like, int* nsteps)                  \
     {                                                                                                                                    \
-        return dzode::integrate_fixed<ALG>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
+        for (long long i = 0; i < n; ++i)                                                                                                \
+            like[i] = dzode::integrate_conditions<ALG>(X + i * ld, blk, nullptr, nullptr, nsteps ? nsteps + i : nullptr);               \
     }                                                                                                                                    \
-    extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
-    extern "C" double dzode_log(double x) { return dzode::dlog(x); }
+    extern "C" void dzode_simulate(const double* X, long long n, int ld, const double* blk, double* sim, double* terms)                \
+    {                                                                                                                                    \
+        const long long C = (long long)blk[0], per = C * (int)blk[2 + 5] * ALG::Net::O;                                                  \
+        for (long long i = 0; i < n; ++i) dzode::integrate_conditions<ALG>(X + i * ld, blk, terms + i * C, sim ? sim + i * per : nullptr, nullptr); \
+    }                                                                                                                                    \
+    DZODE_HOST_COMMON(ALG)
 
 // The entry points around a generated network struct NET: the batch kernel the engine's multi-kernel path launches (one thread per
 // point, 256 threads per block: dz_set_likelihood_module with lanes_per_point 1) and the host build's C functions.
@@ -494,8 +541,29 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         if (i >= n) return;                                                                                                              \
         like[i] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, (const double*)data, nullptr, nullptr);                       \
     }
+// ... with C conditions: the same launch over n = points x C ITEMS (dz_set_likelihood_items), one thread per item; item w is condition
+// w % C of point w / C -- the condition is the fastest index, so neighbouring lanes integrate the same rate constants from different
+// starts -- reads that point's row and writes like[w]; the engine adds a point's C items in ascending order.  The sub-block's address
+// differs by lane, so what the one-experiment kernel keeps in scalar registers (rtol, atol, T, the addresses of t, data and sd) is in
+// vector registers here; the address passes through DZODE_FENCE so that the compiler carries it as one pointer and not as a base and
+// offsets beside it (8 species, 15 reactions, 5 conditions: 12 bytes of scratch without the fence, none with it).
+#define DZODE_ITEM_ENTRIES(NET)                                                                                                         \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_item_batch(const double* X, long long n, int d, int ld, double* like,      \
+                                                                       const void* data)                                               \
+    {                                                                                                                                    \
+        const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
+        if (w >= n) return;                                                                                                              \
+        const double* hdr = (const double*)data;                                                                                         \
+        const long long C = (long long)hdr[0], stride = (long long)hdr[1], i = w / C;                                                    \
+        const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
+        DZODE_FENCE(blk);          /* (one opaque pointer per lane: see below) */                                                        \
+        like[w] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, nullptr, nullptr);                                       \
+    }
 #else
 #define DZODE_ENTRIES(NET)                                                                                                              \
     typedef dzode::OneLane<NET> DzodeOneLane;                                                                                            \
     DZODE_HOST_ENTRIES(DzodeOneLane)
+#define DZODE_ITEM_ENTRIES(NET)                                                                                                         \
+    typedef dzode::OneLane<NET> DzodeOneLane;                                                                                            \
+    DZODE_HOST_ITEM_ENTRIES(DzodeOneLane)
 #endif

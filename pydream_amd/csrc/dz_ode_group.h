@@ -33,7 +33,7 @@
 //                                                                                  N[r][j] a select over constants: no branch on r
 //     static double jac_entry(int r, int q, const double* k, const double* y);     J[r][q], same order (0 where no reaction links them)
 //     static void obs(const double* y, double* o);
-// Data block: dz_ode.h's.
+// Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks).
 #pragma once
 #include "dz_ode.h"
 
@@ -452,8 +452,30 @@ struct HostGroup {
         const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r}, (const double*)data, valid && good, nullptr, nullptr);    \
         if (valid && r == 0) like[i] = v;                                                                                                \
     }
+// ... with C conditions (dz_ode.h's block with the [C, stride] header): a group per ITEM, item w = condition w % C of point w / C; the
+// groups past the last item are predicated as above.
+#define DZODE_GROUP_ITEM_ENTRIES(NET, LANES)                                                                                            \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_group_item_batch(const double* X, long long n, int d, int ld, double* like, \
+                                                                             const void* data)                                         \
+    {                                                                                                                                    \
+        static_assert(NET::S <= LANES, "a lane per species");                                                                            \
+        __shared__ double ks[256 / LANES][NET::R + 1];                                                                                   \
+        const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
+        const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
+        const bool valid = w < n;                                                                                                        \
+        const double* hdr = (const double*)data;                                                                                         \
+        const long long C = (long long)hdr[0], stride = (long long)hdr[1], wv = valid ? w : n - 1, i = wv / C;                           \
+        const bool good = dzode::group_rates<NET, LANES>(X + i * ld, ks[g], r);                                                          \
+        __syncthreads();                                                                                                                 \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r}, hdr + 2 + (wv - i * C) * stride, valid && good, nullptr,  \
+                                          nullptr);                                                                                      \
+        if (valid && r == 0) like[w] = v;                                                                                                \
+    }
 #else
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
     typedef dzode::HostGroup<NET, LANES> DzodeHostGroup;                                                                                 \
     DZODE_HOST_ENTRIES(DzodeHostGroup)
+#define DZODE_GROUP_ITEM_ENTRIES(NET, LANES)                                                                                            \
+    typedef dzode::HostGroup<NET, LANES> DzodeHostGroup;                                                                                 \
+    DZODE_HOST_ITEM_ENTRIES(DzodeHostGroup)
 #endif

@@ -315,14 +315,23 @@ class DeviceKernelLogLike:
     grid, 256 / L points per block -- the groups of the last block whose point index is >= n run too, so the kernel predicates them
     instead of returning in front of a cross-lane operation.  always_finite=True promises the density is finite wherever the priors are (skips the
     per-generation "every try impossible?" check of Dream.py:281-289).  host: an optional Python twin f(x[d]) -> float used when the
-    object is called on the host (Model.total_logp); without it a call evaluates the point on the device."""
+    object is called on the host (Model.total_logp); without it a call evaluates the point on the device.
 
-    def __init__(self, name, ndim, source=None, path=None, data=None, lanes_per_point=1, always_finite=False, host=None, extra_flags=()):
+    items_per_point=C (1..64): a log-likelihood that is a sum of C independent terms (data sets, experimental conditions), one work ITEM
+    per term.  The kernel is launched over n * C items: its `n` is the item count, item w is term w % C of point w // C -- the term is
+    the fastest index -- so it reads the row X + (w / C) * ld and writes like[w]; lanes_per_point counts the lanes of an item.  The engine
+    then adds each point's C terms in ascending order with plain additions, ((l_0 + l_1) + l_2) + ... (a -inf term: the point is -inf)."""
+
+    items_per_point = 1     # (an object pickled before the keyword existed)
+
+    def __init__(self, name, ndim, source=None, path=None, data=None, lanes_per_point=1, always_finite=False, host=None, extra_flags=(),
+                 items_per_point=1):
         if (source is None) == (path is None):
             raise ValueError("give either the kernel's HIP source or the path of a gfx950 code object")
         self.name, self.d, self.source, self.path = name, int(ndim), source, path
         self.data = None if data is None else np.ascontiguousarray(data)
         self.lanes_per_point, self.always_finite, self.host, self.extra_flags = int(lanes_per_point), bool(always_finite), host, tuple(extra_flags)
+        self.items_per_point = int(items_per_point)
         self._eval_engine = None
 
     def code_object(self):
@@ -331,7 +340,8 @@ class DeviceKernelLogLike:
         return self.path
 
     def _dz_apply(self, engine):
-        engine.set_likelihood_module(self.code_object(), self.name, self.lanes_per_point, self.data, self.always_finite)
+        engine.set_likelihood_module(self.code_object(), self.name, self.lanes_per_point, self.data, self.always_finite,
+                                     items_per_point=self.items_per_point)
 
     def __call__(self, x):
         if self.host is not None:
@@ -349,7 +359,8 @@ class DeviceKernelLogLike:
 
 # ---------------------------------------------------------------------------------------------------- mass-action ODE models
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
-ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32))      # lanes_per_point=16 | 32: species <= lanes
+ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
+ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 _LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
 
 
@@ -407,7 +418,7 @@ def _net_source(header, S, R, O, body, observables, entries):
 _ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
 
 
-def _ode_long_source(S, reactions, observables, log10):
+def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)"):
     """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
     order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
     reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
@@ -449,15 +460,16 @@ def _ode_long_source(S, reactions, observables, log10):
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, "DZODE_ENTRIES(Net)")
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, entries)
 
 
-def _ode_source(S, reactions, observables, log10):
+def _ode_source(S, reactions, observables, log10, items=False):
     """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
-    straight-line code with constant indices; powers as repeated products."""
+    straight-line code with constant indices; powers as repeated products.  items: the entry points for several conditions per point."""
     R, O = len(reactions), len(observables)
+    entries = "DZODE_ITEM_ENTRIES(Net)" if items else "DZODE_ENTRIES(Net)"
     if R > _ODE_WHOLE_SUMS:
-        return _ode_long_source(S, reactions, observables, log10)
+        return _ode_long_source(S, reactions, observables, log10, entries)
     N = _stoichiometry(S, reactions)
     L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     for r, (_, _, rate) in enumerate(reactions):
@@ -480,10 +492,10 @@ def _ode_source(S, reactions, observables, log10):
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, "DZODE_ENTRIES(Net)")
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, entries)
 
 
-def _ode_group_source(S, reactions, observables, log10, lanes):
+def _ode_group_source(S, reactions, observables, log10, lanes, items=False):
     """The generated network struct for the lane-group solver (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
     its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
     stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
@@ -522,7 +534,7 @@ def _ode_group_source(S, reactions, observables, log10, lanes):
                  for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
     L += ["        default: return 0.0;", "        }", "    }"]
-    return _net_source("dz_ode_group.h", S, R, O, L, observables, "DZODE_GROUP_ENTRIES(Net, %d)" % lanes)
+    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes)
 
 
 class MassActionODELogLike:
@@ -557,10 +569,21 @@ class MassActionODELogLike:
     (csrc/dz_ode_group.h: pivoted LU, triangular solves and the error norm over the group's lanes): n_species <= lanes_per_point, up to
     128 reactions and 16 observables (ODE_GROUP_LIMITS).  The same stepping loop (dzode::integrate in csrc/dz_ode.h, on another shape of
     state), the same data block, the same host-build contract (the host twin of the group solver gives the device's bits); the two
-    shapes round differently, so their values on a network both can run agree to the integration tolerance, not to the bit."""
+    shapes round differently, so their values on a network both can run agree to the integration tolerance, not to the bit.
+
+    conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
+    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd"; a missing key is the constructor's own argument, which may be
+    None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
+    point is ((l_0 + l_1) + l_2) + ..., l_c exactly what this class gives for condition c alone (-inf if any integration fails).  On the
+    device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
+    dz_ode_group_item_batch, dz_set_likelihood_items), and the engine adds a point's items in that order; the host build loops the same
+    way and gives the same bits.  simulate then returns [n, C, T, O], batch(return_steps=True) the steps of all conditions, and
+    batch_conditions(X) the l_c, [n, C]."""
+
+    conditions = None       # (an object pickled before the keyword existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
-                 max_steps=500, ndim=None, path=None, lanes_per_point=1):
+                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None):
         S = int(n_species)
         lanes = int(lanes_per_point)
         if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"]:
@@ -598,9 +621,20 @@ class MassActionODELogLike:
         self.d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
         if idx and max(idx) >= self.d:
             raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), self.d))
-        y0 = np.asarray(y0, dtype=float).reshape(-1)
-        if y0.shape != (S,) or not np.all(np.isfinite(y0)) or np.any(y0 < 0):
-            raise ValueError("MassActionODELogLike: y0 must hold %d finite, non-negative amounts" % S)
+        if conditions is not None:
+            conditions = list(conditions)
+            if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
+                raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
+            for c, cond in enumerate(conditions):
+                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd"}:
+                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd" (each optional)' % c)
+                for key, top in (("y0", y0), ("data", data), ("sd", sd)):
+                    if cond.get(key) is None and top is None:
+                        raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
+        elif y0 is None or data is None or sd is None:
+            raise ValueError("MassActionODELogLike: y0, data and sd may be None only when every one of the conditions gives its own")
+        if y0 is not None:
+            y0 = self._checked_y0(y0, S, "")
         t = np.asarray(t, dtype=float).reshape(-1)
         if not 1 <= len(t) <= lim["times"]:
             raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (lim["times"], len(t)))
@@ -610,34 +644,76 @@ class MassActionODELogLike:
         if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= lim["observables"] or not np.all(np.isfinite(obs)):
             raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, lim["observables"]))
         O, T = len(obs), len(t)
-        data = np.asarray(data, dtype=float)
-        sd = np.broadcast_to(np.asarray(sd, dtype=float), data.shape) if data.shape == (O, T) else np.asarray(sd, dtype=float)
-        if data.shape != (O, T) or sd.shape != (O, T):
-            raise ValueError("MassActionODELogLike: data and sd must be O x T = %d x %d" % (O, T))
-        seen = np.isfinite(data)
-        if np.any(np.isinf(data)) or not np.all(np.isfinite(sd[seen]) & (sd[seen] > 0)):
-            raise ValueError("MassActionODELogLike: data must be finite or NaN (not observed), and sd finite and > 0 where data is observed")
+        if data is not None and sd is not None:
+            data, sd = self._checked_data(data, sd, O, T, "")
+        if conditions is not None:              # every condition as the single experiment: its own values, else the constructor's (checked above)
+            full = []
+            for c, cond in enumerate(conditions):
+                who = "condition %d: " % c
+                cy0 = y0 if cond.get("y0") is None else self._checked_y0(cond["y0"], S, who)
+                cdata, csd = (data if cond.get("data") is None else cond["data"]), (sd if cond.get("sd") is None else cond["sd"])
+                if cond.get("data") is not None or cond.get("sd") is not None or data is None or sd is None:
+                    cdata, csd = self._checked_data(cdata, csd, O, T, who)
+                full.append(dict(y0=cy0, data=cdata, sd=csd))
+            conditions = full
         if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
             raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
         self.n_species, self.reactions, self.observables, self.log10 = S, rx, obs, rate_scale == "log10"
         self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
-        self.data, self.sd = data, np.array(sd)
+        self.data, self.sd = data, sd
+        self.conditions = conditions            # None, or a list of dict(y0, data, sd): checked arrays, the fallbacks filled in
         self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
         self.path, self.lanes_per_point = path, lanes
         self._host = None
 
+    @staticmethod
+    def _checked_y0(y0, S, who):
+        y0 = np.asarray(y0, dtype=float).reshape(-1)
+        if y0.shape != (S,) or not np.all(np.isfinite(y0)) or np.any(y0 < 0):
+            raise ValueError("MassActionODELogLike: %sy0 must hold %d finite, non-negative amounts" % (who, S))
+        return y0
+
+    @staticmethod
+    def _checked_data(data, sd, O, T, who):
+        data, sd = np.asarray(data, dtype=float), np.asarray(sd, dtype=float)
+        try:
+            sd = np.broadcast_to(sd, data.shape) if data.shape == (O, T) else sd
+        except ValueError:                      # (an sd that does not broadcast to O x T: the shape test below says so)
+            pass
+        if data.shape != (O, T) or sd.shape != (O, T):
+            raise ValueError("MassActionODELogLike: %sdata and sd must be O x T = %d x %d" % (who, O, T))
+        seen = np.isfinite(data)
+        if np.any(np.isinf(data)) or not np.all(np.isfinite(sd[seen]) & (sd[seen] > 0)):
+            raise ValueError("MassActionODELogLike: %sdata must be finite or NaN (not observed), and sd finite and > 0 where data is observed" % who)
+        return data, np.array(sd)
+
     # ---- the data block (csrc/dz_ode.h) and the generated source
+    def _experiment_block(self, y0, data, sd):
+        seen = np.isfinite(data)
+        C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
+        dat = np.where(seen, data, 0.0).T.reshape(-1)               # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
+        sd = np.where(seen, sd, np.inf).T.reshape(-1)
+        return np.concatenate([[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], y0, self.t, dat, sd])
+
+    def condition_block(self, c=0):
+        """One experiment's block: condition c's, or (without conditions) the constructor's own."""
+        if self.conditions is None:
+            return self._experiment_block(self.y0, self.data, self.sd)
+        cond = self.conditions[c]
+        return self._experiment_block(cond["y0"], cond["data"], cond["sd"])
+
     def data_block(self):
-        seen = np.isfinite(self.data)
-        C = float(np.sum(-np.log(self.sd[seen]) - _LOG_2PI_HALF))
-        dat = np.where(seen, self.data, 0.0).T.reshape(-1)          # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
-        sd = np.where(seen, self.sd, np.inf).T.reshape(-1)
-        return np.concatenate([[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], self.y0, self.t, dat, sd])
+        """The block the kernels read (csrc/dz_ode.h): one experiment's, or with conditions [C, stride] and the C experiments' blocks."""
+        if self.conditions is None:
+            return self.condition_block()
+        blocks = [self.condition_block(c) for c in range(len(self.conditions))]
+        return np.concatenate([[float(len(blocks)), float(len(blocks[0]))]] + blocks)
 
     def source(self):
+        items = self.conditions is not None
         if self.lanes_per_point == 1:
-            return _ode_source(self.n_species, self.reactions, self.observables, self.log10)
-        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point)
+            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items)
+        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items)
 
     @staticmethod
     def _header_hash(name="dz_ode.h"):
@@ -654,15 +730,19 @@ class MassActionODELogLike:
         return text
 
     def code_object(self):
-        """The gfx950 code object (kernel dz_ode_batch, or dz_ode_group_batch for a lane group), compiled with hipcc on first use and
-        cached; the key includes csrc/dz_ode.h (and csrc/dz_ode_group.h)."""
+        """The gfx950 code object (kernel dz_ode_batch, or dz_ode_group_batch for a lane group; with conditions dz_ode_item_batch or
+        dz_ode_group_item_batch), compiled with hipcc on first use and cached; the key includes csrc/dz_ode.h (and csrc/dz_ode_group.h)."""
         if self.path is None:
             self.path = compile_device_kernel(self._unit(), extra_flags=("-I" + csrc_dir(),))
         return self.path
 
     def _dz_apply(self, engine):
-        kernel = "dz_ode_batch" if self.lanes_per_point == 1 else "dz_ode_group_batch"
-        engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False)
+        if self.conditions is None:
+            kernel = "dz_ode_batch" if self.lanes_per_point == 1 else "dz_ode_group_batch"
+            engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False)
+        else:
+            kernel = "dz_ode_item_batch" if self.lanes_per_point == 1 else "dz_ode_group_item_batch"
+            engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False, items_per_point=len(self.conditions))
 
     # ---- the host build
     def host_library(self):
@@ -699,7 +779,7 @@ class MassActionODELogLike:
         return getattr(self.host_library(), name)(*[ptr(a) if isinstance(a, np.ndarray) else a for a in args])
 
     def batch(self, X, return_steps=False):
-        """Host-build log-likelihoods of the rows of X (and the accepted steps of each integration)."""
+        """Host-build log-likelihoods of the rows of X (and the accepted steps of each integration; with conditions: of all of them)."""
         X = self._rows(X)
         out, st = np.zeros(len(X)), np.zeros(len(X), dtype=np.int32)
         self._host_call("dzode_loglike", X, len(X), X.shape[1], self.data_block(), out, st)
@@ -709,18 +789,31 @@ class MassActionODELogLike:
         return float(self.batch(np.asarray(x, dtype=float).reshape(1, -1))[0])
 
     def simulate(self, X):
-        """The observables at the output times, [n, T, O] (NaN where the integration failed), from the host build."""
+        """The observables at the output times, [n, T, O] -- with conditions [n, C, T, O] -- (NaN where the integration failed), from the
+        host build."""
         X = self._rows(X)
-        sim, like = np.full((len(X), len(self.t), len(self.observables)), np.nan), np.zeros(len(X))
+        lead = (len(X),) if self.conditions is None else (len(X), len(self.conditions))
+        sim, like = np.full(lead + (len(self.t), len(self.observables)), np.nan), np.zeros(lead)
         self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), sim, like)
         sim[like == -np.inf] = np.nan
         return sim
 
-    def fixed_steps(self, x, t1, nsteps, embedded=False):
-        """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test)."""
+    def batch_conditions(self, X):
+        """The per-condition log-likelihoods of the rows of X, [n, C], from the host build: column c is what an object made of condition c
+        alone returns, and batch(X) their sum from left to right."""
+        if self.conditions is None:
+            raise ValueError("MassActionODELogLike: batch_conditions needs an object made with conditions=[...]")
+        X = self._rows(X)
+        terms = np.zeros((len(X), len(self.conditions)))
+        self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), None, terms)
+        return terms
+
+    def fixed_steps(self, x, t1, nsteps, embedded=False, condition=0):
+        """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test).
+        condition: whose y0, for an object made with conditions."""
         x = np.ascontiguousarray(np.asarray(x, dtype=float).reshape(-1))
         y = np.zeros(self.n_species)
-        ok = self._host_call("dzode_fixed", x, self.data_block(), float(t1), int(nsteps), int(bool(embedded)), y)
+        ok = self._host_call("dzode_fixed", x, self.condition_block(condition), float(t1), int(nsteps), int(bool(embedded)), y)
         return y if ok else np.full(self.n_species, np.nan)
 
     def __getstate__(self):                      # (the host library is a handle of this process: loaded again on first use)

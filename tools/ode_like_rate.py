@@ -10,6 +10,12 @@
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|chain8|enzyme13|chain32] [--lanes 1|16|32]
+                                  [--conditions C]
+
+--conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
+geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
+over the points (what the class could do before it took conditions), alternately, the median of 7 rounds of 10 calls each and the
+rounds' spread; points/s, items/s, and lane efficiency over the waves of the combined launch (consecutive ITEMS).  Kernel only.
 
 chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
 scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
@@ -69,6 +75,59 @@ def network(name, lanes):
         rx, y0, obs = W.chain_network(S)
         return MassActionODELogLike(S, rx, y0, W.CHAIN_T, obs, grp.data, grp.sd), W.CHAIN_NOMINAL, 1.0
     return W.chain(S, lanes or 32), W.CHAIN_NOMINAL, 1.0
+
+
+def with_conditions(like, C):
+    """(the network of `like` under C conditions, the C single-condition objects).  Every condition keeps the network's data: the steps a
+    point takes depend on where it starts, not on what it is compared with."""
+    from pydream_amd.likelihoods import MassActionODELogLike
+    scales = [1.0] if C == 1 else [0.5 * 4.0 ** (c / (C - 1)) for c in range(C)]
+    shared = dict(rate_scale=like.rate_scale, t0=like.t0, rtol=like.rtol, atol=like.atol, max_steps=like.max_steps, lanes_per_point=like.lanes_per_point)
+    args = (like.n_species, like.reactions)
+    multi = MassActionODELogLike(*args, None, like.t, like.observables, like.data, like.sd, conditions=[dict(y0=s * like.y0) for s in scales], **shared)
+    return multi, [MassActionODELogLike(*args, s * like.y0, like.t, like.observables, like.data, like.sd, **shared) for s in scales]
+
+
+def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
+    from pydream_amd import _capi
+    like, nominal, width = network(name, lanes)
+    multi, singles = with_conditions(like, C)
+    n, d = N * k, len(nominal)
+    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
+
+    def engine(obj):
+        eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
+        eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
+        obj._dz_apply(eng)
+        return eng
+    one, many = engine(multi), [engine(s) for s in singles]
+    combined = lambda: one.eval_logp(X)[1]                              # noqa: E731
+    separate = lambda: [e.eval_logp(X)[1] for e in many]                # noqa: E731
+    for _ in range(3):
+        lk, parts = combined(), separate()
+    total = parts[0]
+    for p in parts[1:]:
+        total = total + p
+    assert lk.tobytes() == total.tobytes() == multi.batch(X).tobytes(), "the combined launch, the separate launches and the host build differ"
+    t = {"combined": [], "separate": []}
+    for _ in range(rounds):                                             # alternately: a drift of the machine hits both alike
+        for key, f in (("combined", combined), ("separate", separate)):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            t[key].append((time.perf_counter() - t0) / reps * 1e6)
+    steps = np.stack([s.batch(X, return_steps=True)[1] for s in singles], axis=1).reshape(-1)       # item order: the condition fastest
+    per_wave = 64 // like.lanes_per_point
+    w = steps[: len(steps) // per_wave * per_wave].reshape(-1, per_wave)
+    us, us_sep = float(np.median(t["combined"])), float(np.median(t["separate"]))
+    out = dict(network=name, lanes=like.lanes_per_point, conditions=C, chains=N, tries=k, points=n, items=n * C, us_per_launch=round(us, 1),
+               us_per_launch_min_max=[round(min(t["combined"]), 1), round(max(t["combined"]), 1)], points_per_s=round(n / us * 1e6),
+               items_per_s=round(n * C / us * 1e6), lane_efficiency=round(float(w.sum() / (per_wave * np.maximum(w.max(axis=1), 1)).sum()), 3),
+               steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)),
+               separate_launches_us=round(us_sep, 1), separate_launches_us_min_max=[round(min(t["separate"]), 1), round(max(t["separate"]), 1)],
+               separate_over_combined=round(us_sep / us, 3))
+    print(json.dumps(out), flush=True)
+    return out
 
 
 def gens_per_s(like, N, k, G, host_workers=None, nominal=ROB.NOMINAL, width=3.0):
@@ -132,10 +191,15 @@ def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--network", "--lanes"):
+    for flag in ("--network", "--lanes", "--conditions"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
+    if "--conditions" in opt:
+        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
+        conditions_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
+                        int(opt["--conditions"]))
+        sys.exit(0)
     main(*(int(a) for a in argv[:3] if not a.startswith("--")), kernel_only="--kernel-only" in argv, name=opt.get("--network", "robertson"),
          lanes=int(opt["--lanes"]) if "--lanes" in opt else None)
