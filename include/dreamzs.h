@@ -217,6 +217,10 @@ int64_t dz_redraw_rounds(dz_engine* e);
  * lean / full proposal code [, k1 = multitry off]), "k_generations_mix", or "multi-kernel path".  Lets a parity test assert that the
  * instantiation a benchmark times is the one it compared with the oracle.  The string lives until the next dz_step on the handle. */
 const char* dz_last_kernel_variant(dz_engine* e);
+/* The try count compiled into the instantiation the most recent generation(s) ran (5: multitry 5 outside the crossover burn-in, 16 chains
+ * per block), or 0: the instantiation that reads it at run time.  Both report the same dz_last_kernel_variant and compute the same bits;
+ * DZ_MEGA_KC=0 in the environment forces 0. */
+int dz_last_kernel_tries(dz_engine* e);
 
 int dz_get_state(dz_engine* e, double* X, double* prior, double* like);             /* [nl,d],[nl],[nl] */
 /* trace of generations [g0,g0+ng) since the last reset: sampled_params / log_ps of

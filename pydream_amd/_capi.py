@@ -37,14 +37,14 @@ SYMBOLS = [
     "dz_version", "dz_last_error", "dz_device_count", "dz_create", "dz_destroy", "dz_set_bounds", "dz_set_gamma_table",
     "dz_set_history", "dz_set_state", "dz_set_cr_probs", "dz_set_gamma_probs", "dz_set_prior", "dz_set_likelihood_mvn",
     "dz_set_likelihood_mixture", "dz_set_likelihood_host", "dz_set_likelihood_module", "dz_set_likelihood_items", "dz_hip_library", "dz_comm_library", "dz_comm_unique_id", "dz_comm_init_rccl", "dz_comm_count", "dz_comm_barrier", "dz_set_exchange", "dz_peer_export", "dz_peer_attach", "dz_peer_detach", "dz_exchange_stats", "dz_exchange_bytes", "dz_set_temperatures", "dz_get_swaps",
-    "dz_step", "dz_continue_run", "dz_step_range", "dz_set_chain_state", "dz_get_chain_state", "dz_get_chain_probs", "dz_sync", "dz_trace_reset", "dz_generation", "dz_redraw_rounds", "dz_last_kernel_variant", "dz_get_state", "dz_get_trace", "dz_get_trace_chains", "dz_trace_download_begin", "dz_trace_download_wait", "dz_host_register", "dz_host_unregister", "dz_get_history", "dz_get_history_range", "dz_history_checksum",
+    "dz_step", "dz_continue_run", "dz_step_range", "dz_set_chain_state", "dz_get_chain_state", "dz_get_chain_probs", "dz_sync", "dz_trace_reset", "dz_generation", "dz_redraw_rounds", "dz_last_kernel_variant", "dz_last_kernel_tries", "dz_get_state", "dz_get_trace", "dz_get_trace_chains", "dz_trace_download_begin", "dz_trace_download_wait", "dz_host_register", "dz_host_unregister", "dz_get_history", "dz_get_history_range", "dz_history_checksum",
     "dz_get_cr_state", "dz_get_gamma_state", "dz_get_rhat", "dz_get_chain_moments", "dz_eval_logp", "dz_debug_propose",
     "dz_profile_enable", "dz_profile_get", "dz_profile_reset", "dz_profile_get_list",
 ]
 
 # the environment switches the engine reads when it is made (dz_engine.hip read_switches): each forces or forbids a path, so every rank of a
 # sharded run must see the same values (distributed.attach_transport).  tests/test_capi_symbols.py checks this list against the engine's source.
-ENGINE_SWITCHES = ("DZ_MEGA", "DZ_MEGA_D2", "DZ_MEGA_SEGS", "DZ_MEGA_REDO", "DZ_MEGA_USER", "DZ_PROPOSE_SPLIT", "DZ_LOGP_GEMM", "DZ_QFIN",
+ENGINE_SWITCHES = ("DZ_MEGA", "DZ_MEGA_D2", "DZ_MEGA_SEGS", "DZ_MEGA_KC", "DZ_MEGA_REDO", "DZ_MEGA_USER", "DZ_PROPOSE_SPLIT", "DZ_LOGP_GEMM", "DZ_QFIN",
                    "DZ_STREAMS", "DZ_ADAPT_FUSED", "DZ_ADAPT_MULTI", "DZ_ADAPT_GROUPS")
 
 _lib = None
@@ -70,6 +70,8 @@ def load_library():
     L.dz_redraw_rounds.argtypes = [V]
     L.dz_last_kernel_variant.restype = C.c_char_p
     L.dz_last_kernel_variant.argtypes = [V]
+    L.dz_last_kernel_tries.restype = C.c_int
+    L.dz_last_kernel_tries.argtypes = [V]
     L.dz_create.argtypes = [C.POINTER(Config), C.POINTER(V)]
     L.dz_destroy.argtypes = [V]
     L.dz_set_bounds.argtypes = [V, V, V]
@@ -395,6 +397,10 @@ class Engine:
     def last_kernel_variant(self):
         """what the most recent generations ran as (template instantiation of the persistent kernel, or "multi-kernel path")"""
         return self.L.dz_last_kernel_variant(self.h).decode()
+
+    def last_kernel_tries(self):
+        """the try count compiled into that instantiation (5), or 0: the one that reads it at run time"""
+        return int(self.L.dz_last_kernel_tries(self.h))
 
     # ---- getters ----
     def get_state(self):

@@ -194,6 +194,7 @@ struct dz_engine {
     int mega_d2 = 1;                // 128 < d <= 256: k_generations_d2 from 1025 chains on (DZ_MEGA_D2=0: the multi-kernel path there; 2: at any chain count)
     bool mega_user = true;          // a user's device function inside the persistent kernel when its code object has it; DZ_MEGA_USER=0: the batch kernel only
     int mega_segs = 1 << 20;        // DZ_MEGA_SEGS: history appends per launch cap (1: a launch ends with its append, as without a lag)
+    bool mega_kc = true;            // multitry 5 outside the burn-in: the instantiation with the try count compiled in (MegaLaunch::kc); DZ_MEGA_KC=0: the generic one
     bool tempering = false; double* d_Tc = nullptr; int32_t* d_tswap = nullptr;    // parallel tempering (dz_set_temperatures)
     // Dream.py:281-289: a proposal set whose tries are all impossible is drawn again (redo_possible / one_generation)
     uint8_t* d_redo = nullptr; int32_t* d_redo_list = nullptr; uint8_t* h_redo = nullptr; int32_t* h_redo_list = nullptr;     // (host side: page-locked)
@@ -203,6 +204,7 @@ struct dz_engine {
     double *d_own_cr = nullptr, *d_own_g = nullptr; std::vector<char> own_init;      // per-instance probabilities of single-chain stepping (Params::own_cr)
     std::string broken;             // non-empty: a failed dz_continue_run left the engine without some of its buffers -- dz_step refuses
     std::string last_variant;       // what the last dz_step launched for its generations (dz_last_kernel_variant)
+    int last_kc = 0;                // ... and the try count compiled into it (MegaLaunch::kc; dz_last_kernel_tries)
     bool pending_accept = false;    // generation gen-1's Metropolis step has been deferred into the next proposal kernel
     const double* pending_qfin_r = nullptr;      // ... and with it the reference set's row-tile sums (Params::qfin_r), still in the scratch array
     int64_t pending_slot = -1;
@@ -914,7 +916,7 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
         NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot, publish ? 1 : 0));
         DZCK(launch_check("k_pt_swap"));
     }
-    e->last_variant = "multi-kernel path";
+    e->last_variant = "multi-kernel path"; e->last_kc = 0;
     for (int c = c0; c < c0 + nc; ++c) e->gen_c[c] = (int64_t)g + 1;
     if (full) e->gen = (int64_t)g + 1;
     if (slot >= 0) e->ntrace++;
@@ -1158,6 +1160,7 @@ int mega_segment(const dz_engine* e, uint32_t g, int64_t remaining)
 int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
 {
     dz::Params& p = e->p;
+    e->last_kc = 0;
     // the history appends of generations g .. g + n - 1 (one at the end, or -- mega_segment -- up to history_lag + 1, the last one at the end)
     int napps = 0, seg0 = 0;
     for (int i = 0; i < n; ++i) if ((g + (uint32_t)i) % (uint32_t)p.thin == 0) { if (!napps) seg0 = i + 1; ++napps; }
@@ -1349,6 +1352,9 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
         ml.tri = p.tri != 0; ml.xlds = pb ? true : xlds; ml.pb = pb; ml.k1 = k1; ml.ch = chp; ml.wpc = wpcp; ml.redo = mega_redo(e);
         ml.ahead = chp == 4 && wpcp == 4 && !pb && xlds && !k1 && p.k >= 3 && p.k <= 6;
         ml.multi = multi;
+        // five tries (the reference's multitry=True), nothing but the chains' own steps to leave behind, ONE launch of 16-chain blocks: the instantiation with
+        // the try count compiled in and no publishing / adaptation code (same arithmetic, same draws, same name: k_generations' KC and PLAIN parameters)
+        ml.kc = (e->mega_kc && p.k == 5 && !pb && !k1 && (xlds || !p.tri) && chp == 16 && wpcp == 1 && split_c == p.nl && !pp.to && pp.multi == 0 && !pp.PR && !pp.PC && !pp.TOT && !pp.CNT) ? 5 : 0;
         ml.grid = dim3((c1 - c0 + chp - 1) / chp); ml.block = dim3(64 * chp * wpcp); ml.lds = ldsp; ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
         ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = (uint32_t)visible_rows(e); ml.slot0 = slot0; ml.zappend = append_last ? e->M : (int64_t)-1; ml.seg0 = seg0; ml.publish = &pp;
         if (e->prof) { ml.ka = prof_event(e); ml.kb = prof_event(e); e->ev[PR_GENERATIONS].emplace_back(ml.ka, ml.kb); }
@@ -1362,6 +1368,7 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
         }
         char buf[96]; snprintf(buf, sizeof buf, name, chp, wpcp);
         variant += (variant.empty() ? "" : " + ") + std::string(buf);
+        e->last_kc = ml.kc;
         return 0;
     };
     DZCK(launch_part(0, split_c, ch));
@@ -1381,6 +1388,7 @@ void read_switches(dz_engine* e)
     if (const char* kv = getenv("DZ_MEGA")) e->mega = atoi(kv) != 0;
     if (const char* kv = getenv("DZ_MEGA_D2")) e->mega_d2 = atoi(kv);
     if (const char* kv = getenv("DZ_MEGA_SEGS")) e->mega_segs = std::max(1, atoi(kv));
+    if (const char* kv = getenv("DZ_MEGA_KC")) e->mega_kc = atoi(kv) != 0;
     if (const char* kv = getenv("DZ_MEGA_REDO")) e->mega_redo_on = atoi(kv) != 0;
     if (const char* kv = getenv("DZ_MEGA_USER")) e->mega_user = atoi(kv) != 0;
     if (const char* kv = getenv("DZ_PROPOSE_SPLIT")) e->propose_split = atoi(kv);
@@ -2168,6 +2176,7 @@ int64_t dz_redraw_rounds(dz_engine* e)
     return e->redraw_rounds + (int64_t)dev;
 }
 const char* dz_last_kernel_variant(dz_engine* e) { return e->last_variant.c_str(); }
+int dz_last_kernel_tries(dz_engine* e) { return e->last_kc; }
 
 int dz_get_state(dz_engine* e, double* X, double* prior, double* like)
 {

@@ -166,6 +166,27 @@ DZ_DEV int mt_select_vals(int k, double lp, double u_sel, int lane, bool* anyfin
     }
     return __builtin_amdgcn_readfirstlane(sel);
 }
+// ... with the try count a compile-time constant (k_generations' KC instantiations): the same sums in the same order, unrolled, every lane number an immediate
+template <int K>
+DZ_DEV int mt_select_vals(double lp, double u_sel, int lane, bool* anyfinite)
+{
+    static_assert(K >= 1 && K <= 16, "tries in lanes 0..15");
+    const double mx = readlane_f64(rowmax16(lp), 0);
+    *anyfinite = __any(lane < K && is_finite(lp)) != 0;
+    const double w = dexp(lp - mx);
+    double S = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) S = S + readlane_f64(w, i);
+    const double pr = w / S;
+    double cum = 0.0; int sel = K - 1; bool found = false;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        cum = cum + readlane_f64(pr, i);
+        const bool hit = !found && (u_sel < cum);
+        sel = hit ? i : sel; found = found || hit;
+    }
+    return __builtin_amdgcn_readfirstlane(sel);
+}
 DZ_DEV int mt_select(const Params& p, int c, double u_sel, int lane, bool* anyfinite)
 {
     const int k = p.k;
@@ -193,6 +214,22 @@ DZ_DEV double mt_log_ratio(int k, double val, double u_acc, int lane, double* lo
     *log_u = readlane_f64(lg, 1);
     return nan_to_num(readlane_f64(lg, 0));                                                          // :323
 }
+template <int K>      // (the try count a compile-time constant: cf. mt_select_vals<K>)
+DZ_DEV double mt_log_ratio(double val, double u_acc, int lane, double* log_u)
+{
+    static_assert(K >= 1 && K <= 16, "proposal terms in lanes 0..15, reference terms in lanes 16..31");
+    const double rm = rowmax16(val);
+    const double m2 = fmax(readlane_f64(rm, 0), readlane_f64(rm, 16));
+    const double ev = dexp(val - m2);
+    double SA = 0.0, SB = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) SA = SA + readlane_f64(ev, i);
+#pragma unroll
+    for (int i = 0; i < K; ++i) SB = SB + readlane_f64(ev, 16 + i);
+    const double lg = dlog(lane == 1 ? u_acc : SA / SB);
+    *log_u = readlane_f64(lg, 1);
+    return nan_to_num(readlane_f64(lg, 0));
+}
 template <bool BIG = false>
 DZ_DEV double mt_log_ratio(int k, double val) { double lu; return mt_log_ratio<BIG>(k, val, 0.5, 0, &lu); }
 
@@ -216,6 +253,18 @@ DZ_DEV u32x4 slot_counter_draw_key(const Params& p, int slot, uint32_t gc, uint3
     return philox(k0, k1, (uint32_t)idx, stream_id(K_PT, (uint32_t)tr, (uint32_t)phase), gc, g);
 }
 DZ_DEV u32x4 slot_counter_draw(const Params& p, int slot, uint32_t gc, uint32_t g) { return slot_counter_draw_key(p, slot, gc, g, p.k0, p.k1); }
+// ... with the try count a compile-time constant and ONE pair per DE try (npt = 2; the lean persistent kernel's KC instantiations): no loads of Params::k / npt, no
+// integer divisions.  nslots_c<K>: Params::nslots of such a configuration.
+template <int K> constexpr int nslots_c() { return 3 + (2 * K - 1) * 2; }
+template <int K> DZ_DEV int pt_slot(int phase, int tr, int idx) { return 3 + ((phase ? K + tr : tr) * 2 + idx); }
+template <int K>
+DZ_DEV u32x4 slot_counter_draw(const Params& p, int slot, uint32_t gc, uint32_t g)
+{
+    if (slot < 3) return philox(p.k0, p.k1, (uint32_t)slot, stream_id(K_CTRL, 0, 0), gc, g);
+    const int q = (slot - 3) >> 1, idx = (slot - 3) & 1;
+    const int phase = q >= K ? 1 : 0, tr = phase ? q - K : q;
+    return philox(p.k0, p.k1, (uint32_t)idx, stream_id(K_PT, (uint32_t)tr, (uint32_t)phase), gc, g);
+}
 // Where a wave gets its uniform draws from: lane s of the wave holds slot s of the chain's precomputed table
 // (ONE coalesced 16-byte load per lane at wave start, then v_readlane), or nothing (evaluate Philox in place).
 // xf: the point-stream slots have been turned, lane-parallel and once per generation, into what the tries read from them (persistent
@@ -373,7 +422,7 @@ DZ_DEV void reduce_rows(const ZRows<NCH>& zr, bool snk, RowTerms<NCH>& rt)
 // What a set of tries reads from Params, fetched ONCE per set by the persistent kernel (Params lives in memory there: every p.x inside
 // the try loop is a scalar load plus a wait, and scalar instructions cost nearly as much issue time as vector ones -- measured: 200 extra
 // s_add per generation = -3 %).  slot(i, idx) = slot0 + i npt + idx is pt_slot() of the set's phase.
-struct SetConsts { uint32_t thr; unsigned long long pgu_thr; double zeta, ec1, ec0; int npt, slot0; };
+struct SetConsts { uint32_t thr; unsigned long long pgu_thr; double zeta, ec1, ec0; int npt, slot0; uint32_t k0, k1, gc; int d; };      // (k0, k1, gc, d: set_consts<K> only -- the Philox key, the chain's counter word, Params::d)
 // Per-dimension constants of the priors (SampledParam: kind, loc, scale, log scale) and the hard boundaries, staged in LDS by the
 // persistent kernel's full-code instantiations ([ld] each): a try then costs LDS reads instead of eight dependent global loads.
 struct PBConsts { const double *a, *b, *logb, *lo, *hi; const int* kind; const double* inside; };      // (b: Params::pc2; inside: the log prior of a point inside every support, one LDS word)
@@ -385,23 +434,34 @@ DZ_DEV SetConsts set_consts(const Params& p, int phase, int cr_idx)
     return s;
 }
 
+template <int K>      // (the try count a compile-time constant, one pair per try: cf. pt_slot<K>)
+DZ_DEV SetConsts set_consts(const Params& p, int phase, int cr_idx, uint32_t gc)
+{
+    SetConsts s;
+    s.thr = p.crthr[__builtin_amdgcn_readfirstlane(cr_idx)]; s.pgu_thr = p.pgu_thr; s.zeta = p.zeta; s.ec1 = p.ec1; s.ec0 = p.ec0;
+    s.npt = 2; s.slot0 = 3 + (phase ? 2 * K : 0);
+    s.k0 = p.k0; s.k1 = p.k1; s.gc = gc; s.d = p.d;
+    return s;
+}
+
 // Returns, for a snooker try, the squared distance |proposal - z|^2 (wave-uniform): the caller turns the tries' distances into
 // snooker_logp = (d - 1) log sqrt(.) (:823-824 / :834-835) in ONE pass of the logarithm (snooker_logps below) instead of one per
 // try; 0 for a DE try (snooker_logp = 0).  grow: gamma_arr[level-1][delta-1][:] (any address space; the look-up address is
 // wave-uniform).
-template <int NCH, bool AL16 = true, int LEAN = 0>      // LEAN: 0 full, 1 lean (multi-try sets only), 2 lean with the single-try snooker formula
+// KC: the try count when it is a compile-time constant (one pair per try: pt_slot<KC>), 0: Params::k
+template <int NCH, bool AL16 = true, int LEAN = 0, int KC = 0>      // LEAN: 0 full, 1 lean (multi-try sets only), 2 lean with the single-try snooker formula
 DZ_DEV double propose_point(const Params& p, int phase, uint32_t g, uint32_t M, int c, int i, int n, int lane,
                           const double (&xb)[NCH][2], const double* __restrict__ grow, const RowTerms<NCH>& zr, double* __restrict__ out,
                           double* cur_snk_out, bool snk, int cr_idx, int delta, int glev, const DrawSrc& dr, const u32x4* wpre = nullptr,
                           const SetConsts* sc = nullptr, const PBConsts* pc = nullptr, double (*prv)[2] = nullptr)
 {   // wpre: the DIM draw of chunk 0, computed by the caller one try ahead (software pipelining, NCH == 1)
     // pc: bounds from LDS; prv: receives the lane's proposal values as stored (for the prior evaluation: no read-back of the row)
-    const int d = p.d, ld = p.ld;
-    const uint32_t gc = (uint32_t)(p.off + c);
+    const int d = (KC && sc) ? sc->d : p.d, ld = p.ld;
+    const uint32_t gc = (KC && sc) ? sc->gc : (uint32_t)(p.off + c);
     const uint32_t thr = sc ? sc->thr : p.crthr[__builtin_amdgcn_readfirstlane(cr_idx)];   // CR = CR_values[m], :146 (the decision is wave-uniform)
     const uint32_t s_dim = stream_id(K_DIM, (uint32_t)i, (uint32_t)phase),
                    s_bnd = stream_id(K_BND, (uint32_t)i, (uint32_t)phase);
-    const uint32_t K0 = dr.rekey ? dr.k0 : p.k0, K1 = dr.rekey ? dr.k1 : p.k1;      // (a redraw round's key)
+    const uint32_t K0 = (KC && sc) ? sc->k0 : (dr.rekey ? dr.k0 : p.k0), K1 = (KC && sc) ? sc->k1 : (dr.rekey ? dr.k1 : p.k1);      // (a redraw round's key; KC: no redraw rounds)
     double pr[NCH][2];
     double sqdist = 0.0;
     if (!snk) {
@@ -428,7 +488,7 @@ DZ_DEV double propose_point(const Params& p, int phase, uint32_t g, uint32_t M, 
                         + __popcll(__builtin_amdgcn_ballot_w64((w.x >> 16) < thr) & __builtin_amdgcn_ballot_w64(j0 + 1 < d));
             }
         }
-        const u32x4 wg = uniform_draw(p, dr, sc ? sc->slot0 + i * sc->npt : pt_slot(p, phase, i, 0), gc, g);  // set_gamma :615
+        const u32x4 wg = uniform_draw(p, dr, sc ? sc->slot0 + i * sc->npt : (KC ? pt_slot<KC ? KC : 1>(phase, i, 0) : pt_slot(p, phase, i, 0)), gc, g);  // set_gamma :615
         double gamma = 1.0;
         if (dr.xf ? (wg.x == 0u) : !u53_below(wg.x, wg.y, sc ? sc->pgu_thr : p.pgu_thr))      // u53(wg.x, wg.y) < p_gamma_unity
             gamma = grow[(dprime == 0 ? d : dprime) - 1];                      // gamma_arr[level-1][delta-1][d'-1], :624 (one address for the whole wave)
@@ -441,7 +501,7 @@ DZ_DEV double propose_point(const Params& p, int phase, uint32_t g, uint32_t M, 
                 pr[it][s] = keep[it][s] ? q : xb[it][s];
             }
     } else {
-        const u32x4 wg = uniform_draw(p, dr, pt_slot(p, phase, 0, 0), gc, g);
+        const u32x4 wg = uniform_draw(p, dr, KC ? pt_slot<KC ? KC : 1>(phase, 0, 0) : pt_slot(p, phase, 0, 0), gc, g);
         const double gamma_s = 1.2 + (2.2 - 1.2) * u53(wg.z, wg.w);            // :618
         double v[NCH][2], dzz[NCH][2], zz[NCH][2];
         double accD = 0.0, accS = 0.0;
@@ -734,7 +794,7 @@ DZ_DEV void point_prior(const Params& p, const double* row, int lane, double* pr
 
 // Tries i0..i1-1 of one chain's proposal set (phase 0: around the current state; phase 1: the reference set
 // around the selected proposal).  out / sl / prior_out address try 0's row and scalars.
-template <int NCH, bool AL16, bool GENERIC = true, int LEAN = 0>
+template <int NCH, bool AL16, bool GENERIC = true, int LEAN = 0, int KC = 0>
 DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int c, uint32_t gc, int i0, int i1, int n, int lane,
                         const double (&xb)[NCH][2], const double* __restrict__ grow, bool snk, int cr_idx, int delta, int glev, const DrawSrc& dsrc,
                         double* out, int out_stride, double* sl, double* csn, double* prior_out, const PBConsts* pc = nullptr)
@@ -743,7 +803,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
     auto point_and_prior = [&](int i, const RowTerms<NCH>& rt, bool snk_, int delta_) -> double {
         if (NCH == 1 && !LEAN && pc) {
             double pv[NCH][2];
-            const double sq = propose_point<NCH, AL16, LEAN>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, snk_, cr_idx, delta_, glev, dsrc, nullptr, nullptr, pc, pv);
+            const double sq = propose_point<NCH, AL16, LEAN, KC>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, snk_, cr_idx, delta_, glev, dsrc, nullptr, nullptr, pc, pv);
             if (prior_out) {
                 double pr = 0.0;
                 if (p.have_prior) { const double (&pv1)[1][2] = reinterpret_cast<const double (&)[1][2]>(pv); pr = prior_try_lds(p, *pc, pv1, lane); }
@@ -751,7 +811,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
             }
             return sq;
         }
-        const double sq = propose_point<NCH, AL16, LEAN>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, snk_, cr_idx, delta_, glev, dsrc);
+        const double sq = propose_point<NCH, AL16, LEAN, KC>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, snk_, cr_idx, delta_, glev, dsrc);
         if (prior_out) { if (LEAN) { if (lane == 0) prior_out[i] = 0.0; } else point_prior<NCH>(p, out + (size_t)i * out_stride, lane, prior_out + i); }
         return sq;
     };
@@ -764,7 +824,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
         // define the row registers makes the compiler wait for the loads at the merge.)
         double2 ra[NCH], rb[NCH];
         auto request = [&](int i) {
-            const u32x4 w = uniform_draw(p, dsrc, pt_slot(p, phase, i, 1), gc, g);
+            const u32x4 w = uniform_draw(p, dsrc, KC ? pt_slot<KC ? KC : 1>(phase, i, 1) : pt_slot(p, phase, i, 1), gc, g);
             const uint32_t r0 = __builtin_amdgcn_readfirstlane(mulhi_idx(w.x, M));
             uint32_t r1 = __builtin_amdgcn_readfirstlane(mulhi_idx(w.y, M - 1u));
             if (r1 >= r0) r1++;                                   // random.sample(range(M), 2) :662  (wave-uniform: kept on the scalar unit)
@@ -804,7 +864,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
             request(min(i + 1, i1 - 1));
             if (NCH == 1 && !LEAN && pc) {      // constants through PBConsts: the prior on the values in registers (no read-back of the row)
                 double pv[NCH][2];
-                propose_point<NCH, AL16, LEAN>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, false, cr_idx, 1, glev, dsrc,
+                propose_point<NCH, AL16, LEAN, KC>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, false, cr_idx, 1, glev, dsrc,
                                                AHEAD ? &wcur : nullptr, nullptr, pc, pv);
                 if (lane == 0) sl[i] = 0.0;
                 if (prior_out) {
@@ -814,7 +874,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
                 }
                 continue;
             }
-            propose_point<NCH, AL16, LEAN>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, false, cr_idx, 1, glev, dsrc,
+            propose_point<NCH, AL16, LEAN, KC>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, csn, false, cr_idx, 1, glev, dsrc,
                                            AHEAD ? &wcur : nullptr);
             if (lane == 0) sl[i] = 0.0;
             DZ_STAMP(p, phase, c, 3 + 2 * i);          // try i's arithmetic issued
@@ -826,7 +886,7 @@ DZ_DEV void propose_set(const Params& p, int phase, uint32_t g, uint32_t M, int 
         // snooker move: same pipeline with three rows per try (z and the projected pair, :808-810)
         double2 rz[NCH], r1[NCH], r2[NCH];
         auto request = [&](int i) {
-            const u32x4 w = uniform_draw(p, dsrc, pt_slot(p, phase, i, 1), gc, g);
+            const u32x4 w = uniform_draw(p, dsrc, KC ? pt_slot<KC ? KC : 1>(phase, i, 1) : pt_slot(p, phase, i, 1), gc, g);
             const uint32_t iz = dsrc.xf ? w.x : mulhi_idx(w.x, M), i1x = dsrc.xf ? w.y : mulhi_idx(w.y, M), i2x = dsrc.xf ? w.z : mulhi_idx(w.z, M);
 #pragma unroll
             for (int it = 0; it < NCH; ++it) {

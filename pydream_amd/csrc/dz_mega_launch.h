@@ -15,6 +15,8 @@ struct MegaLaunch {
     bool ahead = false;               // 4 chains x 4 waves, lean, multitry 3..6: k_generations_w4 (the tries' base-independent halves made ahead)
     bool sp = false;                  // k_generations_d2, 16 chains per block whose proposal set goes through the point tiles in two passes (229..256 dimensions at 5 tries)
     bool multi = false;               // adapt_lag >= 1: several burn-in generations per launch (16 chains per block, one wave each, states in LDS: the MG instantiations)
+    int kc = 0;                       // 5: multitry 5 and a launch that publishes nothing and adapts nothing (lean, 16 chains per block, one wave each, one launch per
+                                      // generation run): the instantiation with the try count compiled in (k_generations' KC, PLAIN); 0: the generic one
     // triangular factor / chain states in LDS / full proposal code (priors, bounds, DEpairs > 1) / multitry off
     int ch, wpc;                // chains per block (16, 8, 4), waves per chain (1; 4 at 4 chains per block with multitry on)
     dim3 grid, block; size_t lds; hipStream_t st;

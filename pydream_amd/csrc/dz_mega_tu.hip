@@ -95,6 +95,16 @@ static const char* launch_one(const MegaLaunch& a)
                        : (PB ? "k_generations<" DZ_STR(DZ_TU_NRT) ",dense,xlds,%d,%d,full,multi>" : "k_generations<" DZ_STR(DZ_TU_NRT) ",dense,xlds,%d,%d,lean,multi>");
         }
     }
+    // multitry 5, nothing published, nothing adapted (MegaLaunch::kc): the try count compiled in.  The same kernel by name -- what it computes is the generic
+    // instantiation's, bit for bit.  (The packed triangle leaves room for the states in LDS wherever 16 chains fit: no <tri, xhbm> copy.)
+    if constexpr (CH == 16 && WPC == 1 && !PB && !K1 && (X || !TRI)) {
+        if (a.kc == 5)
+            hipExtLaunchKernelGGL((k_generations<DZ_TU_NRT, TRI, X, CH, WPC, PB, K1, false, false, 5, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0,
+                                  a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
+        else
+            hipExtLaunchKernelGGL((k_generations<DZ_TU_NRT, TRI, X, CH, WPC, PB, K1>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0,
+                                  a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
+    } else
     hipExtLaunchKernelGGL((k_generations<DZ_TU_NRT, TRI, X, CH, WPC, PB, K1>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0,
                           a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
     // (NRT, matrix, chain states, chains per block, waves per chain, proposal code)

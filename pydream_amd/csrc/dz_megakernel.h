@@ -83,6 +83,7 @@ __host__ __device__ inline MegaLayout mega_layout(int d, int k, int nrt, int ncr
 
 // Unit u (0 .. ntl*NRT-1) in dealing order: row tile first (heaviest first for the triangular factor), then point tile.
 // Wave w of tw takes the units w, 2tw-1-w, 2tw+w, ... (snake), which evens out the k-steps per wave and per SIMD.
+__host__ __device__ constexpr int mega_rcp(int ntl) { return ((1 << 20) + ntl - 1) / ntl; }
 DZ_DEV int mega_unit(int j, int wv, int tw) { return (j & 1) ? tw * j + (tw - 1 - wv) : tw * j + wv; }
 
 // One accumulator's chain over the whole batches of a unit that starts at batch T0 (the packed triangle: row tile t joins at k = 16 t),
@@ -134,12 +135,12 @@ DZ_DEV void unit_dispatch(int t, const double* __restrict__ ap, const double* __
 // immediates.
 template <int NRT, bool TRI, bool MZ>
 DZ_DEV void mfma_units(const Params& p, const double* __restrict__ Ms, const double* __restrict__ Pt, const double* __restrict__ mus,
-                       double* __restrict__ qb, int row0, int ntl, int wv, int tw, int l, int LDM, int LDP)
-{
+                       double* __restrict__ qb, int row0, int ntl, int wv, int tw, int l, int LDM, int LDP, int rcp_ntl = 0)
+{   // rcp_ntl: mega_rcp(ntl) where the caller knows it at compile time (no integer division per likelihood pass)
     const int d = p.d, KS = (d + 3) >> 2, KB = KS >> 2;            // KB whole batches of four k-steps (one 16-row block of the matrix)
     const int pi = l & 15, kq = l >> 4;
     const int nun = ntl * NRT;
-    const int rcp = ((1 << 20) + ntl - 1) / ntl;                  // u / ntl == (u * rcp) >> 20 for every u < 2^10
+    const int rcp = rcp_ntl ? rcp_ntl : mega_rcp(ntl);            // u / ntl == (u * rcp) >> 20 for every u < 2^10
     for (int j = 0; tw * j < nun; ++j) {
         const int u = mega_unit(j, wv, tw);
         if (u >= nun) continue;
@@ -254,12 +255,14 @@ DZ_DEV void sample_pair(uint32_t wx, uint32_t wy, uint32_t M, uint32_t& r0, uint
 }
 // What the tries read from the generation's slot draws, made lane-parallel once per generation instead of on the scalar unit once per
 // try (DrawSrc::xf): lane s holds slot s.  snk: the chain's move of this generation (wave-uniform).
+template <int KC = 0>      // KC: the try count when it is a compile-time constant (then nslots and npt are, too)
 DZ_DEV void finish_draws(const Params& p, DrawSrc& q, bool snk, uint32_t M, int lane)
 {
     const int sl = lane - 3;
-    const bool pt = lane >= 3 && lane < p.nslots;
-    const bool rows = pt && (sl % p.npt) == 1;            // (DEpairs = 1: npt = 2 -- idx 0 the gamma draws, idx 1 the rows)
-    const bool gam = pt && (sl % p.npt) == 0;
+    const int nslots = KC ? nslots_c<KC ? KC : 1>() : p.nslots, npt = KC ? 2 : p.npt;
+    const bool pt = lane >= 3 && lane < nslots;
+    const bool rows = pt && (sl % npt) == 1;              // (DEpairs = 1: npt = 2 -- idx 0 the gamma draws, idx 1 the rows)
+    const bool gam = pt && (sl % npt) == 0;
     uint32_t r0, r1;
     sample_pair(q.mine.x, q.mine.y, M, r0, r1);
     const uint32_t s0 = mulhi_idx(q.mine.x, M), s1 = mulhi_idx(q.mine.y, M), s2 = mulhi_idx(q.mine.z, M);      // :808-810
@@ -288,12 +291,12 @@ DZ_DEV void request_pair(const Params& p, const DrawSrc& ds, int slot, uint32_t 
 }
 
 // DE tries i0..i1-1 of one chain's set (one pair, the common case); A and B already hold the rows of tries i0 and i0 + 1.
-template <int LEAN, bool XF>
+template <int LEAN, bool XF, int KC = 0>
 DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, int c, uint32_t gc, int i0, int i1, int n, int lane,
                           const double (&xb)[1][2], const double* __restrict__ grow, int cr_idx, int glev, const DrawSrc& ds,
                           double* out, int out_stride, double* sl, double* prior_out, RowPair& A, RowPair& B, RowPair& C, const PBConsts* pc = nullptr)
 {
-    const SetConsts sc = set_consts(p, phase, cr_idx);
+    const SetConsts sc = KC ? set_consts<KC ? KC : 1>(p, phase, cr_idx, gc) : set_consts(p, phase, cr_idx);
     // (the tries' prior butterflies batched three at a time through wave_bfly4 -- lane partial sums kept across a round -- made the
     //  full-code kernel spill twice as much, 88 -> 180 bytes per lane, and cost 18 %: not kept)
     auto body = [&](int i, const RowPair& R) {
@@ -308,7 +311,7 @@ DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, in
             }
             return;
         }
-        propose_point<1, false, LEAN>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, nullptr, false, cr_idx, 1, glev, ds, nullptr, &sc);
+        propose_point<1, false, LEAN, KC>(p, phase, g, M, c, i, n, lane, xb, grow, rt, out + (size_t)i * out_stride, nullptr, false, cr_idx, 1, glev, ds, nullptr, &sc);
         if (!LEAN && prior_out) point_prior<1>(p, out + (size_t)i * out_stride, lane, prior_out + i);
     };
     const int rs = sc.slot0 + 1;                          // pt_slot(phase, i, 1) = rs + i npt
@@ -354,10 +357,18 @@ DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, in
 // (Publish::multi) -- the prologue applies the pending updates in order and leaves the probabilities of each of the launch's generations in an
 // LDS table; every generation ends with the block's unit sums into that generation's ring slot (one more barrier per generation: the chains'
 // states before the generation come from the Metropolis step's registers, the states after it are the LDS rows).
-template <int NRT, bool TRI, bool XLDS, int CH, int WPC, bool PB, bool K1 = false, bool REDO = false, bool MG = false>
+// KC (0: the try count is Params::k, read at run time): the try count as a compile-time constant -- the LDS layout's rows and offsets, the slot numbers of the
+// draws, the selection's and the ratio's lane loops, the likelihood pass's tile counts all become immediates.  PLAIN: a launch that leaves nothing behind but
+// the chains' own steps -- no published positions, no ring, no fused or multi adaptation sums, no pending totals (every Publish field but c0 / c1 / sh is
+// ignored).  Generic, every one of these is a value in a scalar register, or a spilled one, that lives across the whole generation loop; the host picks
+// <.., 5, true> for multitry 5 outside the crossover burn-in (run_mega_segment, MegaLaunch::kc).  Same arithmetic, same order, same draws: the same bits.
+template <int NRT, bool TRI, bool XLDS, int CH, int WPC, bool PB, bool K1 = false, bool REDO = false, bool MG = false, int KC = 0, bool PLAIN = false>
 __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __restrict__ pp, uint32_t g0, int ngen, uint32_t M0, int64_t trace_slot0, int64_t zappend, int seg0, Publish pub)
 {
-    double* const publish = pub.to;
+    static_assert(!KC || (CH == 16 && WPC == 1 && !PB && !K1 && !REDO && !MG && KC >= 3 && KC <= 15), "compile-time try count: the lean 16-chain instantiations (one DE pair: npt = 2)");
+    static_assert(!PLAIN || !MG, "a plain launch makes no adaptation sums");
+    constexpr int KCC = KC ? KC : 1;      // (a valid template argument in the branches KC == 0 never takes)
+    double* const publish = PLAIN ? nullptr : pub.to;
     const Params& p = *pp;       // read through the scalar cache on demand: keeps the ~70 fields out of the SGPR file
     constexpr int NCH = 1;
     // WPC waves per chain (1 at 16 chains per block; 2 / 4 at 8 / 4 chains per block, i.e. when there are fewer than 16 chains
@@ -367,13 +378,13 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     constexpr int NT = 64 * CH * WPC;
     constexpr int LEANV = PB ? 0 : (K1 ? 2 : 1);
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int d = p.d, k = K1 ? 1 : p.k, ld = p.ld;
+    const int d = p.d, k = K1 ? 1 : (KC ? KC : p.k), ld = p.ld;
     const bool pbl = PB && p.pb_lds != 0;
     static_assert(!MG || (CH == 16 && WPC == 1 && !K1 && XLDS && !REDO), "several burn-in generations per launch: 16 chains per block, one wave each, states in LDS");
     // (any instantiation; Publish::multi == 2) several burn-in generations per launch WITHOUT the block's own unit sums: the positions of every generation go to
     // the ring of published positions and k_adapt_partials_ring makes the sums behind the launch; the prologue and the table as with MG
-    const bool RG = !MG && pub.multi == 2;
-    const bool fuse_adapt = !MG && !RG && CH == 16 && WPC == 1 && !K1 && XLDS && pub.PR != nullptr;
+    const bool RG = !PLAIN && !MG && pub.multi == 2;
+    const bool fuse_adapt = !PLAIN && !MG && !RG && CH == 16 && WPC == 1 && !K1 && XLDS && pub.PR != nullptr;
     const MegaLayout L = mega_layout(d, k, NRT, p.ncr, p.ngamma, TRI, XLDS, CH, pbl, MG || fuse_adapt, false, (MG || RG) ? pub.lag + 1 : 0);
     double* Ms = smem;
     double* Pt = smem + L.off_P;
@@ -431,7 +442,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     if (MG || RG) {     // adapt_lag >= 1: the pending updates, in order; the probabilities of each of the launch's generations into the table
         if (wv == 0) adapt_pending_apply(p, pub.DOT, pub.CNTR, pub.nbp, pub.lag + 1, pub.pend0, pub.pend1, (long long)g0, ngen, pub.lag, pub.burnin, pub.sh, smem + L.off_tab,
                                          blockIdx.x == 0 ? pub.sh_out : nullptr, lane);
-    } else if (pub.TOT) {      // the previous generation's adaptation totals are still to be applied: every block makes the update for itself (wave 0)
+    } else if (!PLAIN && pub.TOT) {      // the previous generation's adaptation totals are still to be applied: every block makes the update for itself (wave 0)
         if (wv == 0) adapt_apply_wave<1>(p, pub.TOT, pub.CNT, pub.sh, probs, blockIdx.x == 0 ? pub.sh_out : nullptr, lane);
     } else {
         if (threadIdx.x < p.ncr) probs[threadIdx.x] = pub.sh[threadIdx.x];
@@ -478,10 +489,11 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     constexpr bool XF = !PB && !K1 && WPC == 1;
     auto generation_draws = [&](uint32_t g_, uint32_t M) {
         DrawSrc q; q.have = true; q.mine = make_uint4(0, 0, 0, 0);
-        if (lane < p.nslots) { const u32x4 w = slot_counter_draw(p, lane, gc, g_); q.mine = make_uint4(w.x, w.y, w.z, w.w); }
+        if (KC) { if (lane < nslots_c<KCC>()) { const u32x4 w = slot_counter_draw<KCC>(p, lane, gc, g_); q.mine = make_uint4(w.x, w.y, w.z, w.w); } }
+        else if (lane < p.nslots) { const u32x4 w = slot_counter_draw(p, lane, gc, g_); q.mine = make_uint4(w.x, w.y, w.z, w.w); }
         if (XF && !multipair) {
             const uint32_t hx = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.mine.x), hy = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.mine.y);
-            finish_draws(p, q, u53_below(hx, hy, p.snk_thr), M, lane);               // (slot 0 = lane 0: set_snooker's draw)
+            finish_draws<KC>(p, q, u53_below(hx, hy, p.snk_thr), M, lane);           // (slot 0 = lane 0: set_snooker's draw)
         }
         return q;
     };
@@ -490,8 +502,8 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     auto prefetch_first = [&](const DrawSrc& q, int phase_, uint32_t g_, uint32_t M) {          // rows of this wave's first two tries of (g_, phase_)
         const int n_ = k - phase_;
         const int a0 = WPC == 1 ? 0 : (sub * n_) / WPC, a1 = WPC == 1 ? n_ : ((sub + 1) * n_) / WPC;
-        if (a0 < a1) request_pair<XF>(p, q, pt_slot(p, phase_, a0, 1), gc, g_, M, lane, RA, p.Z, 8u * (uint32_t)p.ld);
-        if (a0 + 1 < a1) request_pair<XF>(p, q, pt_slot(p, phase_, a0 + 1, 1), gc, g_, M, lane, RB, p.Z, 8u * (uint32_t)p.ld);
+        if (a0 < a1) request_pair<XF>(p, q, KC ? pt_slot<KCC>(phase_, a0, 1) : pt_slot(p, phase_, a0, 1), gc, g_, M, lane, RA, p.Z, 8u * (uint32_t)p.ld);
+        if (a0 + 1 < a1) request_pair<XF>(p, q, KC ? pt_slot<KCC>(phase_, a0 + 1, 1) : pt_slot(p, phase_, a0 + 1, 1), gc, g_, M, lane, RB, p.Z, 8u * (uint32_t)p.ld);
     };
     auto draws_say_snooker = [&](const DrawSrc& q, uint32_t g_) {                   // set_snooker :542-554 on the integer form of the draw
         const u32x4 w0 = uniform_draw(p, q, 0, gc, g_);
@@ -564,7 +576,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                 }
                 bool fin;
                 DZ_MSTAMP(11);
-                const int sel = mt_select_vals(k, lp, u_sel, lane, &fin);
+                const int sel = KC ? mt_select_vals<KCC>(lp, u_sel, lane, &fin) : mt_select_vals(k, lp, u_sel, lane, &fin);
                 DZ_MSTAMP(12);
                 if (lane == 0 && sub == 0) st[4 * cl + 2] = (double)(sel | (fin ? 256 : 0));
                 const double* row = region + (size_t)sel * tstride;
@@ -592,13 +604,13 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                         propose_set<NCH, false, true, 0>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, false, f.cr_idx, f.delta, f.glev, dcur,
                                                           region + (size_t)phase * tstride, tstride, slp, nullptr, prp, pbl ? &pcs : nullptr);
                 } else if (!snk_s) {
-                    propose_de_pf<LEANV, XF>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, f.cr_idx, f.glev, dcur,
+                    propose_de_pf<LEANV, XF, KC>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, f.cr_idx, f.glev, dcur,
                                        region + (size_t)phase * tstride, tstride, slp, prp, A_, B_, C_, pbl ? &pcs : nullptr);
                 } else if (a < b) {
                     // a snooker set is the longest path to the block's barrier (three rows and three reductions per try, one chain in
                     // ten): its wave gets issue priority over the three DE waves it shares a SIMD with
                     __builtin_amdgcn_s_setprio(3);
-                    propose_set<NCH, false, false, LEANV>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, true, f.cr_idx, 1, f.glev, dcur,
+                    propose_set<NCH, false, false, LEANV, KC>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, true, f.cr_idx, 1, f.glev, dcur,
                                                          region + (size_t)phase * tstride, tstride, slp, K1 ? st + 4 * cl + 3 : nullptr, prp, pbl ? &pcs : nullptr);   // (k = 1: log |x - z|^(d-1) of the current point, :328-329)
                     __builtin_amdgcn_s_setprio(0);
                 }
@@ -619,10 +631,11 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                 // mt_evaluate_logps :278, :302 (x - 0.0 == x bit for bit, so a zero mean skips the subtraction and its LDS read)
                 {
                     const int row0 = phase ? CH : 0, ntl = ((k - phase) * CH + 15) / 16;
+                    const int rcp = KC ? (phase ? mega_rcp(((KCC - 1) * CH + 15) / 16) : mega_rcp((KCC * CH + 15) / 16)) : 0;      // (0: mfma_units divides)
                     // (the pair-of-tiles units of k_generations_d2 in here, the matrix still in LDS: 714 against 725 M proposals/s at the headline size -- coarser
                     //  units balance worse over the 16 waves and the rolled batch loop costs address arithmetic; not kept)
-                    if (p.mu_zero) mfma_units<NRT, TRI, true>(p, Ms, Pt, mus, qb, row0, ntl, wv, CH * WPC, lane, L.LDM, L.LDP);
-                    else mfma_units<NRT, TRI, false>(p, Ms, Pt, mus, qb, row0, ntl, wv, CH * WPC, lane, L.LDM, L.LDP);
+                    if (p.mu_zero) mfma_units<NRT, TRI, true>(p, Ms, Pt, mus, qb, row0, ntl, wv, CH * WPC, lane, L.LDM, L.LDP, rcp);
+                    else mfma_units<NRT, TRI, false>(p, Ms, Pt, mus, qb, row0, ntl, wv, CH * WPC, lane, L.LDM, L.LDP, rcp);
                 }
                 DZ_MSTAMP(3 + 4 * phase);
                 __syncthreads();                                                     // q visible
@@ -695,7 +708,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                 else ratio = nan_to_num(q_logp) - nan_to_num(last_logp);                                 // :334
                 lu = dlog(u_acc);
             } else {
-                ratio = mt_log_ratio(k, val, u_acc, lane, &lu);                      // log(u) of :993 rides in the ratio's logarithm pass
+                ratio = KC ? mt_log_ratio<KCC>(val, u_acc, lane, &lu) : mt_log_ratio(k, val, u_acc, lane, &lu);      // log(u) of :993 rides in the ratio's logarithm pass
                 if (!fin) ratio = -__builtin_huge_val();                             // DESIGN.md deviation D1
             }
             const bool accept = is_finite(ratio) && (lu < ratio);                    // :993
