@@ -22,6 +22,23 @@
 //
 // Every loop is bounded: at most max_steps attempted steps per output interval, T intervals.
 //
+// MONOMIALS (likelihoods.Monomial): a rate constant, a start amount, an observable's scale factor or the argument of a Gaussian
+// constraint may be 10**(c + sum_i e_i x[i]), a product of powers of the sampled constants.  The arithmetic is the same on device and
+// host and does not depend on rate_scale:
+//     s = c;   for the indices i in ascending order  s = s + e_i * x[i]  (e_i = +1: s = s + x[i], e_i = -1: s = s - x[i]);
+//     value = dzode::dexp(s * 2.302585092994046)
+// so only + - * and dexp are used and both builds give the same bits.  A point is not live (-inf) if a coordinate that a monomial reads
+// is not finite or if a monomial's value is not finite (an underflow to 0 is allowed, as for 10**x).  A network that uses one carries
+//     static constexpr bool MONOMIALS = true;
+//     static bool live(const double* x);                               every monomial outside the rate constants is finite (those: rates)
+//     static double y0_row(int r, const double* x, double b);          species r's start amount: the block's b, or for b = NaN the monomial
+//                                                                      (a select over constants: no branch on r)
+//     static void scale(const double* x, double* o);                   o[q] = scale_q * o[q], at every output time
+//     static double constraints(const double* x);                      (only with constraints) g = G0 + acc, G0 = sum(-log sd_m - log(2 pi) / 2),
+//                                                                      acc = 0, then for m ascending acc = acc - 0.5 r r, r = (v_m - loc_m) / sd_m
+// and the entry points below pass the point's row x to the shape.  g is added to the value of a single experiment (l + g) and, with
+// conditions, to the term of condition 0 (l_0 + g); a network without these members compiles to what it compiled to before they existed.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -120,6 +137,40 @@ DZO_HD bool finite(double x) { return x - x == 0.0; }
 DZO_HD double dabs(double x) { return x < 0.0 ? -x : x; }
 DZO_HD double dmax(double a, double b) { return a > b ? a : b; }
 DZO_HD double dmin(double a, double b) { return a < b ? a : b; }
+
+// ---------------------------------------------------------------- monomials: what a network that has them adds (see the head of the file)
+template <class Net, class = void> struct has_monomials { static constexpr bool value = false; };
+template <class Net> struct has_monomials<Net, decltype((void)Net::MONOMIALS)> { static constexpr bool value = true; };
+template <class Net, class = void> struct has_constraints { static constexpr bool value = false; };
+template <class Net> struct has_constraints<Net, decltype((void)&Net::constraints)> { static constexpr bool value = true; };
+
+template <class Net>
+DZO_HD bool monomials_live(const double* x)
+{
+    if constexpr (has_monomials<Net>::value) return Net::live(x);
+    else return true;
+}
+
+template <class Net>
+DZO_HD double start_amount(int r, const double* x, double b)        // species r's y0: the data block's entry b, or the network's monomial
+{
+    if constexpr (has_monomials<Net>::value) return Net::y0_row(r, x, b);
+    else return b;
+}
+
+template <class Net>
+DZO_HD void observe_scaled(const double* x, const double* y, double* o)
+{
+    Net::obs(y, o);
+    if constexpr (has_monomials<Net>::value) Net::scale(x, o);
+}
+
+template <class Net>
+DZO_HD double add_constraints(double l, const double* x, bool first)    // l + g for a live point's single experiment or condition 0
+{
+    if constexpr (has_constraints<Net>::value) return first ? l + Net::constraints(x) : l;
+    else return l;
+}
 
 // ---------------------------------------------------------------- dense LU with partial pivoting, unrolled at compile-time S
 // a[S*S] row-major, factored in place; the diagonal holds the pivots' reciprocals.  Rows are exchanged with selects over every
@@ -379,7 +430,7 @@ template <class NET>
 struct OneLane {
     typedef NET Net;
     static constexpr int S = Net::S;
-    DZO_HD static bool rates(const double* x, double* k) { return Net::rates(x, k); }
+    DZO_HD static bool rates(const double* x, double* k) { return Net::rates(x, k) && monomials_live<Net>(x); }
     DZO_HD static void rhs(const double* k, const double* y, double* f) { Net::rhs(k, y, f); }
     DZO_HD static double wnorm2(const double* v, const double* y, double rtol, double atol) { return dzode::wnorm2<S>(v, y, rtol, atol); }
     DZO_HD static bool step(const double* k, const double* y, double h, double rtol, double atol, double* ynew, double* yemb, double& err2)
@@ -409,10 +460,11 @@ struct Array {
     static constexpr int S = Alg::Net::S, O = Alg::Net::O;
     struct State { double v[S]; };
     const double* k;                                   // the rate constants
+    const double* x;                                   // the point's row (read only by a network with monomials)
     DZO_HD void init(const double* blk, State& y) const
     {
 #pragma unroll
-        for (int s = 0; s < S; ++s) y.v[s] = blk[6 + s];
+        for (int s = 0; s < S; ++s) y.v[s] = start_amount<typename Alg::Net>(s, x, blk[6 + s]);
     }
     DZO_HD double start_step(const State& y, double rtol, double atol, double span) const { return dzode::start_step<Alg>(k, y.v, rtol, atol, span); }
     DZO_HD bool step(const State& y, double h, double rtol, double atol, State& yn, double& err2) const
@@ -433,22 +485,31 @@ struct Array {
         for (int s = 0; s < S; ++s) neg = neg || yn.v[s] < -(atol + rtol * dabs(y.v[s]));
         return neg;
     }
-    DZO_HD void observe(const State& y, double* o) const { Alg::Net::obs(y.v, o); }
+    DZO_HD void observe(const State& y, double* o) const { observe_scaled<typename Alg::Net>(x, y.v, o); }
 };
 
 // One point through an array shape.  The rate constants are tested here, ahead of the loop, and the loop runs with live a constant.
+// first: the single experiment, or condition 0 of several -- the term that a network's constraints are added to.
 template <class Alg>
-DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out)
+DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out, bool first = true)
 {
     double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
     if (nsteps_out) *nsteps_out = 0;
     if (!Alg::rates(x, k)) return -__builtin_huge_val();
-    return integrate(Array<Alg>{k}, blk, true, sim, nsteps_out);
+    return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
+}
+
+// The constraints' term g of one point alone (0 for a network without constraints, -inf for a point that is not live).
+template <class Alg>
+DZO_HD double constraint_term(const double* x)
+{
+    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    return Alg::rates(x, k) ? add_constraints<typename Alg::Net>(0.0, x, true) : -__builtin_huge_val();
 }
 
 // The host build's point under C conditions (the data block with the [C, stride] header): the rate constants once, then condition by
 // condition in ascending order through the same integrate as a device item, the terms added as k_sum_items adds the items:
-// ((l_0 + l_1) + l_2) + ...  terms[C] (optional): the l_c; sim (optional): [C][T][O]; nsteps_out: the steps of all conditions.
+// ((l_0 + l_1) + l_2) + ... (l_0 with the constraints' g, if the network has any).  terms[C] (optional): the l_c; sim (optional): [C][T][O]; nsteps_out: the steps of all conditions.
 template <class Alg>
 DZO_HD double integrate_conditions(const double* x, const double* hdr, double* terms, double* sim, int* nsteps_out)
 {
@@ -460,7 +521,8 @@ DZO_HD double integrate_conditions(const double* x, const double* hdr, double* t
     int steps = 0;
     for (int c = 0; c < C; ++c) {
         int st = 0;
-        const double v = live ? integrate(Array<Alg>{k}, hdr + 2 + c * stride, true, sim ? sim + c * per : nullptr, &st) : -__builtin_huge_val();
+        double v = live ? integrate(Array<Alg>{k, x}, hdr + 2 + c * stride, true, sim ? sim + c * per : nullptr, &st) : -__builtin_huge_val();
+        if (live) v = add_constraints<typename Alg::Net>(v, x, c == 0);
         if (terms) terms[c] = v;
         total = c == 0 ? v : total + v;
         steps += st;
@@ -478,7 +540,7 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     double k[Alg::Net::R > 0 ? Alg::Net::R : 1], yn[S], ye[S];
     if (!Alg::rates(x, k)) return false;
 #pragma unroll
-    for (int s = 0; s < S; ++s) y[s] = blk[6 + s];
+    for (int s = 0; s < S; ++s) y[s] = start_amount<typename Alg::Net>(s, x, blk[6 + s]);
     const double h = (t1 - blk[4]) / nsteps;
     bool ok = true;
     for (int n = 0; n < nsteps; ++n) {
@@ -498,6 +560,10 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     extern "C" int dzode_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)                         \
     {                                                                                                                                    \
         return dzode::integrate_fixed<ALG>(x, blk, t1, nsteps, which, y) ? 1 : 0;                                                       \
+    }                                                                                                                                    \
+    extern "C" void dzode_constraints(const double* X, long long n, int ld, double* g)                                                  \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) g[i] = dzode::constraint_term<ALG>(X + i * ld);                                                \
     }                                                                                                                                    \
     extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
     extern "C" double dzode_log(double x) { return dzode::dlog(x); }
@@ -557,7 +623,7 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], i = w / C;                                                    \
         const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
         DZODE_FENCE(blk);          /* (one opaque pointer per lane: see below) */                                                        \
-        like[w] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, nullptr, nullptr);                                       \
+        like[w] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, nullptr, nullptr, w == i * C);                           \
     }
 #else
 #define DZODE_ENTRIES(NET)                                                                                                              \

@@ -33,6 +33,8 @@
 //                                                                                  N[r][j] a select over constants: no branch on r
 //     static double jac_entry(int r, int q, const double* k, const double* y);     J[r][q], same order (0 where no reaction links them)
 //     static void obs(const double* y, double* o);
+// and, for a network with monomials (dz_ode.h's head: the construct, its arithmetic and the members live, y0_row, scale, constraints),
+//     static double rate_mono(int j, const double* x, bool& good);    the rate constant of a reaction whose rate_index is -2
 // Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks).
 #pragma once
 #include "dz_ode.h"
@@ -86,6 +88,9 @@ template <class Net>
 DZO_HD double rate_constant(int j, const double* x, bool& good)
 {
     const int pi = Net::rate_index(j);
+    if constexpr (has_monomials<Net>::value) {
+        if (pi == -2) return Net::rate_mono(j, x, good);
+    }
     if (pi < 0) {
         const double kv = Net::rate_fixed(j);
         good = finite(kv);
@@ -140,7 +145,7 @@ __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
         ks[j] = rate_constant<Net>(j, x, g);
         good = good && g;
     }
-    return !Lanes<L>::any(!good);
+    return !Lanes<L>::any(!(good && monomials_live<Net>(x)));
 }
 
 // piv: the row that pivoted in column k, four columns to an int
@@ -283,7 +288,8 @@ struct Group {
     typedef double State;
     const double* ks;                                  // the point's rate constants (LDS)
     int r;
-    __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? blk[6 + r] : 0.0; }
+    const double* x;                                   // the point's row (read only by a network with monomials)
+    __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? start_amount<Net>(r, x, blk[6 + r]) : 0.0; }
     __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
     {
         return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
@@ -301,7 +307,7 @@ struct Group {
     {
         double yr[S];
         Lanes<L>::template gather<S>(y, yr);
-        Net::obs(yr, o);
+        observe_scaled<Net>(x, yr, o);
     }
 };
 #endif
@@ -329,7 +335,7 @@ struct HostGroup {
             k[j] = rate_constant<Net>(j, x, g);
             good = good && g;
         }
-        return good;
+        return good && monomials_live<Net>(x);
     }
 
     static bool lu_factor(double* w, int* piv, int* pos)
@@ -447,10 +453,11 @@ struct HostGroup {
         const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
         const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
         const bool valid = i < n;                                                                                                        \
-        const bool good = dzode::group_rates<NET, LANES>(X + (valid ? i : n - 1) * ld, ks[g], r);                                        \
+        const double* x = X + (valid ? i : n - 1) * ld;                                                                                  \
+        const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
         __syncthreads();                                       /* (before any loop a group can leave early) */                           \
-        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r}, (const double*)data, valid && good, nullptr, nullptr);    \
-        if (valid && r == 0) like[i] = v;                                                                                                \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, (const double*)data, valid && good, nullptr, nullptr); \
+        if (valid && r == 0) like[i] = good ? dzode::add_constraints<NET>(v, x, true) : v;                                               \
     }
 // ... with C conditions (dz_ode.h's block with the [C, stride] header): a group per ITEM, item w = condition w % C of point w / C; the
 // groups past the last item are predicated as above.
@@ -465,11 +472,12 @@ struct HostGroup {
         const bool valid = w < n;                                                                                                        \
         const double* hdr = (const double*)data;                                                                                         \
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], wv = valid ? w : n - 1, i = wv / C;                           \
-        const bool good = dzode::group_rates<NET, LANES>(X + i * ld, ks[g], r);                                                          \
+        const double* x = X + i * ld;                                                                                                    \
+        const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
         __syncthreads();                                                                                                                 \
-        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r}, hdr + 2 + (wv - i * C) * stride, valid && good, nullptr,  \
-                                          nullptr);                                                                                      \
-        if (valid && r == 0) like[w] = v;                                                                                                \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, hdr + 2 + (wv - i * C) * stride, valid && good,        \
+                                          nullptr, nullptr);                                                                             \
+        if (valid && r == 0) like[w] = good ? dzode::add_constraints<NET>(v, x, wv == i * C) : v;                                        \
     }
 #else
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \

@@ -360,6 +360,7 @@ class DeviceKernelLogLike:
 # ---------------------------------------------------------------------------------------------------- mass-action ODE models
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
 ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
+ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 _LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
 
@@ -368,6 +369,104 @@ def _hexlit(v):
     """A C++17 hexadecimal floating literal: the double exactly."""
     v = float(v)
     return "(%s)" % v.hex() if np.isfinite(v) else ("(__builtin_huge_val())" if v > 0 else "(-__builtin_huge_val())")
+
+
+class Monomial:
+    """10**(log10_factor + sum_i exponents[i] * x[i]): a product of powers of the sampled constants 10**x[i] times a fixed factor, for
+    MassActionODELogLike -- a reaction's rate constant (kr = KD kf: Monomial({i: 1}, log10(kf)); a rate closed by a thermodynamic cycle,
+    k4 = k1 k2 / k3: Monomial({0: 1, 1: 1, 2: -1})), a sampled start amount, an observable's scale factor, or the argument of a Gaussian
+    constraint.  exponents: a non-empty mapping from parameter index to a finite, non-zero float; log10_factor: finite.  An immutable
+    value: `exponents` is the tuple of (index, exponent) pairs in ascending index, the order in which the device and the host build add
+    them (csrc/dz_ode.h)."""
+    __slots__ = ("exponents", "log10_factor")
+
+    def __init__(self, exponents, log10_factor=0.0):
+        if not hasattr(exponents, "items") or len(exponents) == 0:
+            raise ValueError("MassActionODELogLike: a Monomial's exponents must be a non-empty mapping {parameter index: exponent}")
+        pairs = []
+        for i, e in exponents.items():
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or i < 0:
+                raise ValueError("MassActionODELogLike: a Monomial's parameter index must be a non-negative integer (got %r)" % (i,))
+            if isinstance(e, bool) or not isinstance(e, (int, np.integer, float, np.floating)) or not np.isfinite(e) or e == 0:
+                raise ValueError("MassActionODELogLike: a Monomial's exponent must be a finite, non-zero number (got %r for index %d)" % (e, i))
+            pairs.append((int(i), float(e)))
+        if isinstance(log10_factor, bool) or not isinstance(log10_factor, (int, np.integer, float, np.floating)) or not np.isfinite(log10_factor):
+            raise ValueError("MassActionODELogLike: a Monomial's log10_factor must be finite (got %r)" % (log10_factor,))
+        object.__setattr__(self, "exponents", tuple(sorted(pairs)))
+        object.__setattr__(self, "log10_factor", float(log10_factor))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Monomial is immutable")
+
+    __delattr__ = __setattr__
+
+    @property
+    def indices(self):
+        return tuple(i for i, _ in self.exponents)
+
+    def value(self, x):
+        """10.0**(log10_factor + sum e_i x[i]) in numpy (the solvers' own arithmetic: csrc/dz_ode.h), for the rows of x"""
+        x = np.asarray(x, dtype=float)
+        s = self.log10_factor
+        for i, e in self.exponents:
+            s = s + e * x[..., i]
+        return 10.0 ** s
+
+    def __eq__(self, other):
+        return isinstance(other, Monomial) and self.exponents == other.exponents and self.log10_factor == other.log10_factor
+
+    def __hash__(self):
+        return hash((self.exponents, self.log10_factor))
+
+    def __reduce__(self):
+        return Monomial, (dict(self.exponents), self.log10_factor)
+
+    def __repr__(self):
+        return "Monomial(%r, %r)" % (dict(self.exponents), self.log10_factor)
+
+
+_INT = (int, np.integer)
+
+
+def _mono_value(m):
+    """The C++ expression of a monomial's value: the sum in ascending index, an exponent of +-1 as a plain add or subtract."""
+    out = _hexlit(m.log10_factor)
+    for i, e in m.exponents:
+        out += " + x[%d]" % i if e == 1.0 else " - x[%d]" % i if e == -1.0 else " + %s * x[%d]" % (_hexlit(e), i)
+    return "dzode::dexp((%s) * 2.302585092994046)" % out
+
+
+def _rate_indices(reactions):
+    """The parameter indices the rate constants read, bare or inside a monomial, ascending: those whose x is tested for finiteness."""
+    return sorted({r for _, _, r in reactions if isinstance(r, _INT)} | {i for _, _, r in reactions if isinstance(r, Monomial) for i in r.indices})
+
+
+def _monomial_members(mono):
+    """The members of a generated network that has monomials (csrc/dz_ode.h's head), for the one-lane and the lane-group source alike.
+    mono: dict(y0={species: Monomial}, scale=[float | Monomial] or None, constraints=[(Monomial, loc, sd)])."""
+    y0, scale, cons = mono["y0"], mono["scale"] or [], mono["constraints"]
+    outside = [m for _, m in sorted(y0.items())] + [f for f in scale if isinstance(f, Monomial)] + [m for m, _, _ in cons]
+    tests = ["dzode::finite(x[%d])" % i for i in sorted({i for m in outside for i in m.indices})] + ["dzode::finite(%s)" % _mono_value(m) for m in outside]
+    L = ["    static constexpr bool MONOMIALS = true;", "    DZO_HD static bool live(const double* x)", "    {",
+         "        return %s;" % (" && ".join(tests) or "true"), "    }",
+         "    DZO_HD static double y0_row(int r, const double* x, double b)", "    {"]
+    if y0:
+        L += ["        const double m%d = %s;" % (s, _mono_value(m)) for s, m in sorted(y0.items())]
+        sel = "0.0"
+        for s in sorted(y0, reverse=True):
+            sel = "r == %d ? m%d : %s" % (s, s, sel)
+        L += ["        const double m = %s;" % sel, "        return b != b ? m : b;"]
+    else:
+        L.append("        return b;")
+    L += ["    }", "    DZO_HD static void scale(const double* x, double* o)", "    {"]
+    L += ["        o[%d] = %s * o[%d];" % (q, _mono_value(f) if isinstance(f, Monomial) else _hexlit(f), q) for q, f in enumerate(scale) if f != 1.0]
+    L.append("    }")
+    if cons:
+        G0 = float(sum(-np.log(sd) - _LOG_2PI_HALF for _, _, sd in cons))
+        L += ["    DZO_HD static double constraints(const double* x)", "    {", "        double acc = 0.0;"]
+        L += ["        { const double r = (%s - %s) / %s; acc = acc - 0.5 * r * r; }" % (_mono_value(m), _hexlit(loc), _hexlit(sd)) for m, loc, sd in cons]
+        L += ["        return %s + acc;" % _hexlit(G0), "    }"]
+    return L
 
 
 def _stoichiometry(S, reactions):
@@ -418,7 +517,7 @@ def _net_source(header, S, R, O, body, observables, entries):
 _ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
 
 
-def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)"):
+def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None):
     """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
     order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
     reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
@@ -426,8 +525,11 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
     integration is the number of distinct parameters."""
     R, O = len(reactions), len(observables)
     N = _stoichiometry(S, reactions)
-    used = sorted({rate for _, _, rate in reactions if isinstance(rate, (int, np.integer))})
-    kname = ["k[%d]" % used.index(rate) if isinstance(rate, (int, np.integer)) else _hexlit(rate) for _, _, rate in reactions]
+    used = sorted({rate for _, _, rate in reactions if isinstance(rate, _INT)})
+    for _, _, rate in reactions:                # (then a slot per distinct monomial, in the order of their first reactions)
+        if isinstance(rate, Monomial) and rate not in used:
+            used.append(rate)
+    kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for _, _, rate in reactions]
 
     def add(target, started, c, e):
         t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
@@ -437,8 +539,9 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
         return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
 
     L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
-    L += ["        k[%d] = %s;" % (i, ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p) for i, p in enumerate(used)]
-    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in used] + ["dzode::finite(k[%d])" % i for i in range(len(used))]) or "true"))
+    L += ["        k[%d] = %s;" % (i, _mono_value(p) if isinstance(p, Monomial) else ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p)
+          for i, p in enumerate(used)]
+    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in _rate_indices(reactions)] + ["dzode::finite(k[%d])" % i for i in range(len(used))]) or "true"))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     started = set()
     for r, (reac, _, _) in enumerate(reactions):
@@ -460,24 +563,26 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, entries)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries)
 
 
-def _ode_source(S, reactions, observables, log10, items=False):
+def _ode_source(S, reactions, observables, log10, items=False, mono=None):
     """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
     straight-line code with constant indices; powers as repeated products.  items: the entry points for several conditions per point."""
     R, O = len(reactions), len(observables)
     entries = "DZODE_ITEM_ENTRIES(Net)" if items else "DZODE_ENTRIES(Net)"
     if R > _ODE_WHOLE_SUMS:
-        return _ode_long_source(S, reactions, observables, log10, entries)
+        return _ode_long_source(S, reactions, observables, log10, entries, mono)
     N = _stoichiometry(S, reactions)
     L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     for r, (_, _, rate) in enumerate(reactions):
-        if isinstance(rate, (int, np.integer)):
+        if isinstance(rate, _INT):
             L.append("        k[%d] = %s;" % (r, ("dzode::dexp(x[%d] * 2.302585092994046)" % rate) if log10 else "x[%d]" % rate))
+        elif isinstance(rate, Monomial):
+            L.append("        k[%d] = %s;" % (r, _mono_value(rate)))
         else:
             L.append("        k[%d] = %s;" % (r, _hexlit(rate)))
-    used = sorted({rate for _, _, rate in reactions if isinstance(rate, (int, np.integer))})      # (10**-inf is a finite 0: test x itself)
+    used = _rate_indices(reactions)             # (10**-inf is a finite 0: test x itself)
     L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)]))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     for r, (reac, _, _) in enumerate(reactions):
@@ -492,10 +597,10 @@ def _ode_source(S, reactions, observables, log10, items=False):
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"], observables, entries)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries)
 
 
-def _ode_group_source(S, reactions, observables, log10, lanes, items=False):
+def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None):
     """The generated network struct for the lane-group solver (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
     its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
     stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
@@ -522,18 +627,25 @@ def _ode_group_source(S, reactions, observables, log10, lanes, items=False):
 
     L = ["    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
          "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %d;" % (j, rate) for j, (_, _, rate) in enumerate(reactions) if isinstance(rate, (int, np.integer))]
+    L += ["        case %d: return %d;" % (j, -2 if isinstance(rate, Monomial) else rate) for j, (_, _, rate) in enumerate(reactions) if isinstance(rate, _INT + (Monomial,))]
     L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, (_, _, rate) in enumerate(reactions) if not isinstance(rate, (int, np.integer))]
-    L += ["        default: return 0.0;", "        }", "    }",
-          "    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
+    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, (_, _, rate) in enumerate(reactions) if not isinstance(rate, _INT + (Monomial,))]
+    L += ["        default: return 0.0;", "        }", "    }"]
+    if mono:                                             # (rate_index -2: the reaction's own expression, by lane j % L once per point)
+        L += ["    DZO_HD static double rate_mono(int j, const double* x, bool& good)", "    {", "        switch (j) {"]
+        for j, (_, _, rate) in enumerate(reactions):
+            if isinstance(rate, Monomial):
+                L.append("        case %d: { const double v = %s; good = %s; return v; }"
+                         % (j, _mono_value(rate), " && ".join(["dzode::finite(x[%d])" % i for i in rate.indices] + ["dzode::finite(v)"])))
+        L += ["        default: good = false; return 0.0;", "        }", "    }"]
+    L += ["    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
     L += weighted_sum([(j, _product(["k[z + %d]" % j] + _rate_factors(reactions[j][0]))) for j in range(R) if np.any(N[:, j] != 0)], "        ")
     L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
     for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
         terms = [(j, _product(["k[z + %d]" % j] + (["%d.0" % reactions[j][0][q]] if reactions[j][0][q] > 1 else []) + _rate_factors(reactions[j][0], skip=q)))
                  for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
-    L += ["        default: return 0.0;", "        }", "    }"]
+    L += ["        default: return 0.0;", "        }", "    }"] + (_monomial_members(mono) if mono else [])
     return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes)
 
 
@@ -551,7 +663,7 @@ class MassActionODELogLike:
             data=exp_data_ctot[None, :], sd=exp_data_sd_ctot[None, :], rate_scale="log10")
 
     A reaction is (reactants {species: coefficient}, products {species: coefficient}, rate), rate a parameter index (the rate constant is
-    10**x[index] for rate_scale "log10", x[index] for "linear") or a float (the rate constant itself).  Its rate is k prod y_s^nu_s (no
+    10**x[index] for rate_scale "log10", x[index] for "linear"), a float (the rate constant itself) or a Monomial (below).  Its rate is k prod y_s^nu_s (no
     combinatorial factor), dy/dt = N v with N = products - reactants.  The log-likelihood is sum norm(data, sd).logpdf(sim) over the
     finite data entries (NaN data: not observed), sim the observables at the output times t (data and sd are O x T).  rtol, atol: as
     odeint's defaults; max_steps: per output interval, as odeint's mxstep.  A failed integration (more than max_steps steps in an interval,
@@ -578,12 +690,28 @@ class MassActionODELogLike:
     device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
     dz_ode_group_item_batch, dz_set_likelihood_items), and the engine adds a point's items in that order; the host build loops the same
     way and gives the same bits.  simulate then returns [n, C, T, O], batch(return_steps=True) the steps of all conditions, and
-    batch_conditions(X) the l_c, [n, C]."""
+    batch_conditions(X) the l_c, [n, C].
+
+    Products of parameters: a Monomial(exponents, log10_factor) = 10**(log10_factor + sum_i exponents[i] x[i]) may stand
+      * as a reaction's rate (kr = KD kf with a fixed kf: Monomial({i: 1}, log10(kf)); a closed cycle: Monomial({0: 1, 1: 1, 2: -1}));
+      * as an entry of y0, the constructor's or a condition's: a sampled total amount.  A species has the same Monomial wherever a y0
+        gives it one; a condition may still give it a plain number (a knock-out at 0.0);
+      * in scale=[...], O numbers or Monomials shared by all conditions: the residual is (scale_q o[q] - data) / sd, and simulate returns
+        the scaled observables, what is compared with the data;
+      * in constraints=[(Monomial, loc, sd), ...] (at most 16, ODE_MAX_CONSTRAINTS): g(x) = sum norm(loc, sd).logpdf(monomial) is added
+        to the single experiment's value, l + g, and with conditions to the term of condition 0 (l_0 + g, what an object of condition 0
+        alone with the same constraints returns; the other conditions' terms are those of objects without constraints).
+        constraint_terms(X) returns g.
+    Its value is computed the same way on the device and the host (csrc/dz_ode.h: the sum in ascending index, then dzode::dexp) and
+    does not depend on rate_scale; Monomial({i: 1}) as a rate gives the bits of the bare index i under "log10".  A point at which a
+    coordinate read by a monomial, or a monomial's value, is not finite is -inf.  ndim is inferred over every index read, bare or
+    inside a monomial.  A model that uses none of this generates the source, and runs the kernels, it always did."""
 
     conditions = None       # (an object pickled before the keyword existed)
+    scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
-                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None):
+                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None):
         S = int(n_species)
         lanes = int(lanes_per_point)
         if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"]:
@@ -606,9 +734,11 @@ class MassActionODELogLike:
                         raise ValueError("MassActionODELogLike: reaction %d names species %r (0..%d)" % (r, s, S - 1))
                     if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
                         raise ValueError("MassActionODELogLike: reaction %d: stoichiometric coefficients must be non-negative integers (got %r)" % (r, c))
-            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating)):
-                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int) or a fixed rate constant (float)" % r)
-            if isinstance(rate, (int, np.integer)):
+            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating, Monomial)):
+                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int), a fixed rate constant (float) or a Monomial" % r)
+            if isinstance(rate, Monomial):
+                pass
+            elif isinstance(rate, (int, np.integer)):
                 if rate < 0:
                     raise ValueError("MassActionODELogLike: reaction %d: parameter index %d is negative" % (r, rate))
                 rate = int(rate)
@@ -617,10 +747,7 @@ class MassActionODELogLike:
             else:
                 rate = float(rate)
             rx.append(({int(s): int(c) for s, c in dict(reac).items() if c}, {int(s): int(c) for s, c in dict(prod).items() if c}, rate))
-        idx = [r[2] for r in rx if isinstance(r[2], int)]
-        self.d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
-        if idx and max(idx) >= self.d:
-            raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), self.d))
+        idx = [r[2] for r in rx if isinstance(r[2], int)] + [i for r in rx if isinstance(r[2], Monomial) for i in r[2].indices]
         if conditions is not None:
             conditions = list(conditions)
             if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
@@ -633,8 +760,9 @@ class MassActionODELogLike:
                         raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
         elif y0 is None or data is None or sd is None:
             raise ValueError("MassActionODELogLike: y0, data and sd may be None only when every one of the conditions gives its own")
+        y0m = {}                                 # species -> the Monomial its start amount is, wherever a y0 says so (the same in all)
         if y0 is not None:
-            y0 = self._checked_y0(y0, S, "")
+            y0 = self._checked_y0(y0, S, "", y0m)
         t = np.asarray(t, dtype=float).reshape(-1)
         if not 1 <= len(t) <= lim["times"]:
             raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (lim["times"], len(t)))
@@ -650,7 +778,7 @@ class MassActionODELogLike:
             full = []
             for c, cond in enumerate(conditions):
                 who = "condition %d: " % c
-                cy0 = y0 if cond.get("y0") is None else self._checked_y0(cond["y0"], S, who)
+                cy0 = y0 if cond.get("y0") is None else self._checked_y0(cond["y0"], S, who, y0m)
                 cdata, csd = (data if cond.get("data") is None else cond["data"]), (sd if cond.get("sd") is None else cond["sd"])
                 if cond.get("data") is not None or cond.get("sd") is not None or data is None or sd is None:
                     cdata, csd = self._checked_data(cdata, csd, O, T, who)
@@ -658,6 +786,30 @@ class MassActionODELogLike:
             conditions = full
         if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
             raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
+        if scale is not None:
+            scale = list(scale) if hasattr(scale, "__len__") or hasattr(scale, "__iter__") else [scale]
+            if len(scale) != O or not all(isinstance(f, Monomial) or (not isinstance(f, bool) and isinstance(f, (int, np.integer, float, np.floating)) and np.isfinite(f))
+                                          for f in scale):
+                raise ValueError("MassActionODELogLike: scale must hold O = %d finite numbers or Monomials" % O)
+            scale = [f if isinstance(f, Monomial) else float(f) for f in scale]
+        cons = []
+        for m, entry in enumerate(() if constraints is None else constraints):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 3 or not isinstance(entry[0], Monomial):
+                raise ValueError("MassActionODELogLike: constraint %d must be (Monomial, loc, sd)" % m)
+            try:
+                loc, csd = float(entry[1]), float(entry[2])
+            except (TypeError, ValueError):
+                loc = csd = np.nan
+            if not (np.isfinite(loc) and np.isfinite(csd) and csd > 0):
+                raise ValueError("MassActionODELogLike: constraint %d: loc must be finite and sd finite and > 0" % m)
+            cons.append((entry[0], loc, csd))
+        if len(cons) > ODE_MAX_CONSTRAINTS:
+            raise ValueError("MassActionODELogLike: at most %d constraints are supported (got %d)" % (ODE_MAX_CONSTRAINTS, len(cons)))
+        idx += [i for m in list(y0m.values()) + [f for f in scale or [] if isinstance(f, Monomial)] + [c[0] for c in cons] for i in m.indices]
+        self.d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
+        if idx and max(idx) >= self.d:
+            raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), self.d))
+        self.scale, self.constraints, self.y0_monomials = scale, tuple(cons), y0m
         self.n_species, self.reactions, self.observables, self.log10 = S, rx, obs, rate_scale == "log10"
         self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
         self.data, self.sd = data, sd
@@ -667,10 +819,24 @@ class MassActionODELogLike:
         self._host = None
 
     @staticmethod
-    def _checked_y0(y0, S, who):
-        y0 = np.asarray(y0, dtype=float).reshape(-1)
+    def _checked_y0(y0, S, who, monomials):
+        """The start amounts as S doubles, NaN where the entry is a Monomial (csrc/dz_ode.h: "take the network's monomial"); monomials:
+        species -> Monomial, filled in here -- a species has the same one wherever a y0 gives it one."""
+        entries = list(y0) if isinstance(y0, (list, tuple)) or (isinstance(y0, np.ndarray) and y0.dtype == object) else None
+        given = {s: m for s, m in enumerate(entries or ()) if isinstance(m, Monomial)}
+        if given:
+            y0 = [0.0 if s in given else v for s, v in enumerate(entries)]
+        try:
+            y0 = np.array(y0, dtype=float).reshape(-1)
+        except (TypeError, ValueError):
+            y0 = np.zeros(0)
         if y0.shape != (S,) or not np.all(np.isfinite(y0)) or np.any(y0 < 0):
-            raise ValueError("MassActionODELogLike: %sy0 must hold %d finite, non-negative amounts" % (who, S))
+            raise ValueError("MassActionODELogLike: %sy0 must hold %d finite, non-negative amounts (numbers or Monomials)" % (who, S))
+        for s, m in given.items():
+            if monomials.setdefault(s, m) != m:
+                raise ValueError("MassActionODELogLike: %sy0[%d] is %r, but another y0 gives this species %r: one Monomial per species"
+                                 % (who, s, m, monomials[s]))
+            y0[s] = np.nan
         return y0
 
     @staticmethod
@@ -709,11 +875,19 @@ class MassActionODELogLike:
         blocks = [self.condition_block(c) for c in range(len(self.conditions))]
         return np.concatenate([[float(len(blocks)), float(len(blocks[0]))]] + blocks)
 
+    def _monomials(self):
+        """What the generated network needs beyond rate constants of one parameter each, or None: then the source is what it always was
+        (a scale factor of exactly 1.0 multiplies nothing)."""
+        if (self.y0_monomials or self.constraints or any(isinstance(r[2], Monomial) for r in self.reactions)
+                or (self.scale is not None and any(f != 1.0 for f in self.scale))):
+            return dict(y0=self.y0_monomials, scale=self.scale, constraints=self.constraints)
+        return None
+
     def source(self):
         items = self.conditions is not None
         if self.lanes_per_point == 1:
-            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items)
-        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items)
+            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials())
+        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items, self._monomials())
 
     @staticmethod
     def _header_hash(name="dz_ode.h"):
@@ -760,6 +934,7 @@ class MassActionODELogLike:
             L.dzode_simulate.argtypes = [P, I64, I, P, P, P]
             L.dzode_fixed.argtypes = [P, P, D, I, I, P]
             L.dzode_fixed.restype = I
+            L.dzode_constraints.argtypes = [P, I64, I, P]
             L.dzode_exp.argtypes = L.dzode_log.argtypes = [D]
             L.dzode_exp.restype = L.dzode_log.restype = D
             self._host = L
@@ -807,6 +982,15 @@ class MassActionODELogLike:
         terms = np.zeros((len(X), len(self.conditions)))
         self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), None, terms)
         return terms
+
+    def constraint_terms(self, X):
+        """g(x) = sum over the constraints of norm(loc, sd).logpdf(monomial) for the rows of X, from the host build: what the single
+        experiment's value, or condition 0's term, holds beyond the data's likelihood (0 without constraints; -inf where a coordinate
+        that a monomial or a rate reads, or a monomial's value, is not finite)."""
+        X = self._rows(X)
+        g = np.zeros(len(X))
+        self._host_call("dzode_constraints", X, len(X), X.shape[1], g)
+        return g
 
     def fixed_steps(self, x, t1, nsteps, embedded=False, condition=0):
         """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test).

@@ -9,7 +9,7 @@
   * run_dream generations/s with the likelihood on the device against the host path with 16 worker processes
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
-    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|chain8|enzyme13|chain32] [--lanes 1|16|32]
+    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|chain8|enzyme13|chain32|binding_cycle] [--lanes 1|16|32]
                                   [--conditions C]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
@@ -19,7 +19,8 @@ rounds' spread; points/s, items/s, and lane efficiency over the waves of the com
 
 chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
 scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
-enzyme13: pydream_amd/examples/enzyme.  --lanes defaults to the fewest lanes the network fits in.
+enzyme13: pydream_amd/examples/enzyme; binding_cycle: pydream_amd/examples/binding_cycle (monomials; 9 conditions per point, so a
+launch covers points x 9 items and steps are counted over a point's nine integrations).  --lanes defaults to the fewest lanes the network fits in.
 """
 import json
 import os
@@ -67,6 +68,10 @@ def network(name, lanes):
     if name == "enzyme13":
         from pydream_amd.examples.enzyme import enzyme_device as ENZ
         return ENZ.make_likelihood(lanes_per_point=lanes or 16), ENZ.NOMINAL, 1.0
+    if name == "binding_cycle":
+        assert lanes in (None, 1), "binding_cycle is a one-lane example"
+        from pydream_amd.examples.binding_cycle import binding_cycle_device as BC
+        return BC.make_likelihood(), BC.NOMINAL, 1.0
     from tests import ode_wide_networks as W
     S = dict(chain8=8, chain32=32)[name]
     if (lanes or (1 if S == 8 else 32)) == 1:                   # the same network and data through the one-lane kernel
