@@ -1355,6 +1355,10 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
         // five tries (the reference's multitry=True), nothing but the chains' own steps to leave behind, ONE launch of 16-chain blocks: the instantiation with
         // the try count compiled in and no publishing / adaptation code (same arithmetic, same draws, same name: k_generations' KC and PLAIN parameters)
         ml.kc = (e->mega_kc && p.k == 5 && !pb && !k1 && (xlds || !p.tri) && chp == 16 && wpcp == 1 && split_c == p.nl && !pp.to && pp.multi == 0 && !pp.PR && !pp.PC && !pp.TOT && !pp.CNT) ? 5 : 0;
+        if (ml.kc) {      // ... which keeps its output cursors in LDS behind the layout (MegaLayout::off_cur); where they do not fit, the generic instantiation runs
+            const size_t with_cur = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, xlds, chp, false, false, false, 0, false, true).total;
+            if (with_cur <= (size_t)160 * 1024) ldsp = with_cur; else ml.kc = 0;
+        }
         ml.grid = dim3((c1 - c0 + chp - 1) / chp); ml.block = dim3(64 * chp * wpcp); ml.lds = ldsp; ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
         ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = (uint32_t)visible_rows(e); ml.slot0 = slot0; ml.zappend = append_last ? e->M : (int64_t)-1; ml.seg0 = seg0; ml.publish = &pp;
         if (e->prof) { ml.ka = prof_event(e); ml.kb = prof_event(e); e->ev[PR_GENERATIONS].emplace_back(ml.ka, ml.kb); }

@@ -241,6 +241,13 @@ DZ_DEV bool u53_below(uint32_t hi, uint32_t lo, unsigned long long thr)
     return k < thr;
 }
 
+// A wave-uniform 64-bit word of LDS (every lane reads the same address) into scalar registers: the persistent kernel's output cursors
+DZ_DEV uint64_t lds_word_uniform(const double* w)
+{
+    const unsigned long long v = *reinterpret_cast<const unsigned long long*>(w);
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
 DZ_DEV uint32_t mulhi_idx(uint32_t w, uint32_t M) { return (uint32_t)(((uint64_t)w * (uint64_t)M) >> 32); }
 
 // slot layout of the precomputed uniform draws
@@ -422,7 +429,7 @@ DZ_DEV void reduce_rows(const ZRows<NCH>& zr, bool snk, RowTerms<NCH>& rt)
 // What a set of tries reads from Params, fetched ONCE per set by the persistent kernel (Params lives in memory there: every p.x inside
 // the try loop is a scalar load plus a wait, and scalar instructions cost nearly as much issue time as vector ones -- measured: 200 extra
 // s_add per generation = -3 %).  slot(i, idx) = slot0 + i npt + idx is pt_slot() of the set's phase.
-struct SetConsts { uint32_t thr; unsigned long long pgu_thr; double zeta, ec1, ec0; int npt, slot0; uint32_t k0, k1, gc; int d; };      // (k0, k1, gc, d: set_consts<K> only -- the Philox key, the chain's counter word, Params::d)
+struct SetConsts { uint32_t thr; unsigned long long pgu_thr; double zeta, ec1, ec0; int npt, slot0; uint32_t k0, k1, gc; int d, ld; };      // (k0, k1, gc, d, ld: set_consts<K> only -- the Philox key, the chain's counter word, Params::d, the row length)
 // Per-dimension constants of the priors (SampledParam: kind, loc, scale, log scale) and the hard boundaries, staged in LDS by the
 // persistent kernel's full-code instantiations ([ld] each): a try then costs LDS reads instead of eight dependent global loads.
 struct PBConsts { const double *a, *b, *logb, *lo, *hi; const int* kind; const double* inside; };      // (b: Params::pc2; inside: the log prior of a point inside every support, one LDS word)
@@ -434,13 +441,13 @@ DZ_DEV SetConsts set_consts(const Params& p, int phase, int cr_idx)
     return s;
 }
 
-template <int K>      // (the try count a compile-time constant, one pair per try: cf. pt_slot<K>)
-DZ_DEV SetConsts set_consts(const Params& p, int phase, int cr_idx, uint32_t gc)
+template <int K>      // (the try count a compile-time constant, one pair per try: cf. pt_slot<K>; ld: the row length where the caller knows it, 0: Params::ld)
+DZ_DEV SetConsts set_consts(const Params& p, int phase, int cr_idx, uint32_t gc, int ld = 0)
 {
     SetConsts s;
     s.thr = p.crthr[__builtin_amdgcn_readfirstlane(cr_idx)]; s.pgu_thr = p.pgu_thr; s.zeta = p.zeta; s.ec1 = p.ec1; s.ec0 = p.ec0;
     s.npt = 2; s.slot0 = 3 + (phase ? 2 * K : 0);
-    s.k0 = p.k0; s.k1 = p.k1; s.gc = gc; s.d = p.d;
+    s.k0 = p.k0; s.k1 = p.k1; s.gc = gc; s.d = p.d; s.ld = ld ? ld : p.ld;
     return s;
 }
 
@@ -456,7 +463,7 @@ DZ_DEV double propose_point(const Params& p, int phase, uint32_t g, uint32_t M, 
                           const SetConsts* sc = nullptr, const PBConsts* pc = nullptr, double (*prv)[2] = nullptr)
 {   // wpre: the DIM draw of chunk 0, computed by the caller one try ahead (software pipelining, NCH == 1)
     // pc: bounds from LDS; prv: receives the lane's proposal values as stored (for the prior evaluation: no read-back of the row)
-    const int d = (KC && sc) ? sc->d : p.d, ld = p.ld;
+    const int d = (KC && sc) ? sc->d : p.d, ld = (KC && sc) ? sc->ld : p.ld;
     const uint32_t gc = (KC && sc) ? sc->gc : (uint32_t)(p.off + c);
     const uint32_t thr = sc ? sc->thr : p.crthr[__builtin_amdgcn_readfirstlane(cr_idx)];   // CR = CR_values[m], :146 (the decision is wave-uniform)
     const uint32_t s_dim = stream_id(K_DIM, (uint32_t)i, (uint32_t)phase),

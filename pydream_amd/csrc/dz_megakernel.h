@@ -31,7 +31,16 @@ constexpr int DZ_MAX_REDRAWS_DEV = 64;                                  // == DZ
 constexpr unsigned long long DZ_REDRAW_KEY_STEP_DEV = 0x9E3779B97F4A7C15ull;   // == DZ_REDRAW_KEY_STEP
 constexpr int MEGA_CHAINS = 16;      // chains (= waves) per block at full size; 8 or 4 when there are too few chains to give every CU a block
 
-struct MegaLayout { int LDM, LDP, rows, off_P, off_q, off_sP, off_sS, off_sL, off_rP, off_rS, off_mu, off_pr, off_st, off_dec, off_gt, off_X, off_pc, pcn, off_Xo, off_tab, total; };
+// Output cursors of the <.., KC, PLAIN> instantiations: where a chain's stores of generation index 0 go, as 64-bit byte addresses in LDS.  What a chain writes per
+// generation moves by a launch constant (a trace row: ld doubles; a history append: N rows; a scalar column: nl elements), so the prologue builds each address
+// once and the generation loop adds index x stride -- no 64-bit address is rebuilt from kernel arguments and Params fields that would have to live in scalar
+// registers (or their spill lanes) across the whole loop.  Per chain: the trace row | the append row (for an archive of 0 rows: + M rows at use) | the state row |
+// the five scalar trace columns (log p, moved, try, CR index, snooker) | log prior | log likelihood.  Per block: the chain count nl, the columns' stride (one word
+// and one of padding: the area stays a whole number of 16-byte pairs).
+constexpr int MEGA_CUR_WORDS = 10, MEGA_CUR_BLOCK = 2;
+enum { CUR_TX = 0, CUR_APP = 1, CUR_X = 2, CUR_LOGP = 3, CUR_MOVED = 4, CUR_TRY = 5, CUR_CR = 6, CUR_SNK = 7, CUR_LPRI = 8, CUR_LLIK = 9 };
+
+struct MegaLayout { int LDM, LDP, rows, off_P, off_q, off_sP, off_sS, off_sL, off_rP, off_rS, off_mu, off_pr, off_st, off_dec, off_gt, off_X, off_pc, pcn, off_Xo, off_tab, off_cur, total; };
 
 // point rows of a block: try i of chain c at row i*ch + c; tiles are 16 consecutive rows, from row 0 (k tries) or from
 // row ch (the k-1 reference tries); rows past the last point stay zero
@@ -46,10 +55,11 @@ __host__ __device__ inline int mega_rows(int k, int ch)
 // nomat: the matrix is NOT staged (k_generations_d2, 128 < d <= 256: it does not fit next to the point tiles and is read from L2)
 // ntab: rows of the table of crossover / gamma-level probabilities per generation of the launch (adapt_lag >= 1: several burn-in generations per
 // launch, the MG instantiations; rows of (ncr + ngamma + 1) & ~1 doubles)
+// cur (k_generations<.., KC, PLAIN>): room for the launch's output cursors -- MEGA_CUR_WORDS 64-bit words per chain and MEGA_CUR_BLOCK for the block (see the kernel's prologue)
 // sp (k_generations_d2<.., SP>, round 6): the proposal set goes through the point tiles in two passes (tries 0 .. k-2, then the last one), the selected
 // proposal stays in registers: k - 1 tries' rows instead of k
 __host__ __device__ inline MegaLayout mega_layout(int d, int k, int nrt, int ncr, int ngamma, bool tri, bool xlds, int ch = MEGA_CHAINS, bool pb = false, bool xo = false, bool nomat = false, int ntab = 0,
-                                                  bool sp = false)
+                                                  bool sp = false, bool cur = false)
 {
     MegaLayout L;
     const int ks4 = 4 * ((d + 3) / 4);
@@ -78,6 +88,8 @@ __host__ __device__ inline MegaLayout mega_layout(int d, int k, int nrt, int ncr
     if (xo) L.total += ch * L.LDP + ((ch * L.LDP) & 1);
     L.off_tab = L.total;
     L.total += ntab * ((ncr + ngamma + 1) & ~1);
+    L.off_cur = L.total;
+    if (cur) L.total += MEGA_CUR_WORDS * ch + MEGA_CUR_BLOCK;
     return L;
 }
 
@@ -273,7 +285,10 @@ DZ_DEV void finish_draws(const Params& p, DrawSrc& q, bool snk, uint32_t M, int 
     q.xf = true;
 }
 
-template <bool XF>
+// PIN (the row pitch a compile-time constant): the two row bases are handed to the loads as scalar register pairs.  Left to itself the compiler folds the constant
+// pitch into a 64-bit vector address (base + lane offset, hoisted out of the generation loop, + row x pitch per load): two more registers across the loop, and the
+// address lands in the registers of the buffer it is about to fill -- a full vmcnt(0) wait, the trace stores of the generation before included.
+template <bool XF, bool PIN = false>
 DZ_DEV void request_pair(const Params& p, const DrawSrc& ds, int slot, uint32_t gc, uint32_t g, uint32_t M, int lane, RowPair& R, const double* Zb, uint32_t ldb)
 {   // slot = pt_slot(p, phase, i, 1); Zb / ldb: the archive and its row pitch in BYTES (fetched once per set, SetConsts)
     const u32x4 w = uniform_draw(p, ds, slot, gc, g);
@@ -286,6 +301,14 @@ DZ_DEV void request_pair(const Params& p, const DrawSrc& ds, int slot, uint32_t 
     }
     // (no lane predicate: lanes past ld re-read the row's last pair, masked where used)  scalar row base + 32-bit lane offset in bytes
     const uint32_t jb = (uint32_t)min(16 * lane, (int)ldb - 16);
+    if (PIN) {
+        uint64_t b0 = reinterpret_cast<uint64_t>(Zb) + (uint64_t)r0 * ldb, b1 = reinterpret_cast<uint64_t>(Zb) + (uint64_t)r1 * ldb;
+        uint32_t j = jb;      // (the lane offset too: its 64-bit extension would be hoisted out of the loop, away from the block that selects the load's addressing mode)
+        asm volatile("" : "+s"(b0), "+s"(b1), "+v"(j));
+        R.a = gload2(reinterpret_cast<const double*>(reinterpret_cast<const char*>(b0) + j));
+        R.b = gload2(reinterpret_cast<const double*>(reinterpret_cast<const char*>(b1) + j));
+        return;
+    }
     R.a = gload2(reinterpret_cast<const double*>(reinterpret_cast<const char*>(Zb) + (uint64_t)r0 * ldb + jb));
     R.b = gload2(reinterpret_cast<const double*>(reinterpret_cast<const char*>(Zb) + (uint64_t)r1 * ldb + jb));
 }
@@ -294,9 +317,10 @@ DZ_DEV void request_pair(const Params& p, const DrawSrc& ds, int slot, uint32_t 
 template <int LEAN, bool XF, int KC = 0>
 DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, int c, uint32_t gc, int i0, int i1, int n, int lane,
                           const double (&xb)[1][2], const double* __restrict__ grow, int cr_idx, int glev, const DrawSrc& ds,
-                          double* out, int out_stride, double* sl, double* prior_out, RowPair& A, RowPair& B, RowPair& C, const PBConsts* pc = nullptr)
-{
-    const SetConsts sc = KC ? set_consts<KC ? KC : 1>(p, phase, cr_idx, gc) : set_consts(p, phase, cr_idx);
+                          double* out, int out_stride, double* sl, double* prior_out, RowPair& A, RowPair& B, RowPair& C, const PBConsts* pc = nullptr,
+                          const double* Zb_in = nullptr, uint32_t ldb_in = 0)
+{   // Zb_in / ldb_in: the archive and its row pitch in bytes where the caller holds them already (0: Params::Z, 8 Params::ld)
+    const SetConsts sc = KC ? set_consts<KC ? KC : 1>(p, phase, cr_idx, gc, ldb_in ? (int)(ldb_in >> 3) : 0) : set_consts(p, phase, cr_idx);
     // (the tries' prior butterflies batched three at a time through wave_bfly4 -- lane partial sums kept across a round -- made the
     //  full-code kernel spill twice as much, 88 -> 180 bytes per lane, and cost 18 %: not kept)
     auto body = [&](int i, const RowPair& R) {
@@ -315,7 +339,7 @@ DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, in
         if (!LEAN && prior_out) point_prior<1>(p, out + (size_t)i * out_stride, lane, prior_out + i);
     };
     const int rs = sc.slot0 + 1;                          // pt_slot(phase, i, 1) = rs + i npt
-    const double* Zb = p.Z; const uint32_t ldb = 8u * (uint32_t)p.ld;
+    const double* Zb = ldb_in ? Zb_in : p.Z; const uint32_t ldb = ldb_in ? ldb_in : 8u * (uint32_t)p.ld;
     if (!LEAN) {      // full code: two row buffers -- the rows of try i + 1 in flight during try i (the caller requested tries i0 and i0 + 1)
         for (int i = i0; i < i1; i += 2) {
             body(i, A);
@@ -378,14 +402,20 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     constexpr int NT = 64 * CH * WPC;
     constexpr int LEANV = PB ? 0 : (K1 ? 2 : 1);
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int d = p.d, k = K1 ? 1 : (KC ? KC : p.k), ld = p.ld;
+    // CUR: output cursors in LDS (MegaLayout::off_cur), and the row length a constant: it is 16 NRT by construction (the host picks the row-tile count as ld / 16)
+    constexpr bool CUR = KC != 0 && PLAIN;
+    constexpr uint32_t LDB = 128u * NRT;      // (CUR) a row in bytes
+    // (the three arguments the loop keeps arrive in one eight-register load with trace_slot0 and zappend, which only the prologue reads now: taken out of that
+    //  tuple, or the whole of it is spilled and reloaded every generation)
+    if (CUR) asm("" : "+s"(g0), "+s"(ngen), "+s"(M0));
+    const int d = p.d, k = K1 ? 1 : (KC ? KC : p.k), ld = CUR ? 16 * NRT : p.ld;
     const bool pbl = PB && p.pb_lds != 0;
     static_assert(!MG || (CH == 16 && WPC == 1 && !K1 && XLDS && !REDO), "several burn-in generations per launch: 16 chains per block, one wave each, states in LDS");
     // (any instantiation; Publish::multi == 2) several burn-in generations per launch WITHOUT the block's own unit sums: the positions of every generation go to
     // the ring of published positions and k_adapt_partials_ring makes the sums behind the launch; the prologue and the table as with MG
     const bool RG = !PLAIN && !MG && pub.multi == 2;
     const bool fuse_adapt = !PLAIN && !MG && !RG && CH == 16 && WPC == 1 && !K1 && XLDS && pub.PR != nullptr;
-    const MegaLayout L = mega_layout(d, k, NRT, p.ncr, p.ngamma, TRI, XLDS, CH, pbl, MG || fuse_adapt, false, (MG || RG) ? pub.lag + 1 : 0);
+    const MegaLayout L = mega_layout(d, k, NRT, p.ncr, p.ngamma, TRI, XLDS, CH, pbl, MG || fuse_adapt, false, (MG || RG) ? pub.lag + 1 : 0, false, CUR);
     double* Ms = smem;
     double* Pt = smem + L.off_P;
     double* qb = smem + L.off_q;
@@ -457,6 +487,22 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
         q[3 * L.pcn + j] = hb ? p.mins[j] : -__builtin_huge_val(); q[4 * L.pcn + j] = hb ? p.maxs[j] : __builtin_huge_val();
         reinterpret_cast<int*>(q + 5 * L.pcn)[j] = hp ? p.pkind[j] : 0;
     }
+    const double* const curw = smem + L.off_cur + MEGA_CUR_WORDS * cl;      // (CUR) this chain's cursors; the block's words behind the chains'
+    const double* const curb = smem + L.off_cur + MEGA_CUR_WORDS * CH;
+    if (CUR && lane == 0) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(smem + L.off_cur) + MEGA_CUR_WORDS * cl;
+        const bool tr = trace_slot0 >= 0;      // (no trace: the words stay 0 -- the loop's `trace_slot0 >= 0`)
+        const unsigned long long o0 = tr ? (unsigned long long)trace_slot0 * (unsigned long long)p.nl + (unsigned long long)c : 0ull;
+        w[CUR_TX] = tr ? (unsigned long long)(p.tX + ((size_t)c * p.tcap + (size_t)trace_slot0) * ld) : 0ull;
+        // the append of a generation that samples from M rows goes to row zappend + (M - M0) + global chain: the word holds the address for M = 0 (unsigned
+        // arithmetic: with zappend < 0 there is no append and the word is never read)
+        w[CUR_APP] = (unsigned long long)p.Z + ((unsigned long long)zappend - (unsigned long long)M0 + (unsigned long long)gc) * (unsigned long long)LDB;
+        w[CUR_X] = (unsigned long long)(p.X + (size_t)c * ld);
+        w[CUR_LOGP] = tr ? (unsigned long long)(p.tlogp + o0) : 0ull; w[CUR_MOVED] = tr ? (unsigned long long)(p.tmoved + o0) : 0ull;
+        w[CUR_TRY] = tr ? (unsigned long long)(p.ttry + o0) : 0ull; w[CUR_CR] = tr ? (unsigned long long)(p.tcr + o0) : 0ull; w[CUR_SNK] = tr ? (unsigned long long)(p.tsnk + o0) : 0ull;
+        w[CUR_LPRI] = (unsigned long long)(p.lprior + c); w[CUR_LLIK] = (unsigned long long)(p.llike + c);
+        if (wv == 0) reinterpret_cast<unsigned long long*>(smem + L.off_cur)[MEGA_CUR_WORDS * CH] = (unsigned long long)(uint32_t)p.nl;
+    }
     if (lane == 0 && sub == 0) { st[4 * cl] = p.lprior[c]; st[4 * cl + 1] = p.llike[c]; st[4 * cl + 2] = 0.0; dec[8 * cl + 7] = chain_T(p, c); }      // (the chain's temperature: Dream.astep's T, core.py:133-136)
     if (XLDS && sub == 0) {
         for (int j = lane; j < L.LDP; j += 64) {
@@ -502,8 +548,8 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     auto prefetch_first = [&](const DrawSrc& q, int phase_, uint32_t g_, uint32_t M) {          // rows of this wave's first two tries of (g_, phase_)
         const int n_ = k - phase_;
         const int a0 = WPC == 1 ? 0 : (sub * n_) / WPC, a1 = WPC == 1 ? n_ : ((sub + 1) * n_) / WPC;
-        if (a0 < a1) request_pair<XF>(p, q, KC ? pt_slot<KCC>(phase_, a0, 1) : pt_slot(p, phase_, a0, 1), gc, g_, M, lane, RA, p.Z, 8u * (uint32_t)p.ld);
-        if (a0 + 1 < a1) request_pair<XF>(p, q, KC ? pt_slot<KCC>(phase_, a0 + 1, 1) : pt_slot(p, phase_, a0 + 1, 1), gc, g_, M, lane, RB, p.Z, 8u * (uint32_t)p.ld);
+        if (a0 < a1) request_pair<XF, CUR>(p, q, KC ? pt_slot<KCC>(phase_, a0, 1) : pt_slot(p, phase_, a0, 1), gc, g_, M, lane, RA, p.Z, CUR ? LDB : 8u * (uint32_t)p.ld);
+        if (a0 + 1 < a1) request_pair<XF, CUR>(p, q, KC ? pt_slot<KCC>(phase_, a0 + 1, 1) : pt_slot(p, phase_, a0 + 1, 1), gc, g_, M, lane, RB, p.Z, CUR ? LDB : 8u * (uint32_t)p.ld);
     };
     auto draws_say_snooker = [&](const DrawSrc& q, uint32_t g_) {                   // set_snooker :542-554 on the integer form of the draw
         const u32x4 w0 = uniform_draw(p, q, 0, gc, g_);
@@ -605,7 +651,8 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                                                           region + (size_t)phase * tstride, tstride, slp, nullptr, prp, pbl ? &pcs : nullptr);
                 } else if (!snk_s) {
                     propose_de_pf<LEANV, XF, KC>(p, phase, g, M, c, gc, a, b, n, lane, base, grow, f.cr_idx, f.glev, dcur,
-                                       region + (size_t)phase * tstride, tstride, slp, prp, A_, B_, C_, pbl ? &pcs : nullptr);
+                                       region + (size_t)phase * tstride, tstride, slp, prp, A_, B_, C_, pbl ? &pcs : nullptr,
+                                       CUR ? p.Z : nullptr, CUR ? LDB : 0u);
                 } else if (a < b) {
                     // a snooker set is the longest path to the block's barrier (three rows and three reductions per try, one chain in
                     // ten): its wave gets issue priority over the three DE waves it shares a SIMD with
@@ -716,13 +763,37 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
             const int jj = 2 * lane;
             double2 xo = {0.0, 0.0};
             if (XLDS) { const double* xr = Xs + cl * L.LDP; if (jj < d) xo.x = xr[jj]; if (jj + 1 < d) xo.y = xr[jj + 1]; }
-            else if (jj < ld) xo = *reinterpret_cast<const double2*>(p.X + (size_t)c * ld + jj);
+            else if (jj < ld) xo = *reinterpret_cast<const double2*>((CUR ? reinterpret_cast<const double*>(lds_word_uniform(curw + CUR_X)) : p.X + (size_t)c * ld) + jj);
             double2 xn = xo;
             if (accept) { xn.x = jj < d ? region[jj] : 0.0; xn.y = jj + 1 < d ? region[jj + 1] : 0.0; }   // the selected proposal
             const bool moved = __any((xn.x != xo.x) || (xn.y != xo.y));              // core.py:120
             const double npri = accept ? sP[cl * k + sel] : lpri, nlik = accept ? sL[cl * k + sel] : llik;   // :345-347
             if (XLDS && accept) { double* xr = Xs + cl * L.LDP; if (jj < d) xr[jj] = xn.x; if (jj + 1 < d) xr[jj + 1] = xn.y; }
             if (MG) { double* xq = smem + L.off_Xo + cl * L.LDP; if (jj < d) xq[jj] = xo.x; if (jj + 1 < d) xq[jj + 1] = xo.y; }      // the state before this generation (the jump's base)
+            if (CUR) {      // the stores through the chain's cursors: index x stride from the address the prologue built
+                const uint64_t ctx = lds_word_uniform(curw + CUR_TX);
+                const bool tr = ctx != 0;      // trace_slot0 >= 0
+                if (active) {
+                    if (jj < ld) {
+                        if (XLDS ? last : accept) gstore2(reinterpret_cast<double*>(lds_word_uniform(curw + CUR_X)) + jj, xn);
+                        if (tr) gstore2(reinterpret_cast<double*>(ctx + (uint64_t)(uint32_t)gi * LDB) + jj, xn);
+                        if (app) gstore2(reinterpret_cast<double*>(lds_word_uniform(curw + CUR_APP) + (uint64_t)M * LDB) + jj, xn);      // record_history :933-936
+                    }
+                    if (lane == 0) {
+                        if (tr) {
+                            const unsigned long long* w = reinterpret_cast<const unsigned long long*>(curw);
+                            const uint64_t o = (uint64_t)(uint32_t)gi * (uint64_t)(uint32_t)reinterpret_cast<const unsigned long long*>(curb)[0];      // generations x chains (Params::nl)
+                            *reinterpret_cast<double*>(w[CUR_LOGP] + 8 * o) = Tch * nlik + npri;      // core.py:115 (see below)
+                            *reinterpret_cast<uint8_t*>(w[CUR_MOVED] + o) = moved ? 1 : 0; *reinterpret_cast<int32_t*>(w[CUR_TRY] + 4 * o) = sel;
+                            *reinterpret_cast<int32_t*>(w[CUR_CR] + 4 * o) = cr_idx; *reinterpret_cast<uint8_t*>(w[CUR_SNK] + o) = snk ? 1 : 0;
+                        }
+                        if (last) {
+                            const unsigned long long* w = reinterpret_cast<const unsigned long long*>(curw);
+                            *reinterpret_cast<double*>(w[CUR_LPRI]) = npri; *reinterpret_cast<double*>(w[CUR_LLIK]) = nlik;
+                        }
+                    }
+                }
+            } else
             if (active) {
                 if (jj < ld) {
                     if (XLDS ? last : accept) gstore2(p.X + (size_t)c * ld + jj, xn);
