@@ -20,7 +20,25 @@
 // by C sub-blocks of stride doubles, each in the layout above (its own C_c, y0, data and sd; rtol .. T and t the same in all): the work
 // item w of the *_item_batch kernels is condition w % C of point w / C and integrates from sub-block w % C; see integrate_conditions.
 //
-// Every loop is bounded: at most max_steps attempted steps per output interval, T intervals.
+// EVENTS (MassActionODELogLike(events=...)): dosing and wash-out during an experiment.  An event (time, species, factor, amount) sets
+// y[species] = factor * y[species] + amount at `time` (two roundings: a product, then a sum).  A network of an object that has at least
+// one event in some experiment carries
+//     static constexpr int EVENTS = Emax;                              the largest event count over the object's experiments, 1..16
+// and each experiment's block (each sub-block, with conditions) grows after sd[T*O] by
+//     E_c, this experiment's event count (0..Emax),   then Emax records (time, species, factor, amount), sorted by time, padded with zeros
+// so that the conditions' stride stays uniform.  The block of a network without events is what it always was.  The semantics:
+//   * integration runs in SEGMENTS between breakpoints: t0, the event times and the output times; a segment's last step is clipped so
+//     that it lands exactly on the breakpoint; max_steps counts the attempted steps of a segment;
+//   * an output at time tau is taken before the events at tau (measure, then intervene), so an event at t[T-1] has no effect; the events
+//     at t0 are part of the start: they are applied to y0 before the start step is computed (and before an output at t0);
+//   * events at one time apply in the order given;
+//   * after the events at a time tau the controller restarts: h = start_step(y_after, rtol, atol, max(t[T-1] - tau, 1e-300)), the formula
+//     used at t0, rejected = false, the segment's step count 0; a start step that is not finite or not > 0 is a failed integration; the
+//     count of accepted steps (nsteps_out) keeps running;
+//   * a point that is not live applies nothing and takes no step.
+// Event times come from the block, so control flow stays uniform within a lane group.  integrate_fixed ignores events.
+//
+// Every loop is bounded: at most max_steps attempted steps per segment, at most T + Emax segments.
 //
 // MONOMIALS (likelihoods.Monomial): a rate constant, a start amount, an observable's scale factor or the argument of a Gaussian
 // constraint may be 10**(c + sum_i e_i x[i]), a product of powers of the sampled constants.  The arithmetic is the same on device and
@@ -143,6 +161,14 @@ template <class Net, class = void> struct has_monomials { static constexpr bool 
 template <class Net> struct has_monomials<Net, decltype((void)Net::MONOMIALS)> { static constexpr bool value = true; };
 template <class Net, class = void> struct has_constraints { static constexpr bool value = false; };
 template <class Net> struct has_constraints<Net, decltype((void)&Net::constraints)> { static constexpr bool value = true; };
+
+// ... and events (the head of the file): EVENTS is the bound of the event loop and the record count of every experiment's block
+template <class Net, class = void> struct has_events { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_events<Net, decltype((void)Net::EVENTS)> {
+    static constexpr bool value = true;
+    static constexpr int count = Net::EVENTS;
+    static_assert(Net::EVENTS >= 1 && Net::EVENTS <= 16, "1..16 events per experiment");
+};
 
 template <class Net>
 DZO_HD bool monomials_live(const double* x)
@@ -364,9 +390,13 @@ DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h
 //     sh.all_finite(yn, seed)                          seed && every amount of yn finite
 //     sh.any_negative(yn, y, rtol, atol)               an amount of yn below -(atol + rtol |y|)
 //     sh.observe(y, o)                                 o[O]
+//     Shape::EVENTS, sh.apply(y, species, factor, amount)   (a network with events: Emax, and y[species] = factor * y[species] + amount)
 // and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
 // Group<Net, L> (dz_ode_group.h: a group of L lanes per point, and its host twin).  A point that is not live keeps h = 0, ok = false and
 // takes no step, but does not return ahead of the loop: the lanes of a group stay with their wave.
+// With events (the head of the file) every pass of the outer loop is one SEGMENT: the events that are due and the controller's (re)start
+// -- the start at t0 is the first of them, so the start step exists once in the code --, the steps up to the next breakpoint, and the
+// output if the breakpoint is one.  Without events a pass is an output interval, as it always was.
 template <class Shape>
 DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* sim, int* nsteps_out)
 {
@@ -380,14 +410,39 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     double o[O];
     sh.init(blk, y);
     double t = t0, acc = 0.0;
-    double h = live ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
-    bool ok = live && finite(h) && h > 0.0, rejected = false;
+    constexpr int EV = Shape::EVENTS;
+    double h = 0.0;
+    bool ok = live, rejected = false;
+    if constexpr (EV == 0) {
+        h = live ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
+        ok = live && finite(h) && h > 0.0;
+    }
     int nsteps = 0;
-    for (int j = 0; ok && j < T; ++j) {
+    // (without events the block ends with sd: evt is then the pointer one past its end, only formed and never read)
+    [[maybe_unused]] const double* evt = sd + (long long)T * O + (EV > 0 ? 1 : 0);      // records of (time, species, factor, amount)
+    [[maybe_unused]] int ev = 0, E = 0;                                      // the event cursor, this experiment's event count
+    [[maybe_unused]] bool fresh = true;                                      // the controller is to be (re)started: at t0, after events
+    if constexpr (EV > 0) E = (int)dmin(evt[-1], (double)EV);
+    for (int j = 0; ok && j < T;) {
         const double tout = tt[j];
-        for (int n = 0; t < tout; ++n) {
-            const bool clip = t + h >= tout;
-            const double hs = clip ? tout - t : h;
+        double tend = tout;                                                  // the segment's end
+        if constexpr (EV > 0) {
+#pragma unroll 1
+            for (; ev < E && evt[4 * ev] <= t; ++ev) {                       // the events that are due, in the order given
+                sh.apply(y, (int)evt[4 * ev + 1], evt[4 * ev + 2], evt[4 * ev + 3]);
+                fresh = true;
+            }
+            if (fresh) {
+                h = sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t, 1e-300));
+                rejected = false;
+                fresh = false;
+                if (!(finite(h) && h > 0.0)) { ok = false; break; }
+            }
+            if (ev < E && evt[4 * ev] < tout) tend = evt[4 * ev];            // (an event at tout: after the output, in the next pass)
+        }
+        for (int n = 0; t < tend; ++n) {
+            const bool clip = t + h >= tend;
+            const double hs = clip ? tend - t : h;
             if (n >= max_steps || t + hs == t) { ok = false; break; }
             double err2;
             const bool nonsing = sh.step(y, hs, rtol, atol, yn, err2);
@@ -401,8 +456,8 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             if (err2 <= 1.0 && !neg) {
                 if (rejected) fac = dmin(fac, 1.0);
                 y = yn;
-                t = clip ? tout : t + hs;
-                h = clip ? dmax(h, hs * fac) : hs * fac;       // (a step clipped to the output time leaves the controller's size alone)
+                t = clip ? tend : t + hs;
+                h = clip ? dmax(h, hs * fac) : hs * fac;       // (a step clipped to the breakpoint leaves the controller's size alone)
                 rejected = false;
             } else {
                 h = hs * fac;
@@ -410,6 +465,9 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             }
         }
         if (!ok) break;
+        if constexpr (EV > 0) {
+            if (tend < tout) continue;                                       // landed on an event, not on the output time
+        }
         sh.observe(y, o);
 #pragma unroll
         for (int q = 0; q < O; ++q) {
@@ -417,6 +475,7 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             acc = acc - 0.5 * r * r;
             if (sim) sim[(long long)j * O + q] = o[q];
         }
+        ++j;
     }
     if (nsteps_out) *nsteps_out = nsteps;
     return ok ? blk[0] + acc : -__builtin_huge_val();
@@ -457,7 +516,7 @@ DZO_HD double start_step(const double* k, const double* y, double rtol, double a
 
 template <class Alg>
 struct Array {
-    static constexpr int S = Alg::Net::S, O = Alg::Net::O;
+    static constexpr int S = Alg::Net::S, O = Alg::Net::O, EVENTS = has_events<typename Alg::Net>::count;
     struct State { double v[S]; };
     const double* k;                                   // the rate constants
     const double* x;                                   // the point's row (read only by a network with monomials)
@@ -486,6 +545,11 @@ struct Array {
         return neg;
     }
     DZO_HD void observe(const State& y, double* o) const { observe_scaled<typename Alg::Net>(x, y.v, o); }
+    DZO_HD void apply(State& y, int species, double factor, double amount) const      // (a select over the unrolled s: y stays in registers)
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) y.v[s] = s == species ? factor * y.v[s] + amount : y.v[s];
+    }
 };
 
 // One point through an array shape.  The rate constants are tested here, ahead of the loop, and the loop runs with live a constant.

@@ -1,7 +1,7 @@
 // dz_ode_group.h -- dz_ode.h's solver for networks of 9..32 species: a GROUP of L = 16 or 32 lanes integrates one point together
 // (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32)).  The method is dz_ode.h's, and so is the code: its stepping loop
-// (dzode::integrate: step controller, negativity rule, max_steps per output interval, exact landing on the output times, -inf on any
-// failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
+// (dzode::integrate: step controller, negativity rule, max_steps per output interval, exact landing on the output times, events, -inf on
+// any failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
 //     row r of W = I / (h gamma) - J in registers (S doubles, constant column indices after unrolling),
 //     entry r of y, of the stage argument u and of k1..k6,
 //     one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled by S group broadcasts per stage);
@@ -35,7 +35,7 @@
 //     static void obs(const double* y, double* o);
 // and, for a network with monomials (dz_ode.h's head: the construct, its arithmetic and the members live, y0_row, scale, constraints),
 //     static double rate_mono(int j, const double* x, bool& good);    the rate constant of a reaction whose rate_index is -2
-// Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks).
+// Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd).
 #pragma once
 #include "dz_ode.h"
 
@@ -284,7 +284,7 @@ __device__ __forceinline__ double group_start_step(const double* ks, double y, d
 // live = false (a point past the batch's end, or a rate constant that is not finite): no step is taken, -inf.
 template <class Net, int L>
 struct Group {
-    static constexpr int S = Net::S, O = Net::O;
+    static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
     typedef double State;
     const double* ks;                                  // the point's rate constants (LDS)
     int r;
@@ -308,6 +308,10 @@ struct Group {
         double yr[S];
         Lanes<L>::template gather<S>(y, yr);
         observe_scaled<Net>(x, yr, o);
+    }
+    __device__ __forceinline__ void apply(double& y, int species, double factor, double amount) const
+    {
+        y = r == species ? factor * y + amount : y;
     }
 };
 #endif

@@ -361,6 +361,7 @@ class DeviceKernelLogLike:
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
 ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
 ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
+ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 _LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
 
@@ -506,10 +507,13 @@ def _obs_lines(S, observables):
     return L
 
 
-def _net_source(header, S, R, O, body, observables, entries):
+def _net_source(header, S, R, O, body, observables, entries, events=0):
     """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
-    closing brace of the last one), the observables and the entry macro."""
-    L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O)] + body
+    closing brace of the last one), the observables and the entry macro.  events: the largest event count over the object's
+    experiments; the member EVENTS only if there is one (csrc/dz_ode.h)."""
+    L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O)]
+    L += ["    static constexpr int EVENTS = %d;" % events] if events else []
+    L += body
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(S, observables) + ["    }", "};", entries, ""]
     return '#include "%s"\n' % header + "\n".join(L)
 
@@ -517,7 +521,7 @@ def _net_source(header, S, R, O, body, observables, entries):
 _ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
 
 
-def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None):
+def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None, events=0):
     """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
     order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
     reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
@@ -563,16 +567,16 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events)
 
 
-def _ode_source(S, reactions, observables, log10, items=False, mono=None):
+def _ode_source(S, reactions, observables, log10, items=False, mono=None, events=0):
     """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
     straight-line code with constant indices; powers as repeated products.  items: the entry points for several conditions per point."""
     R, O = len(reactions), len(observables)
     entries = "DZODE_ITEM_ENTRIES(Net)" if items else "DZODE_ENTRIES(Net)"
     if R > _ODE_WHOLE_SUMS:
-        return _ode_long_source(S, reactions, observables, log10, entries, mono)
+        return _ode_long_source(S, reactions, observables, log10, entries, mono, events)
     N = _stoichiometry(S, reactions)
     L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     for r, (_, _, rate) in enumerate(reactions):
@@ -597,10 +601,10 @@ def _ode_source(S, reactions, observables, log10, items=False, mono=None):
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events)
 
 
-def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None):
+def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None, events=0):
     """The generated network struct for the lane-group solver (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
     its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
     stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
@@ -646,7 +650,7 @@ def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono
                  for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
     L += ["        default: return 0.0;", "        }", "    }"] + (_monomial_members(mono) if mono else [])
-    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes)
+    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes, events)
 
 
 class MassActionODELogLike:
@@ -684,13 +688,27 @@ class MassActionODELogLike:
     shapes round differently, so their values on a network both can run agree to the integration tolerance, not to the bit.
 
     conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
-    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd"; a missing key is the constructor's own argument, which may be
-    None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
+    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events"; a missing key is the constructor's own argument,
+    which (y0, data, sd) may be None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
     point is ((l_0 + l_1) + l_2) + ..., l_c exactly what this class gives for condition c alone (-inf if any integration fails).  On the
     device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
     dz_ode_group_item_batch, dz_set_likelihood_items), and the engine adds a point's items in that order; the host build loops the same
     way and gives the same bits.  simulate then returns [n, C, T, O], batch(return_steps=True) the steps of all conditions, and
     batch_conditions(X) the l_c, [n, C].
+
+    events: interventions during an experiment -- a sequence of at most 16 (ODE_MAX_EVENTS) tuples (time, species, factor, amount): at
+    `time` the amount of `species` becomes factor * y + amount (a product, then a sum: two roundings).  A bolus is (t, s, 1, dose), a
+    wash-out (t, s, 0, 0), setting a value (t, s, 0, v), a dilution (t, s, 0.5, 0).  t0 <= time <= t[-1]; factor and amount are finite
+    and >= 0.  Events are sorted by time (stably: events at one time apply in the order given).  A condition's "events" replaces the
+    constructor's ([]: none; a missing key or None inherits them, as for y0, data and sd); the constructor's events=None and
+    events=[] both mean none, and an object without any generates the source and the data
+    block it always did.  Integration runs in segments between breakpoints -- t0, the event times, the output times -- and lands
+    exactly on each; max_steps counts the attempted steps of a segment.  An output at an event's time is taken BEFORE the event
+    (measure, then intervene), so an event at t[-1] has no effect; events at t0 are part of the start: applied to y0 before the
+    start step, and seen by an output at t0.  After the events at a time the step controller restarts with the start step's formula
+    from the new state (a start step that is not finite or not > 0: -inf); batch(return_steps=True) counts the accepted steps of all
+    segments.  Both builds and both shapes follow this exactly (csrc/dz_ode.h) and give the same bits.  Not supported: an amount that
+    is a Monomial (a sampled dose), events triggered by the state; fixed_steps ignores events.
 
     Products of parameters: a Monomial(exponents, log10_factor) = 10**(log10_factor + sum_i exponents[i] x[i]) may stand
       * as a reaction's rate (kr = KD kf with a fixed kf: Monomial({i: 1}, log10(kf)); a closed cycle: Monomial({0: 1, 1: 1, 2: -1}));
@@ -708,10 +726,11 @@ class MassActionODELogLike:
     inside a monomial.  A model that uses none of this generates the source, and runs the kernels, it always did."""
 
     conditions = None       # (an object pickled before the keyword existed)
+    events = None           # (likewise)
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
-                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None):
+                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None):
         S = int(n_species)
         lanes = int(lanes_per_point)
         if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"]:
@@ -753,8 +772,8 @@ class MassActionODELogLike:
             if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
                 raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
             for c, cond in enumerate(conditions):
-                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd"}:
-                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd" (each optional)' % c)
+                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events"}:
+                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events" (each optional)' % c)
                 for key, top in (("y0", y0), ("data", data), ("sd", sd)):
                     if cond.get(key) is None and top is None:
                         raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
@@ -774,6 +793,7 @@ class MassActionODELogLike:
         O, T = len(obs), len(t)
         if data is not None and sd is not None:
             data, sd = self._checked_data(data, sd, O, T, "")
+        events = self._checked_events(events, S, float(t0), t, "")
         if conditions is not None:              # every condition as the single experiment: its own values, else the constructor's (checked above)
             full = []
             for c, cond in enumerate(conditions):
@@ -782,7 +802,8 @@ class MassActionODELogLike:
                 cdata, csd = (data if cond.get("data") is None else cond["data"]), (sd if cond.get("sd") is None else cond["sd"])
                 if cond.get("data") is not None or cond.get("sd") is not None or data is None or sd is None:
                     cdata, csd = self._checked_data(cdata, csd, O, T, who)
-                full.append(dict(y0=cy0, data=cdata, sd=csd))
+                cev = events if "events" not in cond or cond["events"] is None else self._checked_events(cond["events"], S, float(t0), t, who)
+                full.append(dict(y0=cy0, data=cdata, sd=csd, events=cev))
             conditions = full
         if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
             raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
@@ -813,6 +834,7 @@ class MassActionODELogLike:
         self.n_species, self.reactions, self.observables, self.log10 = S, rx, obs, rate_scale == "log10"
         self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
         self.data, self.sd = data, sd
+        self.events = events or None            # None, or the checked (time, species, factor, amount) tuples sorted by time
         self.conditions = conditions            # None, or a list of dict(y0, data, sd): checked arrays, the fallbacks filled in
         self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
         self.path, self.lanes_per_point = path, lanes
@@ -840,6 +862,35 @@ class MassActionODELogLike:
         return y0
 
     @staticmethod
+    def _checked_events(events, S, t0, t, who):
+        """The events as a tuple of (time, species, factor, amount), stably sorted by time (events at one time keep the order given)."""
+        real = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer, float, np.floating)) and np.isfinite(v)      # noqa: E731
+        if events is None:
+            return ()
+        try:
+            events = list(events)
+        except TypeError:
+            raise ValueError("MassActionODELogLike: %sevents must be a sequence of (time, species, factor, amount)" % who)
+        if len(events) > ODE_MAX_EVENTS:
+            raise ValueError("MassActionODELogLike: %sat most %d events per experiment are supported (got %d)" % (who, ODE_MAX_EVENTS, len(events)))
+        out = []
+        for e, event in enumerate(events):
+            if not isinstance(event, (tuple, list)) or len(event) != 4:
+                raise ValueError("MassActionODELogLike: %sevent %d must be (time, species, factor, amount)" % (who, e))
+            time, species, factor, amount = event
+            if not real(time) or not t0 <= time <= t[-1]:
+                raise ValueError("MassActionODELogLike: %sevent %d: the time must be finite and lie in t0 = %r <= time <= t[-1] = %r (got %r)"
+                                 % (who, e, t0, float(t[-1]), time))
+            if isinstance(species, bool) or not isinstance(species, (int, np.integer)) or not 0 <= species < S:
+                raise ValueError("MassActionODELogLike: %sevent %d names species %r (an int in 0..%d)" % (who, e, species, S - 1))
+            if isinstance(factor, Monomial) or isinstance(amount, Monomial):
+                raise ValueError("MassActionODELogLike: %sevent %d: factor and amount are numbers; a Monomial (a sampled dose) is not supported" % (who, e))
+            if not real(factor) or factor < 0 or not real(amount) or amount < 0:
+                raise ValueError("MassActionODELogLike: %sevent %d: factor and amount must be finite and >= 0 (got %r, %r)" % (who, e, factor, amount))
+            out.append((float(time), int(species), float(factor), float(amount)))
+        return tuple(sorted(out, key=lambda ev: ev[0]))
+
+    @staticmethod
     def _checked_data(data, sd, O, T, who):
         data, sd = np.asarray(data, dtype=float), np.asarray(sd, dtype=float)
         try:
@@ -854,19 +905,35 @@ class MassActionODELogLike:
         return data, np.array(sd)
 
     # ---- the data block (csrc/dz_ode.h) and the generated source
-    def _experiment_block(self, y0, data, sd):
+    def _event_lists(self):
+        """Every experiment's events (a condition made before the keyword existed has none)."""
+        if self.conditions is None:
+            return [self.events or ()]
+        return [cond.get("events") or () for cond in self.conditions]
+
+    def _max_events(self):
+        """Emax, the generated network's EVENTS: the largest event count over the object's experiments (0: a network without events)."""
+        return max(len(ev) for ev in self._event_lists())
+
+    def _experiment_block(self, y0, data, sd, events=()):
         seen = np.isfinite(data)
         C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
         dat = np.where(seen, data, 0.0).T.reshape(-1)               # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
         sd = np.where(seen, sd, np.inf).T.reshape(-1)
-        return np.concatenate([[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], y0, self.t, dat, sd])
+        blk = [[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], y0, self.t, dat, sd]
+        emax = self._max_events()
+        if emax:                                # (csrc/dz_ode.h: E_c, then Emax records padded with zeros -- one stride for all conditions)
+            rec = np.zeros((emax, 4))
+            rec[:len(events)] = np.asarray(events, dtype=float).reshape(-1, 4)
+            blk += [[float(len(events))], rec.reshape(-1)]
+        return np.concatenate(blk)
 
     def condition_block(self, c=0):
         """One experiment's block: condition c's, or (without conditions) the constructor's own."""
         if self.conditions is None:
-            return self._experiment_block(self.y0, self.data, self.sd)
+            return self._experiment_block(self.y0, self.data, self.sd, self.events or ())
         cond = self.conditions[c]
-        return self._experiment_block(cond["y0"], cond["data"], cond["sd"])
+        return self._experiment_block(cond["y0"], cond["data"], cond["sd"], cond.get("events") or ())
 
     def data_block(self):
         """The block the kernels read (csrc/dz_ode.h): one experiment's, or with conditions [C, stride] and the C experiments' blocks."""
@@ -886,8 +953,9 @@ class MassActionODELogLike:
     def source(self):
         items = self.conditions is not None
         if self.lanes_per_point == 1:
-            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials())
-        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items, self._monomials())
+            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials(), self._max_events())
+        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items, self._monomials(),
+                                 self._max_events())
 
     @staticmethod
     def _header_hash(name="dz_ode.h"):

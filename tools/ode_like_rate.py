@@ -9,15 +9,21 @@
   * run_dream generations/s with the likelihood on the device against the host path with 16 worker processes
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
-    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|chain8|enzyme13|chain32|binding_cycle] [--lanes 1|16|32]
-                                  [--conditions C]
+    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|binding_cycle] [--lanes 1|16|32]
+                                  [--conditions C [--events E]]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
 over the points (what the class could do before it took conditions), alternately, the median of 7 rounds of 10 calls each and the
 rounds' spread; points/s, items/s, and lane efficiency over the waves of the combined launch (consecutive ITEMS).  Kernel only.
 
-chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
+--conditions C --events E: what the restarts of dosing and wash-out events cost (MassActionODELogLike(events=...)) -- the network under C
+conditions with E events in each (at equal distances inside the time span, on the species with the largest start amount: halved, then
+topped up by half its start amount, in turn) against the same C conditions without events, alternately, the median of 7 rounds of 10
+calls each and the rounds' spread; proposals/s and the host build's steps per point for both.  --events 0 times the event-less object
+alone and never names the keyword (so the same script runs on a checkout from before the keyword existed).  Kernel only.
+
+mm: tests/ode_networks' Michaelis-Menten network (4 species), imported from the test package like chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
 scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
 enzyme13: pydream_amd/examples/enzyme; binding_cycle: pydream_amd/examples/binding_cycle (monomials; 9 conditions per point, so a
 launch covers points x 9 items and steps are counted over a point's nine integrations).  --lanes defaults to the fewest lanes the network fits in.
@@ -72,6 +78,10 @@ def network(name, lanes):
         assert lanes in (None, 1), "binding_cycle is a one-lane example"
         from pydream_amd.examples.binding_cycle import binding_cycle_device as BC
         return BC.make_likelihood(), BC.NOMINAL, 1.0
+    if name == "mm":
+        assert lanes in (None, 1), "mm is a one-lane network"
+        from tests import ode_networks as NW
+        return NW.michaelis_menten(), NW.MM_NOMINAL, 1.0
     from tests import ode_wide_networks as W
     S = dict(chain8=8, chain32=32)[name]
     if (lanes or (1 if S == 8 else 32)) == 1:                   # the same network and data through the one-lane kernel
@@ -131,6 +141,51 @@ def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
                steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)),
                separate_launches_us=round(us_sep, 1), separate_launches_us_min_max=[round(min(t["separate"]), 1), round(max(t["separate"]), 1)],
                separate_over_combined=round(us_sep / us, 3))
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10):
+    from pydream_amd import _capi
+    from pydream_amd.likelihoods import MassActionODELogLike
+    like, nominal, width = network(name, lanes)
+    plain, _ = with_conditions(like, C)
+    objs = {"without_events": plain}
+    if E > 0:
+        s = int(np.argmax(like.y0))
+        span = like.t[-1] - like.t0
+        events = [(like.t0 + (e + 1) * span / (E + 1), s, 0.5, 0.0) if e % 2 == 0 else (like.t0 + (e + 1) * span / (E + 1), s, 1.0, 0.5 * like.y0[s])
+                  for e in range(E)]
+        objs["with_events"] = MassActionODELogLike(like.n_species, like.reactions, None, like.t, like.observables, like.data, like.sd,
+                                                   rate_scale=like.rate_scale, t0=like.t0, rtol=like.rtol, atol=like.atol, max_steps=like.max_steps,
+                                                   lanes_per_point=like.lanes_per_point, conditions=[dict(y0=c["y0"]) for c in plain.conditions], events=events)
+    n, d = N * k, len(nominal)
+    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
+    engines = {}
+    for key, obj in objs.items():
+        eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
+        eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
+        obj._dz_apply(eng)
+        engines[key] = eng
+    out = dict(network=name, lanes=like.lanes_per_point, conditions=C, events_per_condition=E, chains=N, tries=k, points=n, items=n * C)
+    for key, eng in engines.items():
+        for _ in range(3):
+            lk = eng.eval_logp(X)[1]
+        host, steps = objs[key].batch(X, return_steps=True)
+        assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
+        out[key] = dict(steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)))
+    t = {key: [] for key in engines}
+    for _ in range(rounds):                                             # alternately: a drift of the machine hits both alike
+        for key, eng in engines.items():
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                eng.eval_logp(X)
+            t[key].append((time.perf_counter() - t0) / reps * 1e6)
+    for key in engines:
+        us = float(np.median(t[key]))
+        out[key].update(us_per_launch=round(us, 1), us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6))
+    if E > 0:
+        out["with_over_without"] = round(out["with_events"]["us_per_launch"] / out["without_events"]["us_per_launch"], 3)
     print(json.dumps(out), flush=True)
     return out
 
@@ -196,11 +251,17 @@ def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--network", "--lanes", "--conditions"):
+    for flag in ("--network", "--lanes", "--conditions", "--events"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
+    if "--events" in opt:
+        assert "--conditions" in opt, "--events goes with --conditions C"
+        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
+        events_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
+                    int(opt["--conditions"]), int(opt["--events"]))
+        sys.exit(0)
     if "--conditions" in opt:
         nums = [int(a) for a in argv[:2] if not a.startswith("--")]
         conditions_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
