@@ -1,6 +1,6 @@
 """Differential fuzzing of the HIP engine against the CPU oracle: random configurations (sizes off every tile and strip boundary,
 multitry on / off, several DE pairs, gamma levels, crossover / gamma adaptation, snooker rates, priors with and without hard boundaries,
-redraw rounds, history thinning and lag, dense / triangular MVN, mixture and host likelihoods, parallel tempering, chain-by-chain
+redraw rounds, history thinning and lag, dense / triangular MVN, mixture, host and user-kernel (module) likelihoods, parallel tempering, chain-by-chain
 stepping, sharded engines), same seeded inputs to both, everything
 compared bit for bit -- decision sequences, states, log densities, archive, adaptation state.
 
@@ -17,16 +17,33 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
+from tests import module_kernels as MK
+
+MODULE_SHAPES = ["thread", "wave", "group16", "group32", "items", "items", "function", "function"]
 DIMS = [2, 3, 5, 10, 16, 17, 31, 32, 33, 48, 64, 65, 100, 100, 100, 112, 127, 128, 129, 200, 333]
 CHAINS = [3, 4, 5, 15, 16, 17, 48, 63, 64, 65, 100, 250, 256, 1000, 1024, 1100, 2048]
 
 
-def draw_config(rng, long=False, dims=None, chains=None, adapt_lag_arm=False, sharded_arm=False):
+def draw_config(rng, long=False, dims=None, chains=None, adapt_lag_arm=False, sharded_arm=False, module_arm=False):
+    """module_arm (off: exactly the draws, and the configurations, of before the arm existed -- tests/test_fuzz_draws_cpu.py pins them): the likelihood is
+    one of tests/module_kernels.py's user kernels (LK_MODULE: dz_set_likelihood_module / dz_set_likelihood_items, DeviceKernelLogLike,
+    DeviceFunctionLogLike) on the HIP engine and its numpy twin through the host callback on the oracle; every shape but `function` half of the
+    time as its non-finite variant (always_finite=False, -inf beyond a cut: redraw rounds through the user kernel, most of them under the
+    uniform_open prior).  Everything else is drawn as without the arm -- sharding over ThreadExchange, tempering, S1, history_lag, adapt_lag,
+    priors, two step calls -- but the sizes are capped for the oracle's host callback: N <= 1100, d <= 200, no 1000-D.
+    Excluded from the arm by rule: nothing.  The engine refuses no mode because its likelihood is a module (read in csrc/dz_engine.hip: the only
+    refusals that name a mode are those of tempering with sharding or adapt_lag and of single-chain stepping with sharding, history_lag or
+    adapt_lag, none of which this function draws with any likelihood); tests/test_module_modes_gpu.py runs each mode with a module likelihood
+    at a fixed size, `function` sharded (where it is carried by k_generations_user as well) included."""
+    user_chains = chains                                      # (what --chains gave: it alone lifts the cap below)
+    if module_arm:                                            # the arm's own lists where the caller gave none
+        dims = dims or [x for x in DIMS if x <= 200]
+        chains = chains or [x for x in CHAINS if x <= 1100]
     d = int(rng.choice(dims or DIMS))
     N = int(rng.choice(chains or (CHAINS + ([3000, 4096, 4096] if long else []))))
-    if d > 128 and not chains:                                # (oracle time; --chains lifts it: the k_generations_d2 regime is 128 < d <= 228)
+    if d > 128 and not user_chains:                                # (oracle time; --chains lifts it: the k_generations_d2 regime is 128 < d <= 228)
         N = min(N, 256)
-    if rng.random() < 0.04:
+    if rng.random() < 0.04 and not module_arm:
         d, N = 1000, int(rng.choice([16, 130]))
     k = int(rng.choice([1, 1, 3, 4, 5, 5, 5, 6, 9, 16, 20]))      # (round 6: 16..32 tries run k_generations_d2 above 1024 chains with the triangular factor; below, and otherwise, the multi-kernel path)
     depairs = int(rng.choice([1, 1, 1, 2, 3]))
@@ -41,6 +58,8 @@ def draw_config(rng, long=False, dims=None, chains=None, adapt_lag_arm=False, sh
     lk = str(rng.choice(["mvn_dense", "mvn_tri", "mvn_tri", "mix"]))
     if N <= 256 and d <= 128 and rng.random() < 0.1:          # a host likelihood (the reference's usual case: a Python function), batch callback
         lk = "host"
+    if module_arm:
+        lk = str(rng.choice(MODULE_SHAPES))
     prior = str(rng.choice(["flat", "flat", "normal", "uniform", "uniform_narrow", "uniform_open"]))
     if prior == "uniform_open" and k == 1:
         prior = "uniform"
@@ -66,6 +85,9 @@ def draw_config(rng, long=False, dims=None, chains=None, adapt_lag_arm=False, sh
     if (adapt_cr or adapt_g) and not cfg["pt"] and not cfg["s1"] and (adapt_lag_arm or rng.random() < 0.6):
         cfg["adapt_lag"] = int(rng.choice([1, 2, 4, 9, 19]))
         cfg["burnin"] = int(rng.choice([6, 15, max(13, n - 8), n + 5]))
+    if module_arm:
+        cfg["items"] = int(rng.choice(MK.ITEM_COUNTS)) if lk == "items" else 1
+        cfg["finite"] = int(lk == "function" or rng.random() < 0.5)
     return cfg
 
 
@@ -103,6 +125,8 @@ def build(Cls, c, device_kw):
         e.set_likelihood_mvn(np.zeros(d) if c["zero_mean"] else np.linspace(-1, 1, d), Mx, 1 if tri else 0, 0.0)
     elif c["lk"] == "host":
         e.set_likelihood_host(lambda X: (np.zeros(len(X)), -0.5 * np.sum((X - 2.0) ** 2, axis=1) / 9.0))
+    elif c["lk"] in MK.SHAPES:                                # the kernel on the HIP engine, its numpy twin on the oracle
+        MK.apply(e, c["lk"], d, module_cut(c, Z0), c["items"], oracle=Cls.__module__.startswith("oracle"))
     else:
         J = c["J"]
         mu = np.array([np.full(d, m) for m in np.linspace(-4.0, 6.0, J)])
@@ -114,6 +138,12 @@ def build(Cls, c, device_kw):
     off, nl = device_kw.get("chain_offset", 0), device_kw.get("nchains_local", N)
     e.set_state(Z0[off:off + nl])
     return e
+
+
+def module_cut(c, Z0):
+    """the non-finite variants' cut: the largest first coordinate of the start states (the first N archive rows), so that every chain
+    starts at a finite density and proposals beyond it are -inf; the finite variants have none"""
+    return np.inf if c.get("finite", 1) else float(Z0[:c["N"], 0].max())
 
 
 class ThreadExchange:
@@ -133,8 +163,9 @@ class ThreadExchange:
         return cb
 
 
-def run_sharded(G, c):
-    """-> (trace dict with the ranks' columns side by side, archive, crossover state) of W sharded HIP engines"""
+def run_sharded(G, c, variants=None):
+    """-> (trace dict with the ranks' columns side by side, archive, crossover state) of W sharded HIP engines; variants: a list that
+    receives rank 0's last_kernel_variant() after each of the two step calls"""
     import threading
     W, N, n = c["world"], c["N"], c["n"]
     nl = N // W
@@ -148,10 +179,10 @@ def run_sharded(G, c):
             half = n // 2
             e.step(half)
             if r == 0:
-                tally(e.last_kernel_variant())
+                tally(e.last_kernel_variant(), variants)
             e.step(n - half)
             if r == 0:
-                tally(e.last_kernel_variant())
+                tally(e.last_kernel_variant(), variants)
             res[r] = (e.get_trace(0, n), e.get_history(), e.get_cr_state(), e.get_gamma_state(), e.get_state())
             e.close()
         except Exception as ex:
@@ -171,8 +202,10 @@ def run_sharded(G, c):
 KINDS = {}
 
 
-def tally(variant):
+def tally(variant, variants=None):
     """which kind of launch ran last (the summary line says how much of each the drawn configurations reached)"""
+    if variants is not None:
+        variants.append(variant)
     kind = ("ring" if variant.endswith("+ring") else "multi" if "multi>" in variant else "multi-kernel" if variant.startswith("multi-kernel") else
             variant.split("<")[0] if variant else "none")
     KINDS[kind] = KINDS.get(kind, 0) + 1
@@ -181,6 +214,8 @@ def tally(variant):
 def run_one(G, O, c):
     """-> None when the two agree on everything, else a description of the first difference."""
     out = []
+    if c["lk"] in MK.SHAPES:
+        MK.code_object(c["lk"])                                 # (compiled on first use: before any rank thread starts)
     for Cls in (G.Engine, O.Engine):
         if Cls is G.Engine and c.get("world", 1) > 1:
             out.append(run_sharded(G, c))
@@ -229,6 +264,7 @@ def main():
     ap.add_argument("--long", action="store_true", help="three times the generations, populations up to 4096 chains")
     ap.add_argument("--adapt-lag", action="store_true", help="every configuration with an adaptation and an adapt_lag (lockstep, no tempering): the launches that hold several burn-in generations")
     ap.add_argument("--sharded", action="store_true", help="every configuration that can be sharded is (2..4 engines of one process, rows exchanged through the host transport); with --chains 512,1024,2048 the ranks own whole groups of 256 chains")
+    ap.add_argument("--module", action="store_true", help="every configuration with a user kernel of tests/module_kernels.py as the likelihood (its numpy twin on the oracle); N <= 1100, d <= 200")
     ap.add_argument("--dims", default="", help="comma-separated dimensions to draw from instead of the built-in list")
     ap.add_argument("--chains", default="", help="comma-separated chain counts to draw from (also lifts the 256-chain cap of d > 128)")
     args = ap.parse_args()
@@ -239,7 +275,7 @@ def main():
     rng = np.random.default_rng(args.seed)
     t0 = time.time(); bad = 0; done = 0
     for i in range(args.n):
-        c = draw_config(rng, args.long, dims, chains, args.adapt_lag, args.sharded)
+        c = draw_config(rng, args.long, dims, chains, args.adapt_lag, args.sharded, args.module)
         try:
             r = run_one(G, O, c)
         except Exception as ex:                                 # an engine refusing a configuration must refuse it on both sides: report

@@ -1,7 +1,10 @@
 """Networks whose rate constants, start amounts, observable scales and constraints are likelihoods.Monomial products of the sampled
 constants, for the tests of that construct.  A SPEC says everything an independent reference needs (reference_loglike below reads the
 spec alone, never the generated code); build(spec) returns (the object, single(c, constraints=...) -> the single-condition object of
-condition c).  All synthetic: the data of every condition come from scipy's Radau at the nominal point, sd = rel |data| + 0.01."""
+condition c).  All synthetic: the data of every condition come from scipy's Radau at the nominal point, sd = rel |data| + 0.01.
+
+A spec with the key "events" (a list of (time, species, factor, amount) per condition: the *_events specs) combines Monomials with dosing
+and wash-out events; its data and its reference come from Radau restarted at every event (ode_event_networks.piecewise_radau)."""
 import functools
 
 import numpy as np
@@ -28,16 +31,27 @@ def numbers(entries, x):
     return np.array([mono_value(v, x) if isinstance(v, Monomial) else v for v in entries], dtype=float)
 
 
+def events_of(spec, c):
+    """condition c's events (time, species, factor, amount) in a spec that has them (the key "events": a list per condition), else none"""
+    return tuple(spec["events"][c]) if spec.get("events") else ()
+
+
 def radau_observed(spec, c, x, rtol=1e-12, atol=1e-14):
-    """what is compared with condition c's data at the point x, [O, T]: scale * observables of a scipy Radau solution"""
-    y = REF.radau(spec["S"], spec["reactions"], constants(spec["reactions"], x), numbers(spec["y0"][c], x), spec["t"], rtol=rtol, atol=atol)
+    """what is compared with condition c's data at the point x, [O, T]: scale * observables of a scipy Radau solution -- restarted at
+    every event of the condition (ode_event_networks.piecewise_radau: the state changed by hand in between) where the spec has events"""
+    k, y0 = constants(spec["reactions"], x), numbers(spec["y0"][c], x)
+    if events_of(spec, c):
+        from .ode_event_networks import piecewise_radau
+        y = piecewise_radau(spec["S"], spec["reactions"], k, y0, spec["t"], events_of(spec, c), rtol=rtol, atol=atol)
+    else:
+        y = REF.radau(spec["S"], spec["reactions"], k, y0, spec["t"], rtol=rtol, atol=atol)
     scale = np.ones(len(spec["obs"])) if spec["scale"] is None else numbers(spec["scale"], x)
     return (y @ np.asarray(spec["obs"], dtype=float).T).T * scale[:, None]
 
 
 def reference_loglike(spec, data, sd, x):
-    """(the log-likelihood of x, the sum of its terms' magnitudes) from scipy alone: Radau at rtol 1e-10 and norm.logpdf for the data of
-    every condition and for the constraints"""
+    """(the log-likelihood of x, the sum of its terms' magnitudes) from scipy alone: Radau at rtol 1e-10 (restarted at every event of a
+    condition, where the spec gives per-condition events) and norm.logpdf for the data of every condition and for the constraints"""
     from scipy.stats import norm
     total = magnitude = 0.0
     for c in range(len(spec["y0"])):
@@ -111,7 +125,31 @@ def _dense8_m():
                 constraints=[(Monomial({0: 1, 1: 1}), 1.0, 0.5)], nominal=np.zeros(20), rel=None, lanes=1, unobserved=(), single=True)
 
 
-SPECS = {"mm_kd": _mm_kd, "mm_kd_doses": lambda: _mm_kd(False), "enzyme13_m": _enzyme13_m, "chain17_m": _chain17_m, "dense8_m": _dense8_m}
+def _mm_kd_events():
+    """mm_kd with a different event list in each of its three conditions: condition 0 changes the ENZYME -- the species whose start is a
+    Monomial -- at t0 (half of it plus 0.1) and gets a bolus of substrate strictly between the outputs 6.0 and 6.5; condition 1 gets one
+    exactly on the output time 2.0, whose substrate reading is the one left unobserved (NaN); condition 2 (the knock-out) has none, so
+    its block is padded to two events"""
+    spec = _mm_kd()
+    return dict(spec, events=[[(0.0, 0, 0.5, 0.1), (6.2, 1, 1.0, 1.0)], [(float(spec["t"][3]), 1, 1.0, 1.5)], []])
+
+
+def _enzyme13_m_events():
+    """enzyme13_m (16 lanes) with ode_event_networks' 0, 1 and 3 events in its three conditions"""
+    from .ode_event_networks import ENZ_CONDITION_EVENTS
+    return dict(_enzyme13_m(), events=[list(ev) for ev in ENZ_CONDITION_EVENTS])
+
+
+def _chain17_m_events():
+    """chain17_m (32 lanes): no events in its first condition, ode_event_networks' wash-out and set-to-value in the second"""
+    from .ode_event_networks import CHAIN17_EVENTS
+    return dict(_chain17_m(), events=[[], list(CHAIN17_EVENTS)])
+
+
+SPECS = {"mm_kd": _mm_kd, "mm_kd_doses": lambda: _mm_kd(False), "enzyme13_m": _enzyme13_m, "chain17_m": _chain17_m, "dense8_m": _dense8_m,
+         "mm_kd_events": _mm_kd_events,
+         "enzyme13_m_events": _enzyme13_m_events,
+         "chain17_m_events": _chain17_m_events}
 
 
 @functools.lru_cache(maxsize=None)
@@ -135,14 +173,15 @@ def build(name, **kw):
     """(the object of the named network, single): single(c, constraints=True, **kw2) is condition c alone as a single experiment, with
     or without the constraints."""
     spec, data, sd = spec_and_data(name)
-    shared = dict(lanes_per_point=spec["lanes"], scale=spec["scale"], **kw)
+    shared = dict(dict(lanes_per_point=spec["lanes"], scale=spec["scale"]), **kw)
 
     def single(c, constraints=True, **kw2):
+        ev = dict(events=list(events_of(spec, c))) if spec.get("events") else {}
         return MassActionODELogLike(spec["S"], spec["reactions"], spec["y0"][c], spec["t"], spec["obs"], data[c], sd[c],
-                                    constraints=spec["constraints"] if constraints else None, **dict(shared, **kw2))
+                                    constraints=spec["constraints"] if constraints else None, **dict(shared, **ev, **kw2))
     if spec.get("single"):
         return single(0), single
-    conds = [dict(y0=spec["y0"][c], data=data[c], sd=sd[c]) for c in range(len(spec["y0"]))]
+    conds = [dict(y0=spec["y0"][c], data=data[c], sd=sd[c], **(dict(events=list(events_of(spec, c))) if spec.get("events") else {})) for c in range(len(spec["y0"]))]
     return MassActionODELogLike(spec["S"], spec["reactions"], None, spec["t"], spec["obs"], None, None, conditions=conds,
                                 constraints=spec["constraints"], **shared), single
 
