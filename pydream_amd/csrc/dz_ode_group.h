@@ -1,12 +1,16 @@
-// dz_ode_group.h -- dz_ode.h's solver for networks of 9..32 species: a GROUP of L = 16 or 32 lanes integrates one point together
-// (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32)).  The method is dz_ode.h's, and so is the code: its stepping loop
+// dz_ode_group.h -- dz_ode.h's solver for networks of 9..64 species: several lanes integrate one point together.  Two shapes:
+//     Group<Net, 16 | 32>   a GROUP of L = 16 or 32 lanes per point, for up to 32 species (likelihoods.MassActionODELogLike(...,
+//                           lanes_per_point=16 | 32)); a group never straddles a wave;
+//     Group<Net, 64>        a whole 64-lane WAVE per point, for 33..64 species (lanes_per_point=64): see "a wave per point" below.
+// The method is dz_ode.h's, and so is the code: its stepping loop
 // (dzode::integrate: step controller, negativity rule, max_steps per output interval, exact landing on the output times, events, -inf on
-// any failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L; a group never straddles a wave) owns
+// any failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L) owns
 //     row r of W = I / (h gamma) - J in registers (S doubles, constant column indices after unrolling),
 //     entry r of y, of the stage argument u and of k1..k6,
 //     one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled by S group broadcasts per stage);
-// lanes r >= S idle: they carry zeros, never pivot, and are masked out of every reduction.  The rate constants (up to 128) are computed
-// once per point, reaction j by lane j % L, and kept in static LDS (256 / L points x (R + 1) doubles per block).
+// lanes r >= S idle: they carry zeros, never pivot, and are masked out of every reduction.  The rate constants (up to 128; 256 for a wave
+// per point) are computed once per point, reaction j by lane j % L, and kept in static LDS (256 / L points x (R + 1) doubles per block).
+// A wave per point keeps the row in registers too, but the replicated state in LDS and its broadcasts in scalar registers.
 //
 // Linear algebra over the group (ds_bpermute through __shfl / __shfl_xor with width L; no LDS round trip, no MFMA: a pivoted f64 LU of
 // S <= 32 is a chain of S dependent column steps, latency- and not throughput-bound):
@@ -314,6 +318,211 @@ struct Group {
         y = r == species ? factor * y + amount : y;
     }
 };
+
+// ---------------------------------------------------------------- a wave per point: 33..64 species
+// The same method, pivot rule, column-oriented solves, summation tree and roundings as above, with L = 64: HostGroup<Net, 64> is its twin.
+// What changes is where things live, because a row of 64 doubles (128 registers) and a replicated state beside it do not fit 512:
+//     row r of W                      in lane r's registers, as above;
+//     the replicated state            in LDS, S doubles per wave behind the wave's rate constants (wave_state): lane r writes entry r,
+//                                     every lane reads entry q at a constant q -- one address per read, a broadcast without a bank conflict.
+//                                     Only this wave touches them, so a wave-scope fence orders the write and the reads; there is NO
+//                                     block barrier anywhere in or after the step loop (the four waves of a block take different numbers
+//                                     of steps);
+//     pivot reciprocal, pivot row,    the pivot index is the same in every lane of the wave (the butterfly arg-max is over a total
+//     b[piv[k]] in the solves         order), so it goes to a scalar register (readfirstlane) and the value is read with v_readlane into
+//                                     scalar registers: no LDS-crossbar round trip on the dependent chain, and piv[] costs no VGPR.
+// The arg-max, the sums and the ballots span the wave and need no mask.
+template <>
+struct Lanes<64> {
+    // lane src of this wave; src must hold the same value in every lane (it is read from the first active one)
+    __device__ __forceinline__ static int from(int v, int src) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src)); }
+    __device__ __forceinline__ static double from(double v, int src)
+    {
+        const int s = __builtin_amdgcn_readfirstlane(src);
+        const uint64_t b = d2bits(v);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, s), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), s);
+        return bits2d(((uint64_t)hi << 32) | lo);
+    }
+    __device__ __forceinline__ static double sum(double v)
+    {
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+        return v;
+    }
+    __device__ __forceinline__ static bool any(bool p) { return __ballot(p) != 0; }
+};
+
+// A wave-uniform index in a scalar register the compiler cannot trace back (the scalar twin of row_index).
+__device__ __forceinline__ int uniform_index(int v)
+{
+    v = __builtin_amdgcn_readfirstlane(v);
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+// The wave's copy of the state in LDS, behind its R + 1 rate constants.
+template <class Net>
+__device__ __forceinline__ double* wave_state(double* ks) { return ks + Net::R + 1; }
+
+// Lane r's entry into the wave's copy.  The fences keep the compiler from moving the reads of the previous copy below the write and the
+// reads of this copy above it; the hardware executes one wave's LDS operations in order.
+template <int S>
+__device__ __forceinline__ void wave_publish(double* ys, int r, double v)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (r < S) ys[r] = v;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+constexpr int WAVE_LU_AHEAD = 8;          // columns of one rank-1 update whose pivot-row broadcasts may be in flight together
+
+template <int S>
+__device__ __forceinline__ bool wave_lu_factor(double* w, int* piv, int& pos, int r)
+{
+    bool ok = true, done = r >= S;
+    pos = -1;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        double key = done ? -1.0 : pivot_key(w[k]);
+        int p = r;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const double okey = __shfl_xor(key, m, 64);
+            const int op = __shfl_xor(p, m, 64);
+            const bool take = (okey > key) | ((okey == key) & (op < p));
+            key = take ? okey : key;
+            p = take ? op : p;
+        }
+        int ps = __builtin_amdgcn_readfirstlane(p);          // every lane holds the same p: the arg-max of a total order over the whole wave
+        piv[k >> 2] = (k & 3) ? piv[k >> 2] | (ps << (8 * (k & 3))) : ps;
+        ok = ok && key != 0.0;
+        const bool me = ps == r, upd = !done && !me;
+        const double inv = Lanes<64>::from(1.0 / w[k], ps);
+        double l = w[k] * inv;
+        w[k] = me ? inv : (upd ? l : w[k]);
+#pragma unroll
+        for (int c = k + 1; c < S; ++c) {
+            // every WAVE_LU_AHEAD columns the last updated entry, the multiplier and the pivot's lane pass through an empty asm statement
+            // together: the next columns' readlanes depend on it and are not all issued (into scalar registers) ahead of the updates
+            if ((c - k - 1) % WAVE_LU_AHEAD == 0 && c > k + 1) asm volatile("" : "+v"(w[c - 1]), "+v"(l), "+s"(ps));
+            const double pc = Lanes<64>::from(w[c], ps);
+            w[c] = upd ? w[c] - l * pc : w[c];
+        }
+        done = done || me;
+        pos = me ? k : pos;
+    }
+    return ok;
+}
+
+template <int S>
+__device__ __forceinline__ double wave_lu_solve(const double* w, const int* pivp, int pos, int r, double b)
+{
+    int piv[(S + 3) / 4];          // (opaque copies, as in group_lu_solve; here in scalar registers)
+#pragma unroll
+    for (int i = 0; i < (S + 3) / 4; ++i) piv[i] = uniform_index(pivp[i]);
+    pos = row_index(pos);
+    r = row_index(r);
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const double bk = Lanes<64>::from(b, pivot_row(piv, k));
+        b = pos > k ? b - w[k] * bk : b;
+    }
+    double x = 0.0;
+#pragma unroll
+    for (int k = S - 1; k >= 0; --k) {
+        const double xk = Lanes<64>::from(b * w[k], pivot_row(piv, k));
+        b = (pos >= 0 && pos < k) ? b - w[k] * xk : b;
+        x = r == k ? xk : x;
+    }
+    return x;
+}
+
+// group_step with the replicated state in LDS (ys) and the wave's LU.
+template <class Net>
+__device__ __forceinline__ bool wave_step(const double* ks, double* ys, double y, double h, double rtol, double atol, int r, double& ynew, double& err2)
+{
+    constexpr int S = Net::S;
+    double w[S];
+    int piv[(S + 3) / 4], pos;
+    const double fac = 1.0 / (h * Rodas4::gamma), ih = 1.0 / h;
+    wave_publish<S>(ys, r, y);
+    int rj = row_index(r), zk = row_index(0);
+    JacobianRow<Net, S>::fill(w, rj, zk, ks, ys, r, fac);
+    const bool ok = wave_lu_factor<S>(w, piv, pos, r);
+    double k1 = 0.0, k2 = 0.0, k3 = 0.0, k4 = 0.0, k5 = 0.0, f = 0.0, arg = y;
+#pragma unroll 1
+    for (int st = 0; st < 6; ++st) {
+        arg = stage_arg(st, y, arg, k1, k2, k3, k4, k5);
+        wave_publish<S>(ys, r, arg);
+        f = Net::rhs_row(row_index(r), ks + row_index(0), ys);
+        if (st > 0) f = f + stage_add(st, ih, k1, k2, k3, k4, k5);
+        f = wave_lu_solve<S>(w, piv, pos, r, f);
+        k1 = st == 0 ? f : k1;
+        k2 = st == 1 ? f : k2;
+        k3 = st == 2 ? f : k3;
+        k4 = st == 3 ? f : k4;
+        k5 = st == 4 ? f : k5;
+    }
+    ynew = arg + f;
+    const double sk = atol + rtol * dmax(dabs(y), dabs(ynew));
+    const double q = f / sk;
+    err2 = Lanes<64>::sum(r < S ? q * q : 0.0) * (1.0 / S);
+    return ok;
+}
+
+template <class Net>
+__device__ __forceinline__ double wave_start_step(const double* ks, double* ys, double y, double rtol, double atol, double span, int r)
+{
+    constexpr int S = Net::S;
+    wave_publish<S>(ys, r, y);
+    const double f0 = Net::rhs_row(row_index(r), ks, ys);
+    const double d0 = group_wnorm2<S, 64>(y, y, rtol, atol, r), d1 = group_wnorm2<S, 64>(f0, y, rtol, atol, r);
+    const double h0 = start_h0(d0, d1, span);
+    wave_publish<S>(ys, r, y + h0 * f0);
+    const double f1 = Net::rhs_row(row_index(r), ks, ys) - f0;
+    return start_h(h0, d1, group_wnorm2<S, 64>(f1, y, rtol, atol, r), span);
+}
+
+// The wave's shape for dz_ode.h's integrate: Group's members on the functions above.  ks: the wave's row of LDS, R + 1 rate constants
+// and S doubles of state (group_lds_row); a wave that is not live takes no step and touches nothing but its own row.
+template <class Net>
+struct Group<Net, 64> {
+    static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
+    typedef double State;
+    double* ks;
+    int r;
+    const double* x;
+    __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? start_amount<Net>(r, x, blk[6 + r]) : 0.0; }
+    __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
+    {
+        return wave_start_step<Net>(ks, wave_state<Net>(ks), y, rtol, atol, span, r);
+    }
+    __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
+    {
+        return wave_step<Net>(ks, wave_state<Net>(ks), y, h, rtol, atol, r, yn, err2);
+    }
+    __device__ __forceinline__ bool all_finite(double yn, bool fin) const { return fin && !Lanes<64>::any(!finite(yn)); }
+    __device__ __forceinline__ bool any_negative(double yn, double y, double rtol, double atol) const
+    {
+        return Lanes<64>::any(yn < -(atol + rtol * dabs(y)));
+    }
+    __device__ __forceinline__ void observe(double y, double* o) const
+    {
+        double* ys = wave_state<Net>(ks);
+        wave_publish<S>(ys, r, y);
+        observe_scaled<Net>(x, ys, o);
+    }
+    __device__ __forceinline__ void apply(double& y, int species, double factor, double amount) const
+    {
+        y = r == species ? factor * y + amount : y;
+    }
+};
+
+// The doubles of static LDS a point's lanes share: R + 1 rate constants, and for a wave per point the S doubles of its state behind them.
+template <class Net, int L>
+constexpr int group_lds_row() { return Net::R + 1 + (L == 64 ? Net::S : 0); }
 #endif
 
 #if !defined(__HIP__)
@@ -443,9 +652,9 @@ struct HostGroup {
 
 }  // namespace dzode
 
-// The entry points around a generated network struct NET for groups of LANES lanes: the batch kernel the engine's multi-kernel path
+// The entry points around a generated network struct NET for groups of LANES = 16, 32 or 64 lanes: the batch kernel the engine's multi-kernel path
 // launches (dz_set_likelihood_module with lanes_per_point LANES: 256 threads per block, point i on lanes [i * LANES, (i + 1) * LANES) of
-// the grid) and the host build's C functions under dz_ode.h's names.  A group whose point index is >= n reads the last point's row,
+// the grid; with 64 lanes: 4 points per block, one per wave) and the host build's C functions under dz_ode.h's names.  A group whose point index is >= n reads the last point's row,
 // takes no step and stores nothing: it stays with its wave through every cross-lane operation.
 #if defined(__HIP__)
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
@@ -453,7 +662,8 @@ struct HostGroup {
                                                                         const void* data)                                              \
     {                                                                                                                                    \
         static_assert(NET::S <= LANES, "a lane per species");                                                                            \
-        __shared__ double ks[256 / LANES][NET::R + 1];         /* (+ 1: the groups of a wave read the same j from different banks) */    \
+        __shared__ double ks[256 / LANES][dzode::group_lds_row<NET, LANES>()];        /* (R + 1: the groups of a wave read the same j    \
+                                                                                         from different banks; 64 lanes: + the state) */ \
         const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
         const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
         const bool valid = i < n;                                                                                                        \
@@ -470,7 +680,7 @@ struct HostGroup {
                                                                              const void* data)                                         \
     {                                                                                                                                    \
         static_assert(NET::S <= LANES, "a lane per species");                                                                            \
-        __shared__ double ks[256 / LANES][NET::R + 1];                                                                                   \
+        __shared__ double ks[256 / LANES][dzode::group_lds_row<NET, LANES>()];                                                           \
         const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
         const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
         const bool valid = w < n;                                                                                                        \

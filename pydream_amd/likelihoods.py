@@ -360,6 +360,7 @@ class DeviceKernelLogLike:
 # ---------------------------------------------------------------------------------------------------- mass-action ODE models
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
 ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
+ODE_WAVE_LIMITS = dict(species=64, reactions=256, observables=16, times=4096, lanes=(64,), conditions=64)            # lanes_per_point=64: 33..64 species
 ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
 ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
@@ -605,7 +606,7 @@ def _ode_source(S, reactions, observables, log10, items=False, mono=None, events
 
 
 def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None, events=0):
-    """The generated network struct for the lane-group solver (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
+    """The generated network struct for the lane-group solver and, with lanes=64, the wave-per-point one (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
     its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
     stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
     diverge inside the right-hand side.  Every f[r] and J[r][q] is the sum over the reactions (for J: those with q among the reactants)
@@ -687,6 +688,13 @@ class MassActionODELogLike:
     state), the same data block, the same host-build contract (the host twin of the group solver gives the device's bits); the two
     shapes round differently, so their values on a network both can run agree to the integration tolerance, not to the bit.
 
+    lanes_per_point=64 gives a point a whole 64-lane WAVE, for networks of 33..64 species (a smaller network is refused: 16 or 32 lanes
+    are its shape), with up to 256 reactions and 16 observables (ODE_WAVE_LIMITS).  The method, the pivot rule, the order of every sum
+    and so the bits are the lane group's at L = 64 -- the host twin is the same plain loop --; what differs is where things live
+    (csrc/dz_ode_group.h, "a wave per point"): a lane keeps its matrix row in registers, the state the right-hand side reads is in LDS
+    (S doubles per wave), and pivot rows travel through scalar registers.  Four points to a block of 256 threads; conditions,
+    Monomials and events work as below.
+
     conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
     (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events"; a missing key is the constructor's own argument,
     which (y0, data, sd) may be None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
@@ -733,11 +741,14 @@ class MassActionODELogLike:
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None):
         S = int(n_species)
         lanes = int(lanes_per_point)
-        if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"]:
-            raise ValueError("MassActionODELogLike: lanes_per_point must be 1, 16 or 32 (got %r)" % (lanes_per_point,))
-        lim = ODE_LIMITS if lanes == 1 else dict(ODE_GROUP_LIMITS, species=lanes)
+        if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"] + ODE_WAVE_LIMITS["lanes"]:
+            raise ValueError("MassActionODELogLike: lanes_per_point must be 1, 16, 32 or 64 (got %r)" % (lanes_per_point,))
+        lim = ODE_LIMITS if lanes == 1 else ODE_WAVE_LIMITS if lanes in ODE_WAVE_LIMITS["lanes"] else dict(ODE_GROUP_LIMITS, species=lanes)
         if not 1 <= S <= lim["species"]:
             raise ValueError("MassActionODELogLike: n_species must be 1..%d (got %d)" % (lim["species"], S))
+        if lim is ODE_WAVE_LIMITS and S <= ODE_GROUP_LIMITS["species"]:          # (half the wave would idle)
+            raise ValueError("MassActionODELogLike: lanes_per_point=%d is for networks of %d..%d species; use 16 or 32 (got %d species)"
+                             % (lanes, ODE_GROUP_LIMITS["species"] + 1, lim["species"], S))
         if not 1 <= len(reactions) <= lim["reactions"]:
             raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (lim["reactions"], len(reactions)))
         if rate_scale not in ("log10", "linear"):

@@ -9,8 +9,8 @@
   * run_dream generations/s with the likelihood on the device against the host path with 16 worker processes
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
-    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|binding_cycle] [--lanes 1|16|32]
-                                  [--conditions C [--events E]]
+    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle]
+                                  [--lanes 1|16|32|64] [--conditions C [--events E]] [--host-twin]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -22,6 +22,15 @@ conditions with E events in each (at equal distances inside the time span, on th
 topped up by half its start amount, in turn) against the same C conditions without events, alternately, the median of 7 rounds of 10
 calls each and the rounds' spread; proposals/s and the host build's steps per point for both.  --events 0 times the event-less object
 alone and never names the keyword (so the same script runs on a checkout from before the keyword existed).  Kernel only.
+
+--host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
+long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
+calls each and the rounds' spread; the host build ONCE, the points split over DREAMZS_HOST_WORKERS processes (default 16), each in one
+call of batch(return_steps=True): that pass also gives the values the device's are compared with, bit for bit, and the steps.  Kernel only.
+
+chain64: tests/ode_wide_networks' chain of 64 species, cascade: pydream_amd/examples/cascade (49 species), both a wave per point
+(--lanes 64, their only shape).  --network chain32 --lanes 64 builds chain32 through the wave shape although the class refuses that
+(half the wave idles): an internal build of this tool, to see what a whole wave per point costs where half a wave would do.
 
 mm: tests/ode_networks' Michaelis-Menten network (4 species), imported from the test package like chain8, chain32: the chains of tests/ode_wide_networks.py, imported from the test package (run from a checkout; their data come from
 scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
@@ -82,8 +91,19 @@ def network(name, lanes):
         assert lanes in (None, 1), "mm is a one-lane network"
         from tests import ode_networks as NW
         return NW.michaelis_menten(), NW.MM_NOMINAL, 1.0
+    if name == "cascade":
+        assert lanes in (None, 64), "cascade is a wave-per-point example"
+        from pydream_amd.examples.cascade import cascade_device as CAS
+        return CAS.make_likelihood(), CAS.NOMINAL, CAS.WIDTH
     from tests import ode_wide_networks as W
-    S = dict(chain8=8, chain32=32)[name]
+    S = dict(chain8=8, chain32=32, chain64=64)[name]
+    if S == 64:
+        assert lanes in (None, 64), "chain64 needs a wave per point"
+        return W.chain(64, 64), W.CHAIN_NOMINAL, 1.0
+    if S == 32 and lanes == 64:                                 # (not through the constructor, which refuses it: see the head)
+        like = W.chain(32, 32)
+        like.lanes_per_point, like.path, like._host = 64, None, None
+        return like, W.CHAIN_NOMINAL, 1.0
     if (lanes or (1 if S == 8 else 32)) == 1:                   # the same network and data through the one-lane kernel
         from pydream_amd.likelihoods import MassActionODELogLike
         grp = W.chain(S, 16)
@@ -190,6 +210,50 @@ def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10):
     return out
 
 
+def _host_part(args):
+    like, part = args
+    return like.batch(part, return_steps=True)
+
+
+def host_twin_rate(N, k, name, lanes, rounds=7, reps=10):
+    import multiprocessing
+    from pydream_amd import _capi
+    like, nominal, width = network(name, lanes)
+    n, d = N * k, len(nominal)
+    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
+    like.host_library()                                                 # (compiled before anything is timed or forked)
+    workers = int(os.environ.get("DREAMZS_HOST_WORKERS", "16"))
+    # (the host pass first: its workers are forked before this process opens the device)
+    with multiprocessing.get_context("fork").Pool(workers) as pool:
+        pool.map(_host_part, [(like, X[:1])] * workers)                 # (every worker has loaded the library)
+        t0 = time.perf_counter()
+        parts = pool.map(_host_part, [(like, part) for part in np.array_split(X, workers)])
+        host_s = time.perf_counter() - t0
+    host, steps = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
+    eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
+    like._dz_apply(eng)
+    for _ in range(3):
+        lk = eng.eval_logp(X)[1]
+    assert lk.tobytes() == host.tobytes(), "device and host builds differ"
+    t = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            eng.eval_logp(X)
+        t.append((time.perf_counter() - t0) / reps * 1e6)
+    us = float(np.median(t))
+    per_wave = 64 // like.lanes_per_point
+    w = steps[: n // per_wave * per_wave].reshape(-1, per_wave)
+    out = dict(network=name, lanes=like.lanes_per_point, species=like.n_species, reactions=len(like.reactions), chains=N, tries=k, points=n,
+               us_per_launch=round(us, 1), us_per_launch_min_max=[round(min(t), 1), round(max(t), 1)], points_per_s=round(n / us * 1e6),
+               steps_median=float(np.median(steps)), steps_max=int(steps.max()),
+               lane_efficiency=round(float(w.sum() / (per_wave * np.maximum(w.max(axis=1), 1)).sum()), 3), failed_points=int(np.sum(lk == -np.inf)),
+               host_workers=workers, host_pass_s=round(host_s, 2), host_points_per_s=round(n / host_s), device_over_host=round(host_s / (us * 1e-6), 1))
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def gens_per_s(like, N, k, G, host_workers=None, nominal=ROB.NOMINAL, width=3.0):
     """generations/s of run_dream from the difference of a G-generation and a 2G-generation run (setup and compilation cancel)"""
     from scipy.stats import uniform
@@ -256,6 +320,10 @@ if __name__ == "__main__":
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
+    if "--host-twin" in argv:
+        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
+        host_twin_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None)
+        sys.exit(0)
     if "--events" in opt:
         assert "--conditions" in opt, "--events goes with --conditions C"
         nums = [int(a) for a in argv[:2] if not a.startswith("--")]
