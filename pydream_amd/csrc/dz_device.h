@@ -127,78 +127,107 @@ DZ_DEV double kd(double c)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// a * b + c with such a constant c as the addend, read straight from its scalar register pair (one v_fma_f64; written as fma(a, b,
-// kd(c)) the compiler copies the pair into vector registers first and uses v_fmac: three vector instructions per Horner step)
-DZ_DEV double fma_k(double a, double b, double c)
+// DZ_HORNER10_K(p, r, c1, .., c10): ten Horner steps p = p r + c_i with such constants as the addends, each read straight from a scalar
+// register pair by ONE v_fma_f64 (written as fma(p, r, kd(c)) the compiler copies the pair into vector registers first and uses v_fmac:
+// three vector instructions per step).
+//
+// The whole chain is ONE asm statement and the pair is vcc: two scalar moves and the fma per step, nothing else.  With a statement per
+// step the hazard recognizer, which cannot see into a statement, puts an s_nop between every two of them (it has to assume the first
+// one's vector result is forwarded with a destination select): four issued instructions per step.  A scalar move followed by a vector
+// read of its result is no hazard on gfx950, an fma that reads the previous fma's result is none either, and inside one statement
+// nothing is inserted.  The pair has to be named in the text (an asm operand of 64 bits has no syntax for its halves); vcc is the pair
+// a Horner chain has no other use for.  The coefficients are immediates of the statement: they cannot be hoisted out of the generation
+// loop, and no vector copy of them exists.  dexp and dlog both have ten such steps.
+// DZ_NO_FMAK: the plain form, fma(p, r, kd(c)) ten times -- the same value, the reference for this one.
+constexpr unsigned long long kbits(double c) { return __builtin_bit_cast(unsigned long long, c); }
+#define DZ_KSTEP(lo, hi) "s_mov_b32 vcc_lo, %" #lo "\n\ts_mov_b32 vcc_hi, %" #hi "\n\tv_fma_f64 %0, %0, %1, vcc\n\t"
+template <unsigned long long C1, unsigned long long C2, unsigned long long C3, unsigned long long C4, unsigned long long C5,
+          unsigned long long C6, unsigned long long C7, unsigned long long C8, unsigned long long C9, unsigned long long C10>
+DZ_DEV double horner10_kbits(double p, double r)
 {
-#ifdef DZ_NO_FMAK
-    return fma(a, b, kd(c));
-#endif
-    unsigned lo = (unsigned)((unsigned long long)__double_as_longlong(c) & 0xffffffffull), hi = (unsigned)((unsigned long long)__double_as_longlong(c) >> 32);
-    asm volatile("" : "+s"(lo), "+s"(hi));
-    const unsigned long long cb = ((unsigned long long)hi << 32) | lo;
-    double r;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(cb));
-    return r;
+#define DZ_KOPS(C) "n"((unsigned)((C) & 0xffffffffull)), "n"((unsigned)((C) >> 32))
+    asm(DZ_KSTEP(2, 3) DZ_KSTEP(4, 5) DZ_KSTEP(6, 7) DZ_KSTEP(8, 9) DZ_KSTEP(10, 11) DZ_KSTEP(12, 13) DZ_KSTEP(14, 15) DZ_KSTEP(16, 17)
+        DZ_KSTEP(18, 19) DZ_KSTEP(20, 21)
+        : "+&v"(p)
+        : "v"(r), DZ_KOPS(C1), DZ_KOPS(C2), DZ_KOPS(C3), DZ_KOPS(C4), DZ_KOPS(C5), DZ_KOPS(C6), DZ_KOPS(C7), DZ_KOPS(C8), DZ_KOPS(C9), DZ_KOPS(C10)
+        : "vcc");
+#undef DZ_KOPS
+    return p;
 }
+#undef DZ_KSTEP
+#ifdef DZ_NO_FMAK
+#define DZ_HORNER10_K(p, r, c1, c2, c3, c4, c5, c6, c7, c8, c9, c10)                                                                          \
+    fma(fma(fma(fma(fma(fma(fma(fma(fma(fma((p), (r), ::dz::kd(c1)), (r), ::dz::kd(c2)), (r), ::dz::kd(c3)), (r), ::dz::kd(c4)), (r), ::dz::kd(c5)), \
+        (r), ::dz::kd(c6)), (r), ::dz::kd(c7)), (r), ::dz::kd(c8)), (r), ::dz::kd(c9)), (r), ::dz::kd(c10))
+#else
+#define DZ_HORNER10_K(p, r, c1, c2, c3, c4, c5, c6, c7, c8, c9, c10)                                                                          \
+    (::dz::horner10_kbits<::dz::kbits(c1), ::dz::kbits(c2), ::dz::kbits(c3), ::dz::kbits(c4), ::dz::kbits(c5), ::dz::kbits(c6), ::dz::kbits(c7), \
+                          ::dz::kbits(c8), ::dz::kbits(c9), ::dz::kbits(c10)>((p), (r)))      // (c1..c10: constant expressions)
+#endif
 
+DZ_DEV double make_f64(unsigned hi, unsigned lo) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
+
+// dexp and dlog have no divergent region: the main path runs in every lane, for every input, and what is left of the special cases is
+// a select on its result.  (As early returns each case was an s_and_saveexec / s_cbranch_execz / s_or exec triple, nested three deep
+// around the multi-try selection's dexp, for inputs that are ordinary finite numbers in every lane that matters.)  Same value for every
+// binary64 input; the reasons stand at each step.  The selects take nothing but the argument, +-0, and two constants the kernels hold
+// anyway: a select against a 32-bit literal costs a vector register for the whole kernel, and the headline kernel has none to spare.
+//
+// dexp: the argument is clamped to [-746, 709.79] and the main path does the rest.
+//   x > 709.782712893384 (was: +inf).  The clamped argument lies in (709.7827.., 709.79]: kf = 1024, the factor 2^kf is the bit pattern
+//     of +inf, and p = exp(r) with 0 < r < 0.008 is positive: +inf.
+//   x < -745.2 (was: +0).  The clamped argument lies in [-746, -745.2) and kf is -1075 or -1076.  With kf = -1075, r = x + 1075 ln2 < -0.06, so
+//     0 < p < 1 and p 2^-1075 < 2^-1075; with kf = -1076, |r| < 0.35, so 0 < p < 2 and p 2^-1076 < 2^-1075.  That is less than half the
+//     smallest subnormal either way: the second product (the only one that rounds) gives +0.
+//   NaN: fmax returns its other operand, the main path runs on -746, and the select at the end returns x itself (v_cndmask moves bits:
+//     payload, sign and signalling bit as before).
+//   Everything between is not touched by the clamp and runs the sequence it always ran.  After the clamp kf is a whole number in
+//   [-1076, 1024] in every lane, so the conversion to int is defined everywhere.
 DZ_DEV double dexp(double x)
 {
-    if (x != x) return x;
-    if (x > 709.782712893384) return __builtin_huge_val();
-    if (x < -745.2) return 0.0;
-    const double kf = floor(x * 1.4426950408889634 + 0.5);
-    double r = fma(-kf, DZ_LN2_HI, x);
+    const double xc = fmin(fmax(x, -746.0), 709.79);
+    const double kf = floor(xc * 1.4426950408889634 + 0.5);
+    double r = fma(-kf, DZ_LN2_HI, xc);
     r = fma(-kf, DZ_LN2_LO, r);
     double p = kd(1.0 / 6227020800.0);
-    p = fma_k(p, r, 1.0 / 479001600.0);
-    p = fma_k(p, r, 1.0 / 39916800.0);
-    p = fma_k(p, r, 1.0 / 3628800.0);
-    p = fma_k(p, r, 1.0 / 362880.0);
-    p = fma_k(p, r, 1.0 / 40320.0);
-    p = fma_k(p, r, 1.0 / 5040.0);
-    p = fma_k(p, r, 1.0 / 720.0);
-    p = fma_k(p, r, 1.0 / 120.0);
-    p = fma_k(p, r, 1.0 / 24.0);
-    p = fma_k(p, r, 1.0 / 6.0);
+    p = DZ_HORNER10_K(p, r, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0,
+                      1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0);
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    int k = (int)kf;
-    if (k < -1000) { p = p * __longlong_as_double((long long)(1023 - 1000) << 52); k += 1000; }
-    return p * __longlong_as_double((long long)(k + 1023) << 52);
+    // 2^k in two factors, 2^max(k, -1000) and 2^(k - max(k, -1000)): for k >= -1000 the second is 1.0 and changes nothing; below (2^k has no
+    // normal representation there) p 2^-1000 is exact and the second product rounds once -- the two steps `if (k < -1000)` made.
+    // k = 1024: the first factor is the bit pattern of +inf, as it always was.
+    const int k = (int)kf, k1 = max(k, -1000);
+    const double v = (p * make_f64((unsigned)(k1 + 1023) << 20, 0u)) * make_f64((unsigned)(k - k1 + 1023) << 20, 0u);
+    return x != x ? x : v;
 }
 
+// dlog: mantissa and exponent come from the hardware's frexp pair, which handles subnormals itself (was: a branch that scaled by 2^54 --
+//   exact, so the same mantissa bits and the same exponent), and m > sqrt 2 is settled by arithmetic: with fm = m / 2 in [1/2, 1) what
+//   the branch made is fm itself above sqrt(2)/2 and 2 fm below (both exact), the exponent one lower in the second case.
+//   Everything but a positive normal or subnormal number gets its value from the selects at the end: NaN -> itself (bits moved), +inf ->
+//   itself, below zero (-inf too) -> the default NaN, +-0 -> -inf.  For those the main path computes on whatever frexp returns (the
+//   argument itself for NaN and inf, 0 for 0); nothing in it is undefined for any input.
 DZ_DEV double dlog(double x)
 {
-    if (x != x) return x;
-    if (x < 0.0) return __builtin_nan("");
-    if (x == 0.0) return -__builtin_huge_val();
-    if (x == __builtin_huge_val()) return x;
-    int e = 0;
-    unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    if ((b >> 52) == 0) { x = x * 18014398509481984.0; e = -54; b = (unsigned long long)__double_as_longlong(x); }
-    e += (int)(b >> 52) - 1023;
-    double m = __longlong_as_double((long long)((b & 0x000fffffffffffffull) | 0x3ff0000000000000ull));
-    if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
+    const double fm = __builtin_amdgcn_frexp_mant(x);
+    const int dbl = fm > 0.5 * 1.4142135623730951 ? 0 : 1;
+    const double m = __builtin_ldexp(fm, dbl);
+    const int e = __builtin_amdgcn_frexp_exp(x) - dbl;
     const double f = m - 1.0;
     const double s = f / (2.0 + f);
     const double z = s * s;
     double p = kd(1.0 / 23.0);
-    p = fma_k(p, z, 1.0 / 21.0);
-    p = fma_k(p, z, 1.0 / 19.0);
-    p = fma_k(p, z, 1.0 / 17.0);
-    p = fma_k(p, z, 1.0 / 15.0);
-    p = fma_k(p, z, 1.0 / 13.0);
-    p = fma_k(p, z, 1.0 / 11.0);
-    p = fma_k(p, z, 1.0 / 9.0);
-    p = fma_k(p, z, 1.0 / 7.0);
-    p = fma_k(p, z, 1.0 / 5.0);
-    p = fma_k(p, z, 1.0 / 3.0);
+    p = DZ_HORNER10_K(p, z, 1.0 / 21.0, 1.0 / 19.0, 1.0 / 17.0, 1.0 / 15.0, 1.0 / 13.0, 1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0, 1.0 / 5.0, 1.0 / 3.0);
     const double t = 2.0 * s;
     const double lm = fma(t * z, p, t);
     const double ef = (double)e;
-    return fma(ef, DZ_LN2_HI, fma(ef, DZ_LN2_LO, lm));
+    const double v = fma(ef, DZ_LN2_HI, fma(ef, DZ_LN2_LO, lm));
+    double sp = x;
+    sp = x < 0.0 ? __builtin_nan("") : sp;
+    sp = x == 0.0 ? -__builtin_huge_val() : sp;
+    return __builtin_amdgcn_class(x, 0x180) ? v : sp;      // 0x180: +subnormal | +normal
 }
 
 DZ_DEV double nan_to_num(double x)
@@ -309,6 +338,41 @@ DZ_DEV double readlane_f64(double v, int ln)
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), ln), hi = __builtin_amdgcn_readlane((int)(b >> 32), ln);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// The value of the lane S places lower in the same row of 16 lanes (DPP row_shr:S); the S lowest lanes of each row read +0.0
+// (bound_ctrl: a source outside the row gives 0, in both halves).
+template <int S>
+DZ_DEV double row_shr_zero(double v)
+{
+    static_assert(S >= 1 && S <= 15, "a shift inside a row of 16 lanes");
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), 0x110 + S, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x110 + S, 0xf, 0xf, true);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// Ordered prefix sum inside each row of 16 lanes: lane i < K of a row ends with ((((+0.0 + w_0) + w_1) + w_2) ... + w_i), w_j the value of
+// the row's lane j -- the sequential left-to-right sum the reduction contract prescribes, bit for bit what
+// `S = 0.0; for (j = 0; j <= i; ++j) S = S + w_j` makes, the +0.0 + w_0 = +0.0 of w_0 = -0.0 included.
+//
+// K - 1 shifted copies of w (two 32-bit DPP moves each) and K additions; no scalar round trip and no hazard nop: every DPP move reads
+// w itself, never the running sum, so the wait states between a vector write and a DPP read of the same register are paid once, if
+// at all, and not per step.  (Shifting the RUNNING value one lane up per step costs s_nop 1 in front of every step.)
+// Why it is the sequential sum: every lane adds, in this order, the copies shifted by K-1, K-2, .., 1 and then w itself.  In lane i the
+// copy shifted by s holds w_(i-s) for s <= i and +0.0 for s > i.  So lane i adds +0.0 to its +0.0 as long as s > i -- which leaves
+// +0.0 -- and then w_0 (at s = i), w_1, .., w_i in turn, each to the sum of those before: the sequence above.  A lane's sum depends on
+// K only through the number of leading +0.0 terms, so a larger K re-adds nothing and lanes i < K hold the same bits for every K > i.
+// Lanes i >= K of a row hold the sum of w_(i-K+1) .. w_i: not a prefix, not used.
+template <int S>      // c + the copies of w shifted by S, S-1, .., 1, added in that order
+DZ_DEV double row_prefix_shifted(double c, double w)
+{
+    if constexpr (S >= 1) return row_prefix_shifted<S - 1>(c + row_shr_zero<S>(w), w);
+    else return c;
+}
+template <int K>
+DZ_DEV double row_prefix_ordered(double w)
+{
+    static_assert(K >= 1 && K <= 16, "a prefix inside a row of 16 lanes");
+    return row_prefix_shifted<K - 1>(0.0, w) + w;
 }
 // maximum over each row of 16 lanes, in every lane of the row (fmax is exact, so the order is immaterial)
 DZ_DEV double rowmax16(double v)

@@ -166,7 +166,7 @@ DZ_DEV int mt_select_vals(int k, double lp, double u_sel, int lane, bool* anyfin
     }
     return __builtin_amdgcn_readfirstlane(sel);
 }
-// ... with the try count a compile-time constant (k_generations' KC instantiations): the same sums in the same order, unrolled, every lane number an immediate
+// ... with the try count a compile-time constant (k_generations' KC instantiations): the same sums in the same order, on the vector unit
 template <int K>
 DZ_DEV int mt_select_vals(double lp, double u_sel, int lane, bool* anyfinite)
 {
@@ -174,18 +174,14 @@ DZ_DEV int mt_select_vals(double lp, double u_sel, int lane, bool* anyfinite)
     const double mx = readlane_f64(rowmax16(lp), 0);
     *anyfinite = __any(lane < K && is_finite(lp)) != 0;
     const double w = dexp(lp - mx);
-    double S = 0.0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) S = S + readlane_f64(w, i);
+    // S, and then cum, as in-row ordered prefix sums (row_prefix_ordered: lane i holds the sum over tries 0..i in try order, the bits of the
+    // generic form's loops): S is lane K-1's, and "the first i with u_sel < cum_i, else K-1" is the lowest set bit of ONE compare's mask
+    // over lanes 0..K-1 with bit K-1 set in any case.  A NaN cum_i compares false, as in the loop.
+    const double S = readlane_f64(row_prefix_ordered<K>(w), K - 1);
     const double pr = w / S;
-    double cum = 0.0; int sel = K - 1; bool found = false;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        cum = cum + readlane_f64(pr, i);
-        const bool hit = !found && (u_sel < cum);
-        sel = hit ? i : sel; found = found || hit;
-    }
-    return __builtin_amdgcn_readfirstlane(sel);
+    const double cum = row_prefix_ordered<K>(pr);
+    const unsigned long long hit = (__ballot(u_sel < cum) & ((1ull << K) - 1ull)) | (1ull << (K - 1));
+    return __builtin_ctzll(hit);
 }
 DZ_DEV int mt_select(const Params& p, int c, double u_sel, int lane, bool* anyfinite)
 {
@@ -221,11 +217,9 @@ DZ_DEV double mt_log_ratio(double val, double u_acc, int lane, double* log_u)
     const double rm = rowmax16(val);
     const double m2 = fmax(readlane_f64(rm, 0), readlane_f64(rm, 16));
     const double ev = dexp(val - m2);
-    double SA = 0.0, SB = 0.0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) SA = SA + readlane_f64(ev, i);
-#pragma unroll
-    for (int i = 0; i < K; ++i) SB = SB + readlane_f64(ev, 16 + i);
+    // both ordered sums from ONE in-row prefix: SA ends in lane K-1 of row 0, SB in lane K-1 of row 1 (the rows do not mix)
+    const double pre = row_prefix_ordered<K>(ev);
+    const double SA = readlane_f64(pre, K - 1), SB = readlane_f64(pre, 16 + K - 1);
     const double lg = dlog(lane == 1 ? u_acc : SA / SB);
     *log_u = readlane_f64(lg, 1);
     return nan_to_num(readlane_f64(lg, 0));
