@@ -38,7 +38,33 @@
 //   * a point that is not live applies nothing and takes no step.
 // Event times come from the block, so control flow stays uniform within a lane group.  integrate_fixed ignores events.
 //
-// Every loop is bounded: at most max_steps attempted steps per segment, at most T + Emax segments.
+// EQUILIBRATION (MassActionODELogLike(equilibrate=...)): an experiment that starts from the resting state of the unstimulated system, a
+// state that depends on the point.  A network of an object that equilibrates in at least one experiment carries
+//     static constexpr bool EQUILIBRATE = true;
+// and each experiment's block (each sub-block, with conditions) grows at its very end -- after the event records if there are any, else
+// after sd -- by six doubles
+//     on (0 / 1),   rtol_ss,   atol_ss,   horizon,   max_step,   max_steps_ss
+// (an experiment without the phase: six zeros), so the conditions' stride stays uniform.  The block of a network without the member is
+// what it always was.  The phase (dzode::equilibrate) runs inside integrate between the shape's init and the first start step:
+//   * it starts from the experiment's y0 (a Monomial entry as always);
+//   * the system is autonomous, so the phase keeps NO CLOCK: only the state and the step size exist;
+//   * the first step is start_step(y0, rtol, atol, horizon); not finite or not > 0: a failed integration.  The steps and the controller
+//     are integrate's (error test, negativity rule, rejection rule, step_factor, the experiment's rtol and atol), but no step is clipped
+//     to a breakpoint and after an accepted step h = min(h * fac, max_step);
+//   * the STEADY-STATE TEST runs before every attempted step, so also on y0 itself: the state is steady when
+//         drift2(y) * horizon * horizon <= 1,     drift2(y) = the shape's wnorm2(f(y), y, rtol_ss, atol_ss)
+//     -- left alone for the length of the experiment the state would move by less than the tolerance, in the RMS sense;
+//   * -inf when the state is not steady after max_steps_ss attempted steps (the test runs once more after the last of them), a state is
+//     not finite, the iteration matrix is singular or a step is not > 0;
+//   * the state at which the test passed is the experiment's start: from there everything is as without the phase -- the events at t0
+//     are applied to it (a stimulus is a bolus (t0, s, 1, dose)), the controller starts with the usual formula from that state, an
+//     output at t0 sees the equilibrated state after the events at t0; nsteps_out includes the phase's steps;
+//   * a point that is not live takes no step; `on`, the tolerances and the limits come from the block and the test's result is one
+//     value per lane group, so control flow stays uniform within a group.
+// integrate_fixed ignores the phase, as it ignores events.  With conditions every item equilibrates on its own.
+//
+// Every loop is bounded: at most max_steps_ss attempted steps of the phase, at most max_steps attempted steps per segment, at most
+// T + Emax segments.
 //
 // MONOMIALS (likelihoods.Monomial): a rate constant, a start amount, an observable's scale factor or the argument of a Gaussian
 // constraint may be 10**(c + sum_i e_i x[i]), a product of powers of the sampled constants.  The arithmetic is the same on device and
@@ -169,6 +195,10 @@ template <class Net> struct has_events<Net, decltype((void)Net::EVENTS)> {
     static constexpr int count = Net::EVENTS;
     static_assert(Net::EVENTS >= 1 && Net::EVENTS <= 16, "1..16 events per experiment");
 };
+
+// ... and the equilibration phase (the head of the file): the network of an object that equilibrates in at least one experiment
+template <class Net, class = void> struct has_equilibrate { static constexpr bool value = false; };
+template <class Net> struct has_equilibrate<Net, decltype((void)Net::EQUILIBRATE)> { static constexpr bool value = Net::EQUILIBRATE; };
 
 template <class Net>
 DZO_HD bool monomials_live(const double* x)
@@ -391,12 +421,57 @@ DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h
 //     sh.any_negative(yn, y, rtol, atol)               an amount of yn below -(atol + rtol |y|)
 //     sh.observe(y, o)                                 o[O]
 //     Shape::EVENTS, sh.apply(y, species, factor, amount)   (a network with events: Emax, and y[species] = factor * y[species] + amount)
+//     Shape::EQUILIBRATE, sh.drift2(y, rtol, atol)     (a network that equilibrates: the steady-state test's wnorm2(f(y), y, rtol, atol))
 // and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
 // Group<Net, L> (dz_ode_group.h: a group of L lanes per point, and its host twin).  A point that is not live keeps h = 0, ok = false and
 // takes no step, but does not return ahead of the loop: the lanes of a group stay with their wave.
 // With events (the head of the file) every pass of the outer loop is one SEGMENT: the events that are due and the controller's (re)start
 // -- the start at t0 is the first of them, so the start step exists once in the code --, the steps up to the next breakpoint, and the
 // output if the breakpoint is one.  Without events a pass is an output interval, as it always was.
+// The equilibration phase (the head of the file) of one experiment: y from the experiment's start amounts to the resting state, by the
+// steps and the controller of integrate without a clock and without an end time.  ok in: the point is live; out: the state is steady
+// (or the experiment does not equilibrate).  nsteps grows by the accepted steps; attempts (optional): the attempted ones.  The loop is
+// bounded by the block's max_steps_ss; `on`, the tolerances and the limits come from the block and the test's result is one value per
+// lane group, so control flow stays uniform within a group.
+template <class Shape>
+DZO_HD bool equilibrate(const Shape& sh, const double* blk, typename Shape::State& y, bool ok, int& nsteps, int* attempts)
+{
+    const long long per = (long long)(int)blk[5] * Shape::O;
+    const double* eq = blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0);
+    if (attempts) *attempts = 0;
+    if (eq[0] == 0.0) return ok;
+    const double rtol = blk[1], atol = blk[2], rtol_ss = eq[1], atol_ss = eq[2], horizon = eq[3], max_step = eq[4];
+    const int max_steps = (int)eq[5];
+    typename Shape::State yn;
+    double h = ok ? sh.start_step(y, rtol, atol, horizon) : 0.0;
+    ok = ok && finite(h) && h > 0.0;
+    bool rejected = false;
+    for (int n = 0; ok; ++n) {
+        if (sh.drift2(y, rtol_ss, atol_ss) * horizon * horizon <= 1.0) break;      // steady: before every attempted step, y0 included
+        if (n >= max_steps || !(h > 0.0)) { ok = false; break; }
+        if (attempts) *attempts = n + 1;
+        // from here integrate's step, error test, negativity and rejection rules, repeated and not shared: with one function called from
+        // both loops the code objects of networks WITHOUT the phase came out different from what they were (two to three VGPRs more)
+        double err2;
+        const bool nonsing = sh.step(y, h, rtol, atol, yn, err2);
+        if (!sh.all_finite(yn, nonsing && finite(err2))) { ok = false; break; }
+        ++nsteps;
+        double fac = step_factor(err2);
+        const bool neg = sh.any_negative(yn, y, rtol, atol);
+        if (neg) fac = dmin(fac, 0.25);
+        if (err2 <= 1.0 && !neg) {
+            if (rejected) fac = dmin(fac, 1.0);
+            y = yn;
+            h = dmin(h * fac, max_step);
+            rejected = false;
+        } else {
+            h = h * fac;
+            rejected = true;
+        }
+    }
+    return ok;
+}
+
 template <class Shape>
 DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* sim, int* nsteps_out)
 {
@@ -413,11 +488,12 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     constexpr int EV = Shape::EVENTS;
     double h = 0.0;
     bool ok = live, rejected = false;
-    if constexpr (EV == 0) {
-        h = live ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
-        ok = live && finite(h) && h > 0.0;
-    }
     int nsteps = 0;
+    if constexpr (Shape::EQUILIBRATE) ok = equilibrate(sh, blk, y, ok, nsteps, nullptr);      // y: the resting state, the experiment's start
+    if constexpr (EV == 0) {
+        h = ok ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
+        ok = ok && finite(h) && h > 0.0;
+    }
     // (without events the block ends with sd: evt is then the pointer one past its end, only formed and never read)
     [[maybe_unused]] const double* evt = sd + (long long)T * O + (EV > 0 ? 1 : 0);      // records of (time, species, factor, amount)
     [[maybe_unused]] int ev = 0, E = 0;                                      // the event cursor, this experiment's event count
@@ -517,6 +593,7 @@ DZO_HD double start_step(const double* k, const double* y, double rtol, double a
 template <class Alg>
 struct Array {
     static constexpr int S = Alg::Net::S, O = Alg::Net::O, EVENTS = has_events<typename Alg::Net>::count;
+    static constexpr bool EQUILIBRATE = has_equilibrate<typename Alg::Net>::value;
     struct State { double v[S]; };
     const double* k;                                   // the rate constants
     const double* x;                                   // the point's row (read only by a network with monomials)
@@ -526,6 +603,12 @@ struct Array {
         for (int s = 0; s < S; ++s) y.v[s] = start_amount<typename Alg::Net>(s, x, blk[6 + s]);
     }
     DZO_HD double start_step(const State& y, double rtol, double atol, double span) const { return dzode::start_step<Alg>(k, y.v, rtol, atol, span); }
+    DZO_HD double drift2(const State& y, double rtol, double atol) const      // the steady-state test's norm of f(y)
+    {
+        double f[S];
+        Alg::rhs(k, y.v, f);
+        return Alg::wnorm2(f, y.v, rtol, atol);
+    }
     DZO_HD bool step(const State& y, double h, double rtol, double atol, State& yn, double& err2) const
     {
         double ye[S];
@@ -561,6 +644,28 @@ DZO_HD double integrate_point(const double* x, const double* blk, double* sim, i
     if (nsteps_out) *nsteps_out = 0;
     if (!Alg::rates(x, k)) return -__builtin_huge_val();
     return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
+}
+
+// The host build's resting state of one point's experiment (blk: one experiment's block): the state handed to the experiment, before
+// the events at t0 -- the start amounts themselves where the experiment does not equilibrate, NaN where the point is not live or the
+// phase fails.  attempts: the phase's attempted steps.
+template <class Alg>
+DZO_HD void equilibrate_point(const double* x, const double* blk, double* yss, int* attempts)
+{
+    constexpr int S = Alg::Net::S;
+    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    const Array<Alg> sh{k, x};
+    typename Array<Alg>::State y;
+    bool ok = Alg::rates(x, k);
+    *attempts = 0;
+    if (ok) {
+        sh.init(blk, y);
+        if constexpr (Array<Alg>::EQUILIBRATE) {
+            int steps = 0;
+            ok = equilibrate(sh, blk, y, ok, steps, attempts);
+        }
+    }
+    for (int s = 0; s < S; ++s) yss[s] = ok ? y.v[s] : __builtin_nan("");
 }
 
 // The constraints' term g of one point alone (0 for a network without constraints, -inf for a point that is not live).
@@ -643,6 +748,10 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         const long long per = (long long)(int)blk[5] * ALG::Net::O;                                                                      \
         for (long long i = 0; i < n; ++i) like[i] = dzode::integrate_point<ALG>(X + i * ld, blk, sim + i * per, nullptr);               \
     }                                                                                                                                    \
+    extern "C" void dzode_equilibrate(const double* X, long long n, int ld, const double* blk, double* yss, int* attempts)              \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) dzode::equilibrate_point<ALG>(X + i * ld, blk, yss + i * ALG::Net::S, attempts + i);          \
+    }                                                                                                                                    \
     DZODE_HOST_COMMON(ALG)
 
 // ... and those of C conditions (blk: the block with the [C, stride] header): dzode_loglike gives the points' sums (nsteps: over the
@@ -657,6 +766,12 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     {                                                                                                                                    \
         const long long C = (long long)blk[0], per = C * (int)blk[2 + 5] * ALG::Net::O;                                                  \
         for (long long i = 0; i < n; ++i) dzode::integrate_conditions<ALG>(X + i * ld, blk, terms + i * C, sim ? sim + i * per : nullptr, nullptr); \
+    }                                                                                                                                    \
+    extern "C" void dzode_equilibrate(const double* X, long long n, int ld, const double* blk, double* yss, int* attempts)              \
+    {                                                                                                                                    \
+        const long long C = (long long)blk[0], stride = (long long)blk[1];                                                               \
+        for (long long w = 0; w < n * C; ++w)                                                                                            \
+            dzode::equilibrate_point<ALG>(X + (w / C) * ld, blk + 2 + (w % C) * stride, yss + w * ALG::Net::S, attempts + w);           \
     }                                                                                                                                    \
     DZODE_HOST_COMMON(ALG)
 

@@ -39,7 +39,9 @@
 //     static void obs(const double* y, double* o);
 // and, for a network with monomials (dz_ode.h's head: the construct, its arithmetic and the members live, y0_row, scale, constraints),
 //     static double rate_mono(int j, const double* x, bool& good);    the rate constant of a reaction whose rate_index is -2
-// Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd).
+// Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd; with the
+// equilibration phase: its six doubles at the end.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
+// the group's norm, a group-wide value).
 #pragma once
 #include "dz_ode.h"
 
@@ -289,6 +291,7 @@ __device__ __forceinline__ double group_start_step(const double* ks, double y, d
 template <class Net, int L>
 struct Group {
     static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
+    static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
     typedef double State;
     const double* ks;                                  // the point's rate constants (LDS)
     int r;
@@ -297,6 +300,12 @@ struct Group {
     __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
     {
         return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
+    }
+    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // the steady-state test's norm of f(y), group-wide
+    {
+        double yr[S];
+        Lanes<L>::template gather<S>(y, yr);
+        return group_wnorm2<S, L>(Net::rhs_row(row_index(r), ks, yr), y, rtol, atol, r);
     }
     __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
     {
@@ -490,6 +499,7 @@ __device__ __forceinline__ double wave_start_step(const double* ks, double* ys, 
 template <class Net>
 struct Group<Net, 64> {
     static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
+    static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
     typedef double State;
     double* ks;
     int r;
@@ -498,6 +508,12 @@ struct Group<Net, 64> {
     __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
     {
         return wave_start_step<Net>(ks, wave_state<Net>(ks), y, rtol, atol, span, r);
+    }
+    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // (the state published as wave_start_step does)
+    {
+        double* ys = wave_state<Net>(ks);
+        wave_publish<S>(ys, r, y);
+        return group_wnorm2<S, 64>(Net::rhs_row(row_index(r), ks, ys), y, rtol, atol, r);
     }
     __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
     {

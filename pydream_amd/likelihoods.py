@@ -363,6 +363,7 @@ ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, l
 ODE_WAVE_LIMITS = dict(species=64, reactions=256, observables=16, times=4096, lanes=(64,), conditions=64)            # lanes_per_point=64: 33..64 species
 ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
 ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
+ODE_EQUILIBRATE_MAX_STEPS = 2000    # equilibrate=...: the attempted steps of the phase before the experiment, unless its "max_steps" says otherwise
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 _LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
 
@@ -508,12 +509,14 @@ def _obs_lines(S, observables):
     return L
 
 
-def _net_source(header, S, R, O, body, observables, entries, events=0):
+def _net_source(header, S, R, O, body, observables, entries, events=0, equilibrate=False):
     """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
     closing brace of the last one), the observables and the entry macro.  events: the largest event count over the object's
-    experiments; the member EVENTS only if there is one (csrc/dz_ode.h)."""
+    experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  equilibrate: some experiment equilibrates first; the member
+    EQUILIBRATE only then."""
     L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O)]
     L += ["    static constexpr int EVENTS = %d;" % events] if events else []
+    L += ["    static constexpr bool EQUILIBRATE = true;"] if equilibrate else []
     L += body
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(S, observables) + ["    }", "};", entries, ""]
     return '#include "%s"\n' % header + "\n".join(L)
@@ -522,7 +525,7 @@ def _net_source(header, S, R, O, body, observables, entries, events=0):
 _ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
 
 
-def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None, events=0):
+def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None, events=0, equilibrate=False):
     """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
     order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
     reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
@@ -568,16 +571,16 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events, equilibrate)
 
 
-def _ode_source(S, reactions, observables, log10, items=False, mono=None, events=0):
+def _ode_source(S, reactions, observables, log10, items=False, mono=None, events=0, equilibrate=False):
     """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
     straight-line code with constant indices; powers as repeated products.  items: the entry points for several conditions per point."""
     R, O = len(reactions), len(observables)
     entries = "DZODE_ITEM_ENTRIES(Net)" if items else "DZODE_ENTRIES(Net)"
     if R > _ODE_WHOLE_SUMS:
-        return _ode_long_source(S, reactions, observables, log10, entries, mono, events)
+        return _ode_long_source(S, reactions, observables, log10, entries, mono, events, equilibrate)
     N = _stoichiometry(S, reactions)
     L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     for r, (_, _, rate) in enumerate(reactions):
@@ -602,10 +605,10 @@ def _ode_source(S, reactions, observables, log10, items=False, mono=None, events
         for q in range(S):
             terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events)
+    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events, equilibrate)
 
 
-def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None, events=0):
+def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None, events=0, equilibrate=False):
     """The generated network struct for the lane-group solver and, with lanes=64, the wave-per-point one (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
     its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
     stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
@@ -651,7 +654,7 @@ def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono
                  for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
     L += ["        default: return 0.0;", "        }", "    }"] + (_monomial_members(mono) if mono else [])
-    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes, events)
+    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes, events, equilibrate)
 
 
 class MassActionODELogLike:
@@ -696,7 +699,7 @@ class MassActionODELogLike:
     Monomials and events work as below.
 
     conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
-    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events"; a missing key is the constructor's own argument,
+    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events", "equilibrate"; a missing key is the constructor's own argument,
     which (y0, data, sd) may be None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
     point is ((l_0 + l_1) + l_2) + ..., l_c exactly what this class gives for condition c alone (-inf if any integration fails).  On the
     device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
@@ -718,6 +721,35 @@ class MassActionODELogLike:
     segments.  Both builds and both shapes follow this exactly (csrc/dz_ode.h) and give the same bits.  Not supported: an amount that
     is a Monomial (a sampled dose), events triggered by the state; fixed_steps ignores events.
 
+    equilibrate: start the experiment from the RESTING STATE of the unstimulated system -- receptor turnover, basal phosphorylation,
+    pre-formed complexes: a state that depends on the sampled rate constants -- instead of from amounts someone wrote down.  None or
+    False: no such phase (an object without it in any experiment generates the source and the data block it always did); True: the
+    defaults; or a mapping with the optional keys
+      * rtol, atol: the tolerances of the steady-state test (default: the constructor's rtol and atol);
+      * horizon: the length of time over which the state is to stand still (default max(t[-1] - t0, 1e-300); finite and > 0);
+      * max_step: the largest step of the phase (default 1e6 * horizon; finite and > 0);
+      * max_steps: the attempted steps of the phase (default 2000, ODE_EQUILIBRATE_MAX_STEPS; >= 1).
+    A condition may carry its own "equilibrate": a missing key or None inherits the constructor's value, False switches the phase off
+    for that condition, True and a mapping stand for themselves (defaults filled in, not the constructor's mapping).  The semantics
+    (csrc/dz_ode.h's head), the same in both builds and every shape:
+      * the phase starts from the experiment's y0 (Monomial entries as always).  The system is autonomous, so the phase keeps no
+        clock: only the state and the step size exist;
+      * the first step is start_step(y0, rtol, atol, horizon) -- not finite or not > 0: -inf --, the steps and the controller are the
+        experiment's (error test, negativity rule, rejection rule, the same rtol and atol), but no step is clipped to a breakpoint, and
+        after an accepted step h = min(h * factor, max_step);
+      * before every attempted step, so also on y0 itself, the steady-state test: the state is steady when
+        mean((f(y) / (atol_ss + rtol_ss |y|))**2) * horizon**2 <= 1 -- left alone for the length of the experiment it would move by
+        less than the tolerance, in the RMS sense;
+      * -inf when the state is not steady after max_steps attempted steps (a limit cycle, a mode too slow for the budget), a state is
+        not finite, the iteration matrix is singular or a step is not > 0;
+      * the state at which the test passed is the experiment's start; from there everything is as without the phase.  The events at t0
+        are applied to it, so a condition's stimulus is a bolus (t0, s, 1, dose); the controller starts with the usual formula from
+        that state; an output at t0 sees the equilibrated state after the events at t0.  batch(return_steps=True) includes the phase's
+        steps.
+    steady_state(X) returns the state handed to the experiment, before the events at t0 (host build).  Not supported: one
+    equilibration shared between the conditions of a point -- every condition equilibrates on its own, also where two of them start
+    from the same y0 --; a setting of the phase that is a Monomial; fixed_steps ignores equilibrate, as it ignores events.
+
     Products of parameters: a Monomial(exponents, log10_factor) = 10**(log10_factor + sum_i exponents[i] x[i]) may stand
       * as a reaction's rate (kr = KD kf with a fixed kf: Monomial({i: 1}, log10(kf)); a closed cycle: Monomial({0: 1, 1: 1, 2: -1}));
       * as an entry of y0, the constructor's or a condition's: a sampled total amount.  A species has the same Monomial wherever a y0
@@ -735,10 +767,12 @@ class MassActionODELogLike:
 
     conditions = None       # (an object pickled before the keyword existed)
     events = None           # (likewise)
+    equilibrate = None      # (likewise)
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
-                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None):
+                 max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
+                 equilibrate=None):
         S = int(n_species)
         lanes = int(lanes_per_point)
         if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"] + ODE_WAVE_LIMITS["lanes"]:
@@ -783,8 +817,8 @@ class MassActionODELogLike:
             if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
                 raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
             for c, cond in enumerate(conditions):
-                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events"}:
-                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events" (each optional)' % c)
+                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate"}:
+                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate" (each optional)' % c)
                 for key, top in (("y0", y0), ("data", data), ("sd", sd)):
                     if cond.get(key) is None and top is None:
                         raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
@@ -805,6 +839,10 @@ class MassActionODELogLike:
         if data is not None and sd is not None:
             data, sd = self._checked_data(data, sd, O, T, "")
         events = self._checked_events(events, S, float(t0), t, "")
+        if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
+            raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
+        span = max(float(t[-1]) - float(t0), 1e-300)
+        equilibrate = self._checked_equilibrate(equilibrate, float(rtol), float(atol), span, "")
         if conditions is not None:              # every condition as the single experiment: its own values, else the constructor's (checked above)
             full = []
             for c, cond in enumerate(conditions):
@@ -814,10 +852,9 @@ class MassActionODELogLike:
                 if cond.get("data") is not None or cond.get("sd") is not None or data is None or sd is None:
                     cdata, csd = self._checked_data(cdata, csd, O, T, who)
                 cev = events if "events" not in cond or cond["events"] is None else self._checked_events(cond["events"], S, float(t0), t, who)
-                full.append(dict(y0=cy0, data=cdata, sd=csd, events=cev))
+                ceq = equilibrate if cond.get("equilibrate") is None else self._checked_equilibrate(cond["equilibrate"], float(rtol), float(atol), span, who)
+                full.append(dict(y0=cy0, data=cdata, sd=csd, events=cev, **({"equilibrate": ceq} if ceq else {})))
             conditions = full
-        if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
-            raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
         if scale is not None:
             scale = list(scale) if hasattr(scale, "__len__") or hasattr(scale, "__iter__") else [scale]
             if len(scale) != O or not all(isinstance(f, Monomial) or (not isinstance(f, bool) and isinstance(f, (int, np.integer, float, np.floating)) and np.isfinite(f))
@@ -846,7 +883,8 @@ class MassActionODELogLike:
         self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
         self.data, self.sd = data, sd
         self.events = events or None            # None, or the checked (time, species, factor, amount) tuples sorted by time
-        self.conditions = conditions            # None, or a list of dict(y0, data, sd): checked arrays, the fallbacks filled in
+        self.equilibrate = equilibrate          # None, or dict(rtol, atol, horizon, max_step, max_steps), every default filled in
+        self.conditions = conditions            # None, or a list of dict(y0, data, sd, events[, equilibrate]): checked, the fallbacks filled in
         self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
         self.path, self.lanes_per_point = path, lanes
         self._host = None
@@ -871,6 +909,33 @@ class MassActionODELogLike:
                                  % (who, s, m, monomials[s]))
             y0[s] = np.nan
         return y0
+
+    @staticmethod
+    def _checked_equilibrate(eq, rtol, atol, span, who):
+        """None (no phase) or the phase's settings, every default filled in: dict(rtol, atol, horizon, max_step, max_steps)."""
+        real = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer, float, np.floating)) and np.isfinite(v)      # noqa: E731
+        if eq is None or eq is False:
+            return None
+        if eq is True:
+            eq = {}
+        keys = ("rtol", "atol", "horizon", "max_step", "max_steps")
+        if not hasattr(eq, "keys") or set(eq.keys()) - set(keys):
+            raise ValueError('MassActionODELogLike: %sequilibrate must be None, False, True or a mapping with the keys "rtol", "atol", "horizon", '
+                             '"max_step", "max_steps" (each optional; got %r)' % (who, eq))
+        out = dict(rtol=eq.get("rtol", rtol), atol=eq.get("atol", atol), horizon=eq.get("horizon", span))
+        for key in ("rtol", "atol", "horizon"):
+            if not real(out[key]) or not out[key] > 0:
+                raise ValueError("MassActionODELogLike: %sequilibrate: %s must be finite and > 0 (got %r)" % (who, key, out[key]))
+            out[key] = float(out[key])
+        out["max_step"] = eq.get("max_step", 1e6 * out["horizon"])
+        if not real(out["max_step"]) or not out["max_step"] > 0:
+            raise ValueError("MassActionODELogLike: %sequilibrate: max_step must be finite and > 0 (got %r)" % (who, out["max_step"]))
+        out["max_step"] = float(out["max_step"])
+        n = eq.get("max_steps", ODE_EQUILIBRATE_MAX_STEPS)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("MassActionODELogLike: %sequilibrate: max_steps must be an integer >= 1 (got %r)" % (who, n))
+        out["max_steps"] = int(n)
+        return out
 
     @staticmethod
     def _checked_events(events, S, t0, t, who):
@@ -926,7 +991,17 @@ class MassActionODELogLike:
         """Emax, the generated network's EVENTS: the largest event count over the object's experiments (0: a network without events)."""
         return max(len(ev) for ev in self._event_lists())
 
-    def _experiment_block(self, y0, data, sd, events=()):
+    def _equilibrate_list(self):
+        """Every experiment's equilibration settings, None where it has none (so for an object from before the keyword existed)."""
+        if self.conditions is None:
+            return [self.equilibrate or None]
+        return [cond.get("equilibrate") or None for cond in self.conditions]
+
+    def _equilibrates(self):
+        """Some experiment of the object equilibrates: the generated network's EQUILIBRATE and the six doubles at each block's end."""
+        return any(eq is not None for eq in self._equilibrate_list())
+
+    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None):
         seen = np.isfinite(data)
         C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
         dat = np.where(seen, data, 0.0).T.reshape(-1)               # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
@@ -937,14 +1012,17 @@ class MassActionODELogLike:
             rec = np.zeros((emax, 4))
             rec[:len(events)] = np.asarray(events, dtype=float).reshape(-1, 4)
             blk += [[float(len(events))], rec.reshape(-1)]
+        if self._equilibrates():                # (csrc/dz_ode.h: on, rtol_ss, atol_ss, horizon, max_step, max_steps_ss at the very end)
+            eq = equilibrate
+            blk += [[1.0, eq["rtol"], eq["atol"], eq["horizon"], eq["max_step"], float(eq["max_steps"])] if eq else [0.0] * 6]
         return np.concatenate(blk)
 
     def condition_block(self, c=0):
         """One experiment's block: condition c's, or (without conditions) the constructor's own."""
         if self.conditions is None:
-            return self._experiment_block(self.y0, self.data, self.sd, self.events or ())
+            return self._experiment_block(self.y0, self.data, self.sd, self.events or (), self.equilibrate)
         cond = self.conditions[c]
-        return self._experiment_block(cond["y0"], cond["data"], cond["sd"], cond.get("events") or ())
+        return self._experiment_block(cond["y0"], cond["data"], cond["sd"], cond.get("events") or (), cond.get("equilibrate"))
 
     def data_block(self):
         """The block the kernels read (csrc/dz_ode.h): one experiment's, or with conditions [C, stride] and the C experiments' blocks."""
@@ -964,9 +1042,10 @@ class MassActionODELogLike:
     def source(self):
         items = self.conditions is not None
         if self.lanes_per_point == 1:
-            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials(), self._max_events())
+            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials(), self._max_events(),
+                               self._equilibrates())
         return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items, self._monomials(),
-                                 self._max_events())
+                                 self._max_events(), self._equilibrates())
 
     @staticmethod
     def _header_hash(name="dz_ode.h"):
@@ -1014,6 +1093,7 @@ class MassActionODELogLike:
             L.dzode_fixed.argtypes = [P, P, D, I, I, P]
             L.dzode_fixed.restype = I
             L.dzode_constraints.argtypes = [P, I64, I, P]
+            L.dzode_equilibrate.argtypes = [P, I64, I, P, P, C.POINTER(C.c_int)]
             L.dzode_exp.argtypes = L.dzode_log.argtypes = [D]
             L.dzode_exp.restype = L.dzode_log.restype = D
             self._host = L
@@ -1061,6 +1141,17 @@ class MassActionODELogLike:
         terms = np.zeros((len(X), len(self.conditions)))
         self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), None, terms)
         return terms
+
+    def steady_state(self, X, return_steps=False):
+        """The state handed to the experiment, before the events at t0, from the host build: [n, S], with conditions [n, C, S].  An
+        experiment that equilibrates gives the state at which the steady-state test passed (NaN where the phase failed or the point is
+        not live), one that does not gives its y0.  return_steps: also the ATTEMPTED steps of the phase, [n] or [n, C] -- what the
+        phase's max_steps counts."""
+        X = self._rows(X)
+        lead = (len(X),) if self.conditions is None else (len(X), len(self.conditions))
+        y, st = np.full(lead + (self.n_species,), np.nan), np.zeros(lead, dtype=np.int32)
+        self._host_call("dzode_equilibrate", X, len(X), X.shape[1], self.data_block(), y, st)
+        return (y, st) if return_steps else y
 
     def constraint_terms(self, X):
         """g(x) = sum over the constraints of norm(loc, sd).logpdf(monomial) for the rows of X, from the host build: what the single

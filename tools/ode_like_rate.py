@@ -10,7 +10,7 @@
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle]
-                                  [--lanes 1|16|32|64] [--conditions C [--events E]] [--host-twin]
+                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -22,6 +22,11 @@ conditions with E events in each (at equal distances inside the time span, on th
 topped up by half its start amount, in turn) against the same C conditions without events, alternately, the median of 7 rounds of 10
 calls each and the rounds' spread; proposals/s and the host build's steps per point for both.  --events 0 times the event-less object
 alone and never names the keyword (so the same script runs on a checkout from before the keyword existed).  Kernel only.
+
+--conditions C --equilibrate: what equilibrating to the resting state before the experiment costs (MassActionODELogLike(equilibrate=
+True)) -- the network under C conditions with the phase on in every condition against the same C conditions without it, alternately,
+the median of 7 rounds of 10 calls each and the rounds' spread; proposals/s, the host build's steps per point for both and the phase's
+attempted steps per item.  Kernel only.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -165,20 +170,24 @@ def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
     return out
 
 
-def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10):
+def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10, equilibrate=False):
+    """E events per condition against none or (equilibrate) the phase on in every condition against off: see the head"""
     from pydream_amd import _capi
     from pydream_amd.likelihoods import MassActionODELogLike
     like, nominal, width = network(name, lanes)
     plain, _ = with_conditions(like, C)
-    objs = {"without_events": plain}
-    if E > 0:
+    first, second = ("without_phase", "with_phase") if equilibrate else ("without_events", "with_events")
+    objs = {first: plain}
+    shared = dict(rate_scale=like.rate_scale, t0=like.t0, rtol=like.rtol, atol=like.atol, max_steps=like.max_steps, lanes_per_point=like.lanes_per_point,
+                  conditions=[dict(y0=c["y0"]) for c in plain.conditions])
+    if equilibrate:
+        objs[second] = MassActionODELogLike(like.n_species, like.reactions, None, like.t, like.observables, like.data, like.sd, equilibrate=True, **shared)
+    elif E > 0:
         s = int(np.argmax(like.y0))
         span = like.t[-1] - like.t0
         events = [(like.t0 + (e + 1) * span / (E + 1), s, 0.5, 0.0) if e % 2 == 0 else (like.t0 + (e + 1) * span / (E + 1), s, 1.0, 0.5 * like.y0[s])
                   for e in range(E)]
-        objs["with_events"] = MassActionODELogLike(like.n_species, like.reactions, None, like.t, like.observables, like.data, like.sd,
-                                                   rate_scale=like.rate_scale, t0=like.t0, rtol=like.rtol, atol=like.atol, max_steps=like.max_steps,
-                                                   lanes_per_point=like.lanes_per_point, conditions=[dict(y0=c["y0"]) for c in plain.conditions], events=events)
+        objs[second] = MassActionODELogLike(like.n_species, like.reactions, None, like.t, like.observables, like.data, like.sd, events=events, **shared)
     n, d = N * k, len(nominal)
     X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
     engines = {}
@@ -187,13 +196,17 @@ def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10):
         eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
         obj._dz_apply(eng)
         engines[key] = eng
-    out = dict(network=name, lanes=like.lanes_per_point, conditions=C, events_per_condition=E, chains=N, tries=k, points=n, items=n * C)
+    out = dict(network=name, lanes=like.lanes_per_point, conditions=C, chains=N, tries=k, points=n, items=n * C,
+               **(dict(equilibrate=True) if equilibrate else dict(events_per_condition=E)))
     for key, eng in engines.items():
         for _ in range(3):
             lk = eng.eval_logp(X)[1]
         host, steps = objs[key].batch(X, return_steps=True)
         assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
         out[key] = dict(steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)))
+        if equilibrate and key == second:
+            attempts = objs[key].steady_state(X, return_steps=True)[1]
+            out[key].update(phase_attempts_median=float(np.median(attempts)), phase_attempts_max=int(attempts.max()))
     t = {key: [] for key in engines}
     for _ in range(rounds):                                             # alternately: a drift of the machine hits both alike
         for key, eng in engines.items():
@@ -204,8 +217,8 @@ def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10):
     for key in engines:
         us = float(np.median(t[key]))
         out[key].update(us_per_launch=round(us, 1), us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6))
-    if E > 0:
-        out["with_over_without"] = round(out["with_events"]["us_per_launch"] / out["without_events"]["us_per_launch"], 3)
+    if second in out:
+        out["with_over_without"] = round(out[second]["us_per_launch"] / out[first]["us_per_launch"], 3)
     print(json.dumps(out), flush=True)
     return out
 
@@ -323,6 +336,12 @@ if __name__ == "__main__":
     if "--host-twin" in argv:
         nums = [int(a) for a in argv[:2] if not a.startswith("--")]
         host_twin_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None)
+        sys.exit(0)
+    if "--equilibrate" in argv:
+        assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
+        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
+        events_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
+                    int(opt["--conditions"]), 0, equilibrate=True)
         sys.exit(0)
     if "--events" in opt:
         assert "--conditions" in opt, "--events goes with --conditions C"
