@@ -13,14 +13,14 @@ def _side(*species):
     return out
 
 
-def random_network(rng, S, R, P):
-    """(reactions, kinds): R reactions over S species, each drawn from KINDS
+def random_network(rng, S, R, P, kinds=KINDS):
+    """(reactions, kinds): R reactions over S species, each drawn from `kinds` (all of KINDS, or a subset of its names)
         0 -> a,  a -> 0,  a -> b,  2a -> b,  3a -> b + 2c,  a + 2b -> c,  a + c -> b + c,  a + b -> 2a,  a + b -> c + d
     with distinct species where S allows it (S < 4: species are reused, so coefficients merge).  About 70 % of the rates are a parameter
     index below P (shared between reactions), the rest fixed floats in [0.2, 1.5].  Deterministic in rng's seed."""
-    reactions, kinds = [], []
+    reactions, drawn = [], []
     for _ in range(R):
-        kind = KINDS[int(rng.integers(len(KINDS)))]
+        kind = kinds[int(rng.integers(len(kinds)))]
         a, b, c, d = (int(s) for s in (rng.choice(S, 4, replace=False) if S >= 4 else rng.integers(0, S, 4)))
         reac, prod = {"source": (_side(), _side(a)), "degradation": (_side(a), _side()), "conversion": (_side(a), _side(b)),
                       "dimerisation": (_side(a, a), _side(b)), "third_order": (_side(a, a, a), _side(b, c, c)),
@@ -28,8 +28,8 @@ def random_network(rng, S, R, P):
                       "autocatalysis": (_side(a, b), _side(a, a)), "exchange": (_side(a, b), _side(c, d))}[kind]
         rate = int(rng.integers(P)) if rng.uniform() < 0.7 else float(rng.uniform(0.2, 1.5))
         reactions.append((reac, prod, rate))
-        kinds.append(kind)
-    return reactions, kinds
+        drawn.append(kind)
+    return reactions, drawn
 
 
 def rate_constants(reactions, x, rate_scale):
@@ -146,11 +146,29 @@ def rodas4_fixed_f64(S, reactions, k, y0, t0, t1, n, embedded=False):
     return np.array(_rodas4_fixed(S, reactions, k, y0, t0, t1, n, embedded, np.float64, lambda W: np.array(W, dtype=np.float64), solve), dtype=float)
 
 
-def fixed_step_reference(S, reactions, k, y0, t0, t1, n, embedded):
-    """(the mp solution rounded to doubles, max |mp|, tol) with tol = 64 max|f64 - mp| / max|mp| + 16 eps: what a correct float64
-    implementation with another operation order (an LU of up to 32 rows) may deviate from the mp solution, relative to max |mp|."""
+def pivot_rows(W):
+    """The row that pivots in every column of W under the solvers' rule (the head of csrc/dz_ode_group.h), restated in numpy float64:
+    per column the largest |w| among the rows that have not pivoted yet (equal maxima: the lowest row; a NaN counts as +inf), the other
+    such rows subtract their multiple of the pivot's row, rows do not move.  A column k pivots off the diagonal where the result is
+    not k.  For conditions on a test's INPUT, on the reference's own matrices (on_matrix below); never applied to the code under test."""
+    W = np.array([[float(v) for v in row] for row in W], dtype=np.float64)
+    S = len(W)
+    free, piv = np.ones(S, dtype=bool), np.zeros(S, dtype=np.int64)
+    for k in range(S):
+        key = np.abs(W[:, k])
+        key = np.where(free, np.where(np.isnan(key), np.inf, key), -1.0)
+        p = int(np.argmax(key))                                               # (the first of equal maxima)
+        piv[k], free[p] = p, False
+        W[free, k + 1:] -= np.outer(W[free, k] / W[p, k], W[p, k + 1:])
+    return piv
+
+
+def fixed_step_reference(S, reactions, k, y0, t0, t1, n, embedded, on_matrix=None):
+    """(the mp solution, max |mp|, tol) with tol = 64 max|f64 - mp| / max|mp| + 16 eps: what a correct float64 implementation with
+    another operation order (a pivoted LU of up to 64 rows: one lane, a group of 16 or 32, a wave of 64) may deviate from the mp
+    solution, relative to max |mp|.  on_matrix(step, W): handed to the mp integration."""
     import mpmath
-    ref = rodas4_fixed_mp(S, reactions, k, y0, t0, t1, n, embedded)
+    ref = rodas4_fixed_mp(S, reactions, k, y0, t0, t1, n, embedded, on_matrix=on_matrix)
     f64 = rodas4_fixed_f64(S, reactions, k, y0, t0, t1, n, embedded)
     with mpmath.mp.workdps(40):
         scale = max(abs(v) for v in ref)

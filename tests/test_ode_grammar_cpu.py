@@ -1,7 +1,23 @@
-"""The three host builds of MassActionODELogLike (one lane, 16 and 32 lanes per point) on a grammar of seeded random networks, against
+"""The four host builds of MassActionODELogLike (one lane, 16, 32 and 64 lanes per point) on a grammar of seeded random networks, against
 references that share no code with them (tests/ode_reference.py): fixed Rodas4 steps against a 40-digit restatement at a tolerance
 sized by a float64 restatement, the adaptive path against scipy's Radau, the linear invariants of the stoichiometric matrix, edge
-inputs, relabelled species and reordered reactions, and a network whose pivot candidates tie.
+inputs, relabelled species and reordered reactions, large steps whose pivots leave the diagonal, and a network whose pivot candidates tie.
+
+The grammar's fixed steps (t1 = 1, n = 4 and 16) never pivot: 1 / (h gamma) is 16 or 64 against Jacobian entries of order 1, W is
+diagonally dominant, and REF.pivot_rows on the float64 restatement's W finds no column off the diagonal in any step of any of the 37
+cases, at n = 4 or at n = 16.  There the arg-max, piv, pos and the solves' b[piv[k]] are the same as no pivoting at all.  The large-step family
+(tests/ode_grammar.LARGE_STEP_CASES) and the tied network are where a permutation is checked to rounding; fixed n = 16 runs on every
+64-lane case (the slowest, S = 63, takes about 40 s, most of it the mp restatement).
+
+Permutation faults seeded in a scratch copy (never committed), and what they did: the host twin's forward solve reading b[k] for
+b[piv[k]] (csrc/dz_ode_group.h, HostGroup::lu_solve: the builds of 16, 32 and 64 lanes) together with the one-lane lu_solve leaving b
+unpermuted (csrc/dz_ode.h).  All 29 fixed-step cases the grammar had before pass with both faults, at the ratios they show without
+(0.013 .. 0.051); so do the eight 64-lane cases.  All eight large-step cases fail: the state after four steps is not finite in seven and
+7e12 tolerances off in large-S16R32@16; after two steps the deviation is 1e13 .. 1e88 tolerances in every case, after the first step
+6e15 (large-S6R12@1), 2e21 (large-S12R24@16) and 9e16 (large-S64R80@64) where the first W already pivots, and 0.02 .. 0.09 where it
+does not.  The tied network fails in every build (not finite).  On the inputs of tests/test_ode_grammar_gpu.py the faults change the
+host value's bits at 2002 of 2051 (one lane), 1004 of 1027 (16 and 32 lanes) and 250 of 259 (64 lanes) tied points, and at 1027 of
+1027, 515 of 515, 512 of 515 and 131 of 131 large-step points: what the device comparison resolves there.
 
 Faults seeded while these were written, and what caught them: the multiplicity factor (2.0 *, 3.0 *) dropped from the generated Jacobian
 of the one-lane generator fails the fixed-step test on all 10 one-lane networks, dropped from the group generator on all 18 group
@@ -20,7 +36,7 @@ INDEX = list(range(len(G.CASES)))
 IDS = [G.network(i).name for i in INDEX]
 N_POINTS = 3
 _REPLACED, _NETS, _RADAU = set(), {}, {}
-_WORST = {lanes: dict(fixed=0.0, radau=0.0) for lanes in (1, 16, 32)}          # per build, for the summary the last grammar test prints
+_WORST = {lanes: dict(fixed=0.0, radau=0.0) for lanes in G.BUILDS}             # per build, for the summary the last grammar test prints
 
 
 def resolved(i):
@@ -39,14 +55,14 @@ def resolved(i):
     return _NETS[i], _RADAU[i]
 
 
-def _check_fixed_steps(builds, S, reactions, x, y0, t1, label):
+def _check_fixed_steps(builds, S, reactions, x, y0, t1, label, ns=(4, 16), on_matrix=None):
     """fixed_steps(x, t1, n, embedded) of every build against the mp restatement, n = 4 and 16, both solutions; the largest ratio of
-    deviation to tolerance"""
+    deviation to tolerance.  on_matrix(step, W): sees the reference's iteration matrices, the order-4 run's first."""
     k = REF.rate_constants(reactions, x, "linear")
     worst = 0.0
-    for n in (4, 16):
+    for n in ns:
         for embedded in (False, True):
-            ref, scale, tol = REF.fixed_step_reference(S, reactions, k, y0, 0.0, t1, n, embedded)
+            ref, scale, tol = REF.fixed_step_reference(S, reactions, k, y0, 0.0, t1, n, embedded, on_matrix=on_matrix)
             assert all(np.isfinite(float(v)) for v in ref) and float(scale) <= 1e3 * np.max(y0)      # (the input is tame: on the reference)
             for like in builds:
                 dev = REF.deviation(like.fixed_steps(x, t1, n, embedded), ref, scale)
@@ -107,7 +123,7 @@ def test_at_most_two_networks_were_replaced_and_the_grammar_is_still_covered():
     nets = [resolved(i)[0] for i in INDEX]
     assert len(_REPLACED) <= 2, _REPLACED
     assert not G.coverage_gaps(nets), G.coverage_gaps(nets)
-    for lanes in (1, 16, 32):                                                  # and every build meets invariants that more than one species shares
+    for lanes in G.BUILDS:                                                     # and every build meets invariants that more than one species shares
         shared = sum(int(np.sum(np.sum(np.abs(null_space(REF.stoichiometry(n.S, n.reactions)[0].T.astype(float))) > 1e-9, axis=0) > 1))
                      for n in nets if n.lanes == lanes)
         print("%d lanes: %d invariants over more than one species" % (lanes, shared))
@@ -117,7 +133,7 @@ def test_at_most_two_networks_were_replaced_and_the_grammar_is_still_covered():
 
 
 # ---------------------------------------------------------------------------------------------------- edges
-EDGE = {1: 4, 16: 11}          # the case each build's edge tests use (S = 5 with one lane, S = 9 with 16 lanes)
+EDGE = {1: 4, 16: 11, 32: 19, 64: 29}          # the case each build's edge tests use (S = 5 with one lane, 9 with 16 lanes, 20 with 32, 33 with 64)
 
 
 def _close(sim, ref, rtol, factor=10):
@@ -129,7 +145,7 @@ def _edge(lanes):
     return net, net.points(4, seed=3)
 
 
-@pytest.mark.parametrize("lanes", [1, 16])
+@pytest.mark.parametrize("lanes", sorted(EDGE))
 def test_edge_t0_and_repeated_output_times(lanes):
     net, X = _edge(lanes)
     kw = dict(rtol=1e-9, atol=1e-9, max_steps=20000)
@@ -143,7 +159,7 @@ def test_edge_t0_and_repeated_output_times(lanes):
             assert np.array_equal(sim[:, 0], np.tile(net.y0, (len(X), 1)))
 
 
-@pytest.mark.parametrize("lanes", [1, 16])
+@pytest.mark.parametrize("lanes", sorted(EDGE))
 def test_edge_a_single_output_time_equal_to_t0_is_the_likelihood_of_y0_and_takes_no_step(lanes):
     from scipy.stats import norm
     net, X = _edge(lanes)
@@ -158,7 +174,7 @@ def test_edge_a_single_output_time_equal_to_t0_is_the_likelihood_of_y0_and_takes
         assert np.all(np.abs(L - ref) <= 1e-12 * np.sum(np.abs(norm(loc=data[:, 0], scale=sd[:, 0]).logpdf(obs @ net.y0)))), (L, ref)
 
 
-@pytest.mark.parametrize("lanes", [1, 16])
+@pytest.mark.parametrize("lanes", sorted(EDGE))
 def test_edge_nan_data_and_negative_non_integer_observable_weights(lanes):
     """Observables with weights like -0.73 against Radau; the likelihood against scipy.stats.norm over the observed entries."""
     from scipy.stats import norm
@@ -181,7 +197,7 @@ def test_edge_nan_data_and_negative_non_integer_observable_weights(lanes):
         assert np.isfinite(like(x)) and abs(like(x) - np.sum(terms)) <= 1e-12 * np.sum(np.abs(terms))
 
 
-@pytest.mark.parametrize("lanes", [1, 16])
+@pytest.mark.parametrize("lanes", sorted(EDGE))
 def test_edge_ndim_above_the_highest_parameter_index_and_wider_rows(lanes):
     net, X = _edge(lanes)
     kw = dict(rtol=1e-9, atol=1e-9, max_steps=20000)
@@ -196,7 +212,7 @@ def test_edge_ndim_above_the_highest_parameter_index_and_wider_rows(lanes):
         like.batch(X)
 
 
-@pytest.mark.parametrize("lanes", [1, 16])
+@pytest.mark.parametrize("lanes", sorted(EDGE))
 def test_edge_a_log10_parameter_of_minus_400_switches_its_reactions_off(lanes):
     """10**-400 is 0: finite, and the network without the reactions that parameter drives."""
     net, X = _edge(lanes)
@@ -214,7 +230,10 @@ def test_edge_a_log10_parameter_of_minus_400_switches_its_reactions_off(lanes):
 
 
 # ---------------------------------------------------------------------------------------------------- metamorphic
-@pytest.mark.parametrize("i", [3, 7, 11, 14, 18, 23], ids=[IDS[i] for i in (3, 7, 11, 14, 18, 23)])
+RELABELLED = [3, 7, 11, 14, 18, 23, 31, 35]                                    # (the last two: 64 lanes, S = 48 and 64)
+
+
+@pytest.mark.parametrize("i", RELABELLED, ids=[IDS[i] for i in RELABELLED])
 def test_relabelled_species_and_reordered_reactions_give_the_same_states(i):
     """new species perm[s] is old species s: rows move between lanes and the pivot sequence changes; then the reactions in another order"""
     net, _ = resolved(i)
@@ -235,18 +254,91 @@ def test_relabelled_species_and_reordered_reactions_give_the_same_states(i):
         assert not np.array_equal(perm, np.arange(net.S)) and not np.array_equal(order, np.arange(net.R))
 
 
-# ---------------------------------------------------------------------------------------------------- tied pivots
-def test_tied_pivot_candidates_in_all_three_builds():
-    ties = []
+# ---------------------------------------------------------------------------------------------------- large steps
+LARGE = list(range(len(G.LARGE_STEP_CASES)))
+_PIVOTS, _LARGE_WORST = {}, {}           # per large-step case: the reference's pivot rows of every step; deviation / tolerance
+# The tolerance is sized by ONE float64 ordering of the operations (numpy's).  Where W is badly conditioned that sample says little: on
+# a one-lane network of this family with cond(W) = 2e6 (seed 5, S = 8, h = 16) numpy's own deviation from mp went from 2e-14 to 6e-12
+# when nothing but the species' labels changed, a spread of 300 where the formula allows 64.  So a large-step input has cond(W) <= 1e3
+# in every step: then cond * eps = 2e-13 bounds what any backward-stable ordering may lose, and the 16 eps floor times 64 is of that size.
+MAX_CONDITION = 1e3
+
+
+def _pivots(j):
+    """The pivot rows (REF.pivot_rows) of every step's W in the mp integration of large-step case j: from the reference alone"""
+    if j not in _PIVOTS:
+        net, (_, _, _, _, t1, n) = G.large_step_network(j), G.LARGE_STEP_CASES[j]
+        found = []
+        REF.rodas4_fixed_mp(net.S, net.reactions, REF.rate_constants(net.reactions, net.nominal(), "linear"), net.y0, 0.0, t1, n,
+                            on_matrix=lambda step, W: found.append(REF.pivot_rows(W)))
+        _PIVOTS[j] = found
+    return _PIVOTS[j]
+
+
+def _off_diagonal(piv):
+    """[(column, row)] of the pivots that left the diagonal"""
+    return [(int(c), int(piv[c])) for c in np.flatnonzero(piv != np.arange(len(piv)))]
+
+
+@pytest.mark.parametrize("j", LARGE, ids=[G.large_step_network(j).name for j in LARGE])
+def test_large_steps_whose_pivots_leave_the_diagonal_equal_the_mp_restatement_to_rounding(j):
+    """h = 4 .. 16 on a network that stays tame there: in at least one step three or more columns pivot off the diagonal (a condition on
+    the reference's matrices), and both solutions are the mp restatement's to the tolerance its float64 restatement sizes -- a
+    permutation that is wrong anywhere (the arg-max, the packed piv bytes, pos, the solves' b[piv[k]], the wave's broadcast of the
+    pivot lane) is an error of the order of the solution."""
+    net, (_, _, _, _, t1, n) = G.large_step_network(j), G.LARGE_STEP_CASES[j]
+    found, cond = [], []
 
     def on_matrix(step, W):
-        for q in range(4):
-            mag = [abs(W[s][q]) for s in range(4)]
-            top = [s for s in range(4) if mag[s] == max(mag)]
-            if len(top) >= 2 and q not in top:
-                ties.append((step, q, top))
-    REF.rodas4_fixed_mp(4, G.TIED_REACTIONS, REF.rate_constants(G.TIED_REACTIONS, G.TIED_X, "linear"), G.TIED_Y0, 0.0, 4.0, 4, on_matrix=on_matrix)
-    print("tied pivot candidates (step, column, rows):", ties)
-    assert ties                                                                # (a condition on the reference's matrices, not on the code under test)
-    worst = _check_fixed_steps([G.tied(lanes) for lanes in (1, 16, 32)], 4, G.TIED_REACTIONS, G.TIED_X, G.TIED_Y0, 4.0, "tied")
-    print("tied: largest deviation / tolerance %.3f" % worst)
+        cond.append(float(np.linalg.cond(np.array([[float(v) for v in row] for row in W]))))
+        assert cond[-1] <= MAX_CONDITION, (net.name, step, cond[-1])           # (on the reference, before any build is looked at)
+        if len(found) < n:
+            found.append(REF.pivot_rows(W))
+    worst = _check_fixed_steps([net.like()], net.S, net.reactions, net.nominal(), net.y0, t1, net.name, ns=(n,), on_matrix=on_matrix)
+    _PIVOTS[j], _LARGE_WORST[j] = found, worst
+    counts = [len(_off_diagonal(p)) for p in found]
+    print("%s, h = %g: off-diagonal pivot columns per step %s, largest condition of W %.0f, largest deviation / tolerance %.3f"
+          % (net.name, t1 / n, counts, max(cond), worst))
+    assert len(found) == n and len(cond) == 2 * n and max(counts) >= 3
+
+
+@pytest.mark.parametrize("lanes", G.BUILDS)
+def test_large_step_cases_pivot_off_the_diagonal_in_every_quarter_of_the_columns(lanes):
+    """Over a build's large-step cases a column of each quarter of 0..S-1 pivots off the diagonal, so every int of packed piv bytes
+    carries one that is not its own index; with 64 lanes also a pivot with column and row both >= 32, and one with column and row on
+    opposite sides of 32 (the wave's halves).  All from the reference's matrices."""
+    quarters, high, across, counts = set(), False, False, {}
+    for j in [j for j in LARGE if G.LARGE_STEP_CASES[j][0] == lanes]:
+        S = G.LARGE_STEP_CASES[j][1]
+        off = [cr for piv in _pivots(j) for cr in _off_diagonal(piv)]
+        counts[G.large_step_network(j).name] = [len(_off_diagonal(piv)) for piv in _pivots(j)]
+        quarters |= {4 * c // S for c, _ in off}
+        high |= any(c >= 32 and r >= 32 for c, r in off)
+        across |= any((c >= 32) != (r >= 32) for c, r in off)
+    ran = [_LARGE_WORST[j] for j in LARGE if G.LARGE_STEP_CASES[j][0] == lanes and j in _LARGE_WORST]
+    print("%d lanes, large steps: off-diagonal pivot columns per step %s; largest deviation / tolerance %s (of the tests that ran before)"
+          % (lanes, counts, "%.3f" % max(ran) if ran else "-"))
+    assert quarters == {0, 1, 2, 3}, quarters
+    if lanes == 64:
+        assert high and across
+
+
+# ---------------------------------------------------------------------------------------------------- tied pivots
+def test_tied_pivot_candidates_in_all_four_builds():
+    """The 4-species network for one lane and groups of 16 and 32; for the wave its copy behind an inert chain (tests/ode_grammar.py),
+    where the tied rows are 34 and 35 and the column is 32"""
+    for builds in ((1, 16, 32), (64,)):
+        S, reactions, y0, abcd = G.tied_network(builds[0])
+        ties = []
+
+        def on_matrix(step, W):
+            for q in abcd:
+                mag = [abs(W[s][q]) for s in abcd]
+                top = [int(abcd[s]) for s in range(4) if mag[s] == max(mag)]
+                if len(top) >= 2 and q not in top:
+                    ties.append((step, int(q), top))
+        REF.rodas4_fixed_mp(S, reactions, REF.rate_constants(reactions, G.TIED_X, "linear"), y0, 0.0, 4.0, 4, on_matrix=on_matrix)
+        print("tied pivot candidates (step, column, rows):", ties)
+        assert ties                                                            # (a condition on the reference's matrices, not on the code under test)
+        worst = _check_fixed_steps([G.tied(lanes) for lanes in builds], S, reactions, G.TIED_X, y0, 4.0, "tied")
+        print("tied @%s: largest deviation / tolerance %.3f" % (builds, worst))
