@@ -1,19 +1,19 @@
-// dz_ode_group.h -- dz_ode.h's solver for networks of 9..64 species: several lanes integrate one point together.  Two shapes:
-//     Group<Net, 16 | 32>   a GROUP of L = 16 or 32 lanes per point, for up to 32 species (likelihoods.MassActionODELogLike(...,
-//                           lanes_per_point=16 | 32)); a group never straddles a wave;
-//     Group<Net, 64>        a whole 64-lane WAVE per point, for 33..64 species (lanes_per_point=64): see "a wave per point" below.
+// dz_ode_group.h -- dz_ode.h's solver for networks of 9..64 species: a GROUP of L = 16, 32 or 64 lanes integrates one point together
+// (likelihoods.MassActionODELogLike(..., lanes_per_point=16 | 32) for up to 32 species, lanes_per_point=64, a whole wave per point, for
+// 33..64).  A group never straddles a wave.  There is ONE solver, Group<Net, L> and the functions it calls, for the three lane counts;
+// L decides only how lanes talk to each other (Lanes<L>) and where the replicated state lives (Replica<Net, L>): see "a wave per point".
 // The method is dz_ode.h's, and so is the code: its stepping loop
 // (dzode::integrate: step controller, negativity rule, max_steps per output interval, exact landing on the output times, events, -inf on
 // any failure) runs here on the shape Group below, with Rodas4's coefficients and the start step's formulas; what changes is who holds what.  Lane r of a group (r = threadIdx.x % L) owns
 //     row r of W = I / (h gamma) - J in registers (S doubles, constant column indices after unrolling),
-//     entry r of y, of the stage argument u and of k1..k6,
-//     one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled by S group broadcasts per stage);
-// lanes r >= S idle: they carry zeros, never pivot, and are masked out of every reduction.  The rate constants (up to 128; 256 for a wave
+//     entry r of y, of the stage argument u and of k1..k6;
+// every lane reads, at constant indices, one replicated copy of the state the right-hand side is evaluated at (S doubles, refilled once
+// per stage): with 16 or 32 lanes its own S registers, with 64 lanes the wave's S doubles of LDS.
+// Lanes r >= S idle: they carry zeros, never pivot, and are masked out of every reduction.  The rate constants (up to 128; 256 for a wave
 // per point) are computed once per point, reaction j by lane j % L, and kept in static LDS (256 / L points x (R + 1) doubles per block).
-// A wave per point keeps the row in registers too, but the replicated state in LDS and its broadcasts in scalar registers.
 //
-// Linear algebra over the group (ds_bpermute through __shfl / __shfl_xor with width L; no LDS round trip, no MFMA: a pivoted f64 LU of
-// S <= 32 is a chain of S dependent column steps, latency- and not throughput-bound):
+// Linear algebra over the group (16 | 32 lanes: ds_bpermute through __shfl / __shfl_xor with width L; no LDS round trip, no MFMA: a pivoted
+// f64 LU of S <= 64 is a chain of S dependent column steps, latency- and not throughput-bound):
 //   LU, implicit partial pivoting: per column k a butterfly arg-max of |w[k]| over the lanes that have not pivoted yet (equal maxima:
 //     the lowest row; a NaN counts as +inf), the pivot's reciprocal and its row right of k broadcast, one multiplier and one rank-1 row
 //     update per remaining lane.  Rows do not move: piv[k] is the row that pivoted in column k, pos the column a row pivoted in.
@@ -134,204 +134,12 @@ struct Lanes {
         const unsigned long long mask = (L == 32 ? 0xffffffffull : 0xffffull) << ((threadIdx.x & 63) & ~(L - 1));
         return (__ballot(p) & mask) != 0;
     }
-    template <int S>
-    __device__ __forceinline__ static void gather(double own, double* all)
-    {
-#pragma unroll
-        for (int q = 0; q < S; ++q) all[q] = from(own, q);
-    }
-};
-
-template <class Net, int L>
-__device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
-{
-    bool good = true;
-    for (int j = r; j < Net::R; j += L) {
-        bool g;
-        ks[j] = rate_constant<Net>(j, x, g);
-        good = good && g;
-    }
-    return !Lanes<L>::any(!(good && monomials_live<Net>(x)));
-}
-
-// piv: the row that pivoted in column k, four columns to an int
-__device__ __forceinline__ int pivot_row(const int* piv, int k) { return (piv[k >> 2] >> (8 * (k & 3))) & 0xff; }
-
-template <int S, int L>
-__device__ __forceinline__ bool group_lu_factor(double* w, int* piv, int& pos, int r)
-{
-    bool ok = true, done = r >= S;
-    pos = -1;
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        double key = done ? -1.0 : pivot_key(w[k]);
-        int p = r;
-#pragma unroll
-        for (int m = 1; m < L; m <<= 1) {
-            const double okey = __shfl_xor(key, m, L);
-            const int op = __shfl_xor(p, m, L);
-            const bool take = (okey > key) | ((okey == key) & (op < p));
-            key = take ? okey : key;
-            p = take ? op : p;
-        }
-        piv[k >> 2] = (k & 3) ? piv[k >> 2] | (p << (8 * (k & 3))) : p;
-        ok = ok && key != 0.0;
-        const bool me = p == r, upd = !done && !me;
-        const double inv = Lanes<L>::from(1.0 / w[k], p);
-        const double l = w[k] * inv;
-        w[k] = me ? inv : (upd ? l : w[k]);
-#pragma unroll
-        for (int c = k + 1; c < S; ++c) {
-            const double pc = Lanes<L>::from(w[c], p);
-            w[c] = upd ? w[c] - l * pc : w[c];
-        }
-        done = done || me;
-        pos = me ? k : pos;
-    }
-    return ok;
-}
-
-template <int S, int L>
-__device__ __forceinline__ double group_lu_solve(const double* w, const int* pivp, int pos, int r, double b)
-{
-    int piv[(S + 3) / 4];          // (opaque copies: the S broadcast addresses and 3 S lane masks the compiler would otherwise carry from
-#pragma unroll                     //  the factorisation through all six solves are rebuilt here from these few registers)
-    for (int i = 0; i < (S + 3) / 4; ++i) piv[i] = row_index(pivp[i]);
-    pos = row_index(pos);
-    r = row_index(r);
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        const double bk = Lanes<L>::from(b, pivot_row(piv, k));
-        b = pos > k ? b - w[k] * bk : b;
-    }
-    double x = 0.0;
-#pragma unroll
-    for (int k = S - 1; k >= 0; --k) {
-        const double xk = Lanes<L>::from(b * w[k], pivot_row(piv, k));
-        b = (pos >= 0 && pos < k) ? b - w[k] * xk : b;
-        x = r == k ? xk : x;
-    }
-    return x;
-}
-
-// w[0..Q) = row r of I / (h gamma) - J, column by column.  A recursion over the column and not a loop: every column index must be a
-// constant (w lives in registers), and a loop around the whole generated switch is too long for the compiler to unroll on its own.
-// zk is an offset (always 0) into the rate constants: R of them are read from LDS where they are used, not kept in registers across steps.
-template <class Net, int Q>
-struct JacobianRow {
-    __device__ __forceinline__ static void fill(double* w, int& rj, int& zk, const double* ks, const double* yr, int r, double fac)
-    {
-        JacobianRow<Net, Q - 1>::fill(w, rj, zk, ks, yr, r, fac);
-        double m = -Net::jac_entry(rj, Q - 1, ks + zk, yr);
-        DZODE_SUM_FENCE(m, rj, zk);             // (column by column, for the same reason as inside a sum)
-        w[Q - 1] = Q - 1 == r ? m + fac : m;
-    }
-};
-template <class Net>
-struct JacobianRow<Net, 0> {
-    __device__ __forceinline__ static void fill(double*, int&, int&, const double*, const double*, int, double) {}
-};
-
-// One step of size h: this lane's entry of the order-4 solution and the group's err2.  False if the iteration matrix is singular.
-template <class Net, int L>
-__device__ __forceinline__ bool group_step(const double* ks, double y, double h, double rtol, double atol, int r, double& ynew, double& err2)
-{
-    constexpr int S = Net::S;
-    double yr[S], w[S];
-    int piv[(S + 3) / 4], pos;
-    const double fac = 1.0 / (h * Rodas4::gamma), ih = 1.0 / h;
-    Lanes<L>::template gather<S>(y, yr);
-    int rj = row_index(r), zk = row_index(0);
-    JacobianRow<Net, S>::fill(w, rj, zk, ks, yr, r, fac);
-    const bool ok = group_lu_factor<S, L>(w, piv, pos, r);
-    double k1 = 0.0, k2 = 0.0, k3 = 0.0, k4 = 0.0, k5 = 0.0, f = 0.0, arg = y;
-#pragma unroll 1
-    for (int st = 0; st < 6; ++st) {          // (one copy of the right-hand side and of the solve in the code object, not six)
-        arg = stage_arg(st, y, arg, k1, k2, k3, k4, k5);
-        Lanes<L>::template gather<S>(arg, yr);          // (also at stage 0: the copy the Jacobian used is not kept alive across the LU)
-        f = Net::rhs_row(row_index(r), ks + row_index(0), yr);
-        if (st > 0) f = f + stage_add(st, ih, k1, k2, k3, k4, k5);
-        f = group_lu_solve<S, L>(w, piv, pos, r, f);
-        k1 = st == 0 ? f : k1;
-        k2 = st == 1 ? f : k2;
-        k3 = st == 2 ? f : k3;
-        k4 = st == 3 ? f : k4;
-        k5 = st == 4 ? f : k5;
-    }
-    ynew = arg + f;                            // arg: y5 + k5, f: k6
-    const double sk = atol + rtol * dmax(dabs(y), dabs(ynew));
-    const double q = f / sk;
-    err2 = Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
-    return ok;
-}
-
-template <int S, int L>
-__device__ __forceinline__ double group_wnorm2(double v, double y, double rtol, double atol, int r)
-{
-    const double q = v / (atol + rtol * dabs(y));
-    return Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
-}
-
-template <class Net, int L>
-__device__ __forceinline__ double group_start_step(const double* ks, double y, double rtol, double atol, double span, int r)
-{
-    constexpr int S = Net::S;
-    double yr[S];
-    Lanes<L>::template gather<S>(y, yr);
-    const double f0 = Net::rhs_row(row_index(r), ks, yr);
-    const double d0 = group_wnorm2<S, L>(y, y, rtol, atol, r), d1 = group_wnorm2<S, L>(f0, y, rtol, atol, r);
-    const double h0 = start_h0(d0, d1, span);
-    Lanes<L>::template gather<S>(y + h0 * f0, yr);
-    const double f1 = Net::rhs_row(row_index(r), ks, yr) - f0;
-    return start_h(h0, d1, group_wnorm2<S, L>(f1, y, rtol, atol, r), span);
-}
-
-// The group's shape for dz_ode.h's integrate: lane r's entry of the state.  Every lane of the group returns the same value.  The caller's
-// live = false (a point past the batch's end, or a rate constant that is not finite): no step is taken, -inf.
-template <class Net, int L>
-struct Group {
-    static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
-    static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
-    typedef double State;
-    const double* ks;                                  // the point's rate constants (LDS)
-    int r;
-    const double* x;                                   // the point's row (read only by a network with monomials)
-    __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? start_amount<Net>(r, x, blk[6 + r]) : 0.0; }
-    __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
-    {
-        return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
-    }
-    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // the steady-state test's norm of f(y), group-wide
-    {
-        double yr[S];
-        Lanes<L>::template gather<S>(y, yr);
-        return group_wnorm2<S, L>(Net::rhs_row(row_index(r), ks, yr), y, rtol, atol, r);
-    }
-    __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
-    {
-        return group_step<Net, L>(ks, y, h, rtol, atol, r, yn, err2);
-    }
-    __device__ __forceinline__ bool all_finite(double yn, bool fin) const { return fin && !Lanes<L>::any(!finite(yn)); }
-    __device__ __forceinline__ bool any_negative(double yn, double y, double rtol, double atol) const
-    {
-        return Lanes<L>::any(yn < -(atol + rtol * dabs(y)));
-    }
-    __device__ __forceinline__ void observe(double y, double* o) const
-    {
-        double yr[S];
-        Lanes<L>::template gather<S>(y, yr);
-        observe_scaled<Net>(x, yr, o);
-    }
-    __device__ __forceinline__ void apply(double& y, int species, double factor, double amount) const
-    {
-        y = r == species ? factor * y + amount : y;
-    }
 };
 
 // ---------------------------------------------------------------- a wave per point: 33..64 species
-// The same method, pivot rule, column-oriented solves, summation tree and roundings as above, with L = 64: HostGroup<Net, 64> is its twin.
-// What changes is where things live, because a row of 64 doubles (128 registers) and a replicated state beside it do not fit 512:
-//     row r of W                      in lane r's registers, as above;
+// The same solver with L = 64: the same method, pivot rule, column-oriented solves, summation tree and roundings, and HostGroup<Net, 64>
+// is its twin.  Two things are placed differently, because a row of 64 doubles (128 registers) and a replicated state beside it do not
+// fit 512 registers:
 //     the replicated state            in LDS, S doubles per wave behind the wave's rate constants (wave_state): lane r writes entry r,
 //                                     every lane reads entry q at a constant q -- one address per read, a broadcast without a bank conflict.
 //                                     Only this wave touches them, so a wave-scope fence orders the write and the reads; there is NO
@@ -340,7 +148,7 @@ struct Group {
 //     pivot reciprocal, pivot row,    the pivot index is the same in every lane of the wave (the butterfly arg-max is over a total
 //     b[piv[k]] in the solves         order), so it goes to a scalar register (readfirstlane) and the value is read with v_readlane into
 //                                     scalar registers: no LDS-crossbar round trip on the dependent chain, and piv[] costs no VGPR.
-// The arg-max, the sums and the ballots span the wave and need no mask.
+// Row r of W stays in lane r's registers.  The arg-max, the sums and the ballots span the wave and need no mask.
 template <>
 struct Lanes<64> {
     // lane src of this wave; src must hold the same value in every lane (it is read from the first active one)
@@ -385,10 +193,46 @@ __device__ __forceinline__ void wave_publish(double* ys, int r, double v)
     __builtin_amdgcn_wave_barrier();
 }
 
-constexpr int WAVE_LU_AHEAD = 8;          // columns of one rank-1 update whose pivot-row broadcasts may be in flight together
+constexpr int WAVE_LU_AHEAD = 8;          // 64 lanes: columns of one rank-1 update whose pivot-row broadcasts may be in flight together
 
-template <int S>
-__device__ __forceinline__ bool wave_lu_factor(double* w, int* piv, int& pos, int r)
+// ---------------------------------------------------------------- the solver, for every L
+// The replicated state: fill(r, own) makes every lane's entry visible to the group, y is where every lane then reads the S entries.
+// ks: the point's row of LDS (group_lds_row).  (fill returns nothing and the callers read through the member: a pointer held in a local
+// of the stage loop was enough to change the register allocation of the loop.)
+template <class Net, int L>
+struct Replica {                              // 16 | 32 lanes: S registers per lane, refilled by S group broadcasts
+    double y[Net::S];
+    __device__ __forceinline__ explicit Replica(double*) {}
+    __device__ __forceinline__ void fill(int, double own)
+    {
+#pragma unroll
+        for (int q = 0; q < Net::S; ++q) y[q] = Lanes<L>::from(own, q);
+    }
+};
+template <class Net>
+struct Replica<Net, 64> {                     // a wave: its S doubles of LDS; a wave that is not live touches nothing but its own row
+    double* y;
+    __device__ __forceinline__ explicit Replica(double* ks) : y(wave_state<Net>(ks)) {}
+    __device__ __forceinline__ void fill(int r, double own) { wave_publish<Net::S>(y, r, own); }
+};
+
+template <class Net, int L>
+__device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
+{
+    bool good = true;
+    for (int j = r; j < Net::R; j += L) {
+        bool g;
+        ks[j] = rate_constant<Net>(j, x, g);
+        good = good && g;
+    }
+    return !Lanes<L>::any(!(good && monomials_live<Net>(x)));
+}
+
+// piv: the row that pivoted in column k, four columns to an int
+__device__ __forceinline__ int pivot_row(const int* piv, int k) { return (piv[k >> 2] >> (8 * (k & 3))) & 0xff; }
+
+template <int S, int L>
+__device__ __forceinline__ bool group_lu_factor(double* w, int* piv, int& pos, int r)
 {
     bool ok = true, done = r >= S;
     pos = -1;
@@ -397,26 +241,27 @@ __device__ __forceinline__ bool wave_lu_factor(double* w, int* piv, int& pos, in
         double key = done ? -1.0 : pivot_key(w[k]);
         int p = r;
 #pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const double okey = __shfl_xor(key, m, 64);
-            const int op = __shfl_xor(p, m, 64);
+        for (int m = 1; m < L; m <<= 1) {
+            const double okey = __shfl_xor(key, m, L);
+            const int op = __shfl_xor(p, m, L);
             const bool take = (okey > key) | ((okey == key) & (op < p));
             key = take ? okey : key;
             p = take ? op : p;
         }
-        int ps = __builtin_amdgcn_readfirstlane(p);          // every lane holds the same p: the arg-max of a total order over the whole wave
-        piv[k >> 2] = (k & 3) ? piv[k >> 2] | (ps << (8 * (k & 3))) : ps;
+        if constexpr (L == 64) p = __builtin_amdgcn_readfirstlane(p);          // every lane holds the same p: the arg-max of a total order over the whole wave
+        piv[k >> 2] = (k & 3) ? piv[k >> 2] | (p << (8 * (k & 3))) : p;
         ok = ok && key != 0.0;
-        const bool me = ps == r, upd = !done && !me;
-        const double inv = Lanes<64>::from(1.0 / w[k], ps);
+        const bool me = p == r, upd = !done && !me;
+        const double inv = Lanes<L>::from(1.0 / w[k], p);
         double l = w[k] * inv;
         w[k] = me ? inv : (upd ? l : w[k]);
 #pragma unroll
         for (int c = k + 1; c < S; ++c) {
-            // every WAVE_LU_AHEAD columns the last updated entry, the multiplier and the pivot's lane pass through an empty asm statement
-            // together: the next columns' readlanes depend on it and are not all issued (into scalar registers) ahead of the updates
-            if ((c - k - 1) % WAVE_LU_AHEAD == 0 && c > k + 1) asm volatile("" : "+v"(w[c - 1]), "+v"(l), "+s"(ps));
-            const double pc = Lanes<64>::from(w[c], ps);
+            // 64 lanes: every WAVE_LU_AHEAD columns the last updated entry, the multiplier and the pivot's lane pass through an empty asm
+            // statement together: the next columns' readlanes depend on it and are not all issued (into scalar registers) ahead of the updates
+            if constexpr (L == 64)
+                if ((c - k - 1) % WAVE_LU_AHEAD == 0 && c > k + 1) asm volatile("" : "+v"(w[c - 1]), "+v"(l), "+s"(p));
+            const double pc = Lanes<L>::from(w[c], p);
             w[c] = upd ? w[c] - l * pc : w[c];
         }
         done = done || me;
@@ -425,110 +270,140 @@ __device__ __forceinline__ bool wave_lu_factor(double* w, int* piv, int& pos, in
     return ok;
 }
 
-template <int S>
-__device__ __forceinline__ double wave_lu_solve(const double* w, const int* pivp, int pos, int r, double b)
+template <int S, int L>
+__device__ __forceinline__ double group_lu_solve(const double* w, const int* pivp, int pos, int r, double b)
 {
-    int piv[(S + 3) / 4];          // (opaque copies, as in group_lu_solve; here in scalar registers)
-#pragma unroll
-    for (int i = 0; i < (S + 3) / 4; ++i) piv[i] = uniform_index(pivp[i]);
+    int piv[(S + 3) / 4];          // (opaque copies: the S broadcast addresses and 3 S lane masks the compiler would otherwise carry from
+#pragma unroll                     //  the factorisation through all six solves are rebuilt here from these few registers; 64 lanes: scalar ones)
+    for (int i = 0; i < (S + 3) / 4; ++i) {
+        if constexpr (L == 64) piv[i] = uniform_index(pivp[i]);
+        else piv[i] = row_index(pivp[i]);
+    }
     pos = row_index(pos);
     r = row_index(r);
 #pragma unroll
     for (int k = 0; k < S; ++k) {
-        const double bk = Lanes<64>::from(b, pivot_row(piv, k));
+        const double bk = Lanes<L>::from(b, pivot_row(piv, k));
         b = pos > k ? b - w[k] * bk : b;
     }
     double x = 0.0;
 #pragma unroll
     for (int k = S - 1; k >= 0; --k) {
-        const double xk = Lanes<64>::from(b * w[k], pivot_row(piv, k));
+        const double xk = Lanes<L>::from(b * w[k], pivot_row(piv, k));
         b = (pos >= 0 && pos < k) ? b - w[k] * xk : b;
         x = r == k ? xk : x;
     }
     return x;
 }
 
-// group_step with the replicated state in LDS (ys) and the wave's LU.
+// w[0..Q) = row r of I / (h gamma) - J, column by column.  A recursion over the column and not a loop: every column index must be a
+// constant (w lives in registers), and a loop around the whole generated switch is too long for the compiler to unroll on its own.
+// zk is an offset (always 0) into the rate constants: R of them are read from LDS where they are used, not kept in registers across steps.
+template <class Net, int Q>
+struct JacobianRow {
+    __device__ __forceinline__ static void fill(double* w, int& rj, int& zk, const double* ks, const double* yr, int r, double fac)
+    {
+        JacobianRow<Net, Q - 1>::fill(w, rj, zk, ks, yr, r, fac);
+        double m = -Net::jac_entry(rj, Q - 1, ks + zk, yr);
+        DZODE_SUM_FENCE(m, rj, zk);             // (column by column, for the same reason as inside a sum)
+        w[Q - 1] = Q - 1 == r ? m + fac : m;
+    }
+};
 template <class Net>
-__device__ __forceinline__ bool wave_step(const double* ks, double* ys, double y, double h, double rtol, double atol, int r, double& ynew, double& err2)
+struct JacobianRow<Net, 0> {
+    __device__ __forceinline__ static void fill(double*, int&, int&, const double*, const double*, int, double) {}
+};
+
+// One step of size h: this lane's entry of the order-4 solution and the group's err2.  False if the iteration matrix is singular.
+template <class Net, int L>
+__device__ __forceinline__ bool group_step(double* ks, double y, double h, double rtol, double atol, int r, double& ynew, double& err2)
 {
     constexpr int S = Net::S;
+    Replica<Net, L> rep(ks);
     double w[S];
     int piv[(S + 3) / 4], pos;
     const double fac = 1.0 / (h * Rodas4::gamma), ih = 1.0 / h;
-    wave_publish<S>(ys, r, y);
+    rep.fill(r, y);
     int rj = row_index(r), zk = row_index(0);
-    JacobianRow<Net, S>::fill(w, rj, zk, ks, ys, r, fac);
-    const bool ok = wave_lu_factor<S>(w, piv, pos, r);
+    JacobianRow<Net, S>::fill(w, rj, zk, ks, rep.y, r, fac);
+    const bool ok = group_lu_factor<S, L>(w, piv, pos, r);
     double k1 = 0.0, k2 = 0.0, k3 = 0.0, k4 = 0.0, k5 = 0.0, f = 0.0, arg = y;
 #pragma unroll 1
-    for (int st = 0; st < 6; ++st) {
+    for (int st = 0; st < 6; ++st) {          // (one copy of the right-hand side and of the solve in the code object, not six)
         arg = stage_arg(st, y, arg, k1, k2, k3, k4, k5);
-        wave_publish<S>(ys, r, arg);
-        f = Net::rhs_row(row_index(r), ks + row_index(0), ys);
+        rep.fill(r, arg);                         // (also at stage 0: registers the Jacobian read are not kept alive across the LU)
+        f = Net::rhs_row(row_index(r), ks + row_index(0), rep.y);
         if (st > 0) f = f + stage_add(st, ih, k1, k2, k3, k4, k5);
-        f = wave_lu_solve<S>(w, piv, pos, r, f);
+        f = group_lu_solve<S, L>(w, piv, pos, r, f);
         k1 = st == 0 ? f : k1;
         k2 = st == 1 ? f : k2;
         k3 = st == 2 ? f : k3;
         k4 = st == 3 ? f : k4;
         k5 = st == 4 ? f : k5;
     }
-    ynew = arg + f;
+    ynew = arg + f;                            // arg: y5 + k5, f: k6
     const double sk = atol + rtol * dmax(dabs(y), dabs(ynew));
     const double q = f / sk;
-    err2 = Lanes<64>::sum(r < S ? q * q : 0.0) * (1.0 / S);
+    err2 = Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
     return ok;
 }
 
-template <class Net>
-__device__ __forceinline__ double wave_start_step(const double* ks, double* ys, double y, double rtol, double atol, double span, int r)
+template <int S, int L>
+__device__ __forceinline__ double group_wnorm2(double v, double y, double rtol, double atol, int r)
 {
-    constexpr int S = Net::S;
-    wave_publish<S>(ys, r, y);
-    const double f0 = Net::rhs_row(row_index(r), ks, ys);
-    const double d0 = group_wnorm2<S, 64>(y, y, rtol, atol, r), d1 = group_wnorm2<S, 64>(f0, y, rtol, atol, r);
-    const double h0 = start_h0(d0, d1, span);
-    wave_publish<S>(ys, r, y + h0 * f0);
-    const double f1 = Net::rhs_row(row_index(r), ks, ys) - f0;
-    return start_h(h0, d1, group_wnorm2<S, 64>(f1, y, rtol, atol, r), span);
+    const double q = v / (atol + rtol * dabs(y));
+    return Lanes<L>::sum(r < S ? q * q : 0.0) * (1.0 / S);
 }
 
-// The wave's shape for dz_ode.h's integrate: Group's members on the functions above.  ks: the wave's row of LDS, R + 1 rate constants
-// and S doubles of state (group_lds_row); a wave that is not live takes no step and touches nothing but its own row.
-template <class Net>
-struct Group<Net, 64> {
+template <class Net, int L>
+__device__ __forceinline__ double group_start_step(double* ks, double y, double rtol, double atol, double span, int r)
+{
+    constexpr int S = Net::S;
+    Replica<Net, L> rep(ks);
+    rep.fill(r, y);
+    const double f0 = Net::rhs_row(row_index(r), ks, rep.y);
+    const double d0 = group_wnorm2<S, L>(y, y, rtol, atol, r), d1 = group_wnorm2<S, L>(f0, y, rtol, atol, r);
+    const double h0 = start_h0(d0, d1, span);
+    rep.fill(r, y + h0 * f0);
+    const double f1 = Net::rhs_row(row_index(r), ks, rep.y) - f0;
+    return start_h(h0, d1, group_wnorm2<S, L>(f1, y, rtol, atol, r), span);
+}
+
+// The group's shape for dz_ode.h's integrate: lane r's entry of the state.  Every lane of the group returns the same value.  The caller's
+// live = false (a point past the batch's end, or a rate constant that is not finite): no step is taken, -inf.
+template <class Net, int L>
+struct Group {
     static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
     static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
     typedef double State;
-    double* ks;
+    double* ks;                                        // the point's row of LDS: its rate constants (64 lanes: and its state behind them)
     int r;
-    const double* x;
+    const double* x;                                   // the point's row (read only by a network with monomials)
     __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? start_amount<Net>(r, x, blk[6 + r]) : 0.0; }
     __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
     {
-        return wave_start_step<Net>(ks, wave_state<Net>(ks), y, rtol, atol, span, r);
+        return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
     }
-    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // (the state published as wave_start_step does)
+    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // the steady-state test's norm of f(y), group-wide
     {
-        double* ys = wave_state<Net>(ks);
-        wave_publish<S>(ys, r, y);
-        return group_wnorm2<S, 64>(Net::rhs_row(row_index(r), ks, ys), y, rtol, atol, r);
+        Replica<Net, L> rep(ks);
+        rep.fill(r, y);
+        return group_wnorm2<S, L>(Net::rhs_row(row_index(r), ks, rep.y), y, rtol, atol, r);
     }
     __device__ __forceinline__ bool step(double y, double h, double rtol, double atol, double& yn, double& err2) const
     {
-        return wave_step<Net>(ks, wave_state<Net>(ks), y, h, rtol, atol, r, yn, err2);
+        return group_step<Net, L>(ks, y, h, rtol, atol, r, yn, err2);
     }
-    __device__ __forceinline__ bool all_finite(double yn, bool fin) const { return fin && !Lanes<64>::any(!finite(yn)); }
+    __device__ __forceinline__ bool all_finite(double yn, bool fin) const { return fin && !Lanes<L>::any(!finite(yn)); }
     __device__ __forceinline__ bool any_negative(double yn, double y, double rtol, double atol) const
     {
-        return Lanes<64>::any(yn < -(atol + rtol * dabs(y)));
+        return Lanes<L>::any(yn < -(atol + rtol * dabs(y)));
     }
     __device__ __forceinline__ void observe(double y, double* o) const
     {
-        double* ys = wave_state<Net>(ks);
-        wave_publish<S>(ys, r, y);
-        observe_scaled<Net>(x, ys, o);
+        Replica<Net, L> rep(ks);
+        rep.fill(r, y);
+        observe_scaled<Net>(x, rep.y, o);
     }
     __device__ __forceinline__ void apply(double& y, int species, double factor, double amount) const
     {

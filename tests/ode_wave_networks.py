@@ -15,6 +15,7 @@ LANES = 64
 STARVED_MAX_STEPS = 40      # per output interval: part of the +-1 decade box (chains) and of the cascade's +-0.5 box fails, part finishes
 CHAIN_NOMINAL = W.CHAIN_NOMINAL
 CASCADE_WIDTH = CAS.WIDTH
+N_ITER, N_CHAINS = 6, 8     # the reduced size at which the cascade example's main() runs on the device and through the host twin
 
 
 @functools.lru_cache(maxsize=None)

@@ -14,6 +14,7 @@ from pydream_amd.likelihoods import MVNormalLogLike
 from pydream_amd.model import Model
 from pydream_amd.parameters import FlatParam, SampledParam
 from tests import helpers as H
+from tests.ode_support import oracle_run_dream
 from tests.test_api_cpu import multidmodel, multidmodel_uniform, onedmodel
 
 pytestmark = pytest.mark.gpu
@@ -326,25 +327,6 @@ def test_python_likelihood_over_worker_processes():
     assert out["8t"] < 0.75 * out["1t"], (out["1t"], out["8t"])
 
 
-def _oracle_run_dream(params, like, nchains, niterations, start, seed, **kwargs):
-    """run_dream's own sequence (core.py) with the CPU oracle as the engine: the checker for API-level runs."""
-    from oracle import oracle as O
-    from pydream_amd.core import _sample_dream_batched
-    restart = kwargs.pop("restart", False)
-    if restart:
-        mn = kwargs["model_name"]
-        kwargs.update(history_file=mn + '_DREAM_chain_history.npy', crossover_file=mn + '_DREAM_chain_adapted_crossoverprob.npy',
-                      gamma_file=mn + '_DREAM_chain_adapted_gammalevelprob.npy')
-    step = Dream(model=Model(like, params), variables=params, verbose=False, **kwargs)
-    pool = _setup_mp_dream_pool(nchains, niterations, step, start_pt=start, seed=seed, engine_cls=O.Engine)
-    try:
-        pool._initializer(*pool._initargs)
-        step.save_history = False
-        return _sample_dream_batched(pool.engine, step, niterations, False, 10)
-    finally:
-        pool.close(); pool.join()
-
-
 # ---- the shipped Robertson example without PySB (examples/robertson_nopysb/example_sample_robertson_nopysb_with_dream.py:58-118):
 # a stiff three-species ODE solved by scipy inside a Python likelihood, log10 rate constants under a uniform prior six decades wide,
 # "-inf when the integrator fails".  The experimental data file is replaced by data simulated from the example's own nominal constants.
@@ -393,7 +375,7 @@ def test_robertson_example_with_a_python_ode_likelihood(tmp_path, multitry, hard
     os.environ["DREAMZS_HOST_WORKERS"] = "1"
     try:
         sampled, log_ps = run_dream(params, _rob_like, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=55, **kw)
-        o_s, o_l = _oracle_run_dream(params, _rob_like, N, G, starts, 55, **kw)
+        o_s, o_l = oracle_run_dream(params, _rob_like, N, G, starts, 55, **kw)
     finally:
         del os.environ["DREAMZS_HOST_WORKERS"]
     S = np.concatenate(sampled)
@@ -427,7 +409,7 @@ def test_restart_continues_bit_for_bit_like_the_oracle(tmp_path):
     # the restarted run: GPU through run_dream, oracle through the same host code
     s2, l2 = run_dream(params, like, nchains=N, niterations=G2, verbose=False, restart=True, start=starts, model_name="rs",
                        save_history=False, seed=202, **kw)
-    o2, ol2 = _oracle_run_dream(params, like, N, G2, starts, 202, restart=True, model_name="rs", save_history=False, **kw)
+    o2, ol2 = oracle_run_dream(params, like, N, G2, starts, 202, restart=True, model_name="rs", save_history=False, **kw)
     np.testing.assert_array_equal(np.array(s2), np.array(o2))
     np.testing.assert_array_equal(np.array(l2), np.array(ol2))
     # ... and the files mattered: the same run from the original seed history with uniform probabilities goes elsewhere
@@ -609,7 +591,7 @@ def test_run_dream_at_the_reference_examples_dimension(tmp_path, monkeypatch, mu
     sampled, log_ps = run_dream(pri, like, nchains=N, niterations=n, start=[Z0[c] for c in range(N)], verbose=False, seed=4, **kw)
     from pydream_amd import core
     assert core.last_kernel_variant == ("k_generations_d2<13,tri,xhbm,16,1,full>" if multitry else "k_generations_d2<13,tri,xhbm,16,1,full,k1>")
-    s_o, l_o = _oracle_run_dream(pri, like, N, n, [Z0[c] for c in range(N)], 4, **kw)
+    s_o, l_o = oracle_run_dream(pri, like, N, n, [Z0[c] for c in range(N)], 4, **kw)
     np.testing.assert_array_equal(np.array(sampled), np.array(s_o))
     np.testing.assert_array_equal(np.array(log_ps), np.array(l_o))
     acc = np.mean([np.any(np.diff(np.asarray(s), axis=0) != 0, axis=1).mean() for s in sampled])

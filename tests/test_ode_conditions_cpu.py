@@ -15,9 +15,7 @@ from . import ode_condition_networks as CN
 from . import ode_networks as NW
 from . import ode_reference as REF
 from . import ode_wide_networks as W
-from .test_ode_group_cpu import _notes
-
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+from .ode_support import READELF, notes
 
 
 def _check_terms_and_sum(multi, single, X, **kw):
@@ -196,7 +194,7 @@ def test_item_kernels_cross_compile_for_gfx950_without_scratch(name, tmp_path, m
     assert open(path, "rb").read(4) == b"\x7fELF" and multi.code_object() == path
     syms = subprocess.run([READELF, "-s", path], capture_output=True, text=True).stdout
     assert kernel + ".kd" in syms and kernel.replace("_item", "") + ".kd" not in syms
-    n, one = _notes(path), _notes(single(0).code_object())
+    n, one = notes(path), notes(single(0).code_object())
     print("%s: %d VGPRs (%d of them AGPRs), static LDS %d B, scratch %d; the single-condition build: %d VGPRs (%d AGPRs), scratch %d"
           % (name, n["vgpr"], n["agpr"], n["lds"], n["scratch"], one["vgpr"], one["agpr"], one["scratch"]))
     assert n["scratch"] == 0

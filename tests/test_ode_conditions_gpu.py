@@ -8,26 +8,15 @@ import pytest
 from scipy.stats import uniform
 
 from pydream_amd import _capi
-from pydream_amd.core import run_dream
 from pydream_amd.likelihoods import DeviceKernelLogLike
 from pydream_amd.parameters import SampledParam
 
 from . import ode_condition_networks as CN
 from . import ode_networks as NW
 from . import ode_wide_networks as W
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_equals_host, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _device_equals_host(multi, X, nom):
-    pr, lk = _device_logp(multi, X, nom - 1.0, 2.0)
-    host = multi.batch(X)
-    assert lk.tobytes() == host.tobytes()
-    outside = np.any((X < nom - 1.0) | (X > nom + 1.0), axis=1)
-    assert np.all(pr[outside] == -np.inf) and np.all(np.isfinite(pr[~outside]))
-    return host, multi.batch_conditions(X) == -np.inf
 
 
 @pytest.mark.parametrize("doses,max_steps", [(CN.MM_DOSES, 500), (CN.MM_DOSES_5, 500), (CN.MM_DOSES, 60)])
@@ -36,7 +25,8 @@ def test_device_equals_host_build_one_lane_per_item(doses, max_steps):
     fail in every condition, in some, in none."""
     multi, _ = CN.mm(doses, max_steps=max_steps)
     X = NW.box_points(NW.MM_NOMINAL, 1027, 21, width=1.0, outside=0.05)
-    host, failed = _device_equals_host(multi, X, NW.MM_NOMINAL)
+    host = device_equals_host(multi, X, NW.MM_NOMINAL)
+    failed = multi.batch_conditions(X) == -np.inf
     count = failed.sum(axis=1)
     print("MM x %d at max_steps %d: points failing in all / some / no conditions: %d / %d / %d"
           % (len(doses), max_steps, np.sum(count == len(doses)), np.sum((count > 0) & (count < len(doses))), np.sum(count == 0)))
@@ -54,7 +44,7 @@ def test_device_equals_host_twin_a_lane_group_per_item(name):
     else:
         (multi, _), nom, n = CN.chain(17, 32, (1.0, 2.0)), W.CHAIN_NOMINAL, 131
     X = NW.box_points(nom, n, 21, width=1.0)
-    host, _ = _device_equals_host(multi, X, nom)
+    host = device_equals_host(multi, X, nom)
     assert np.all(np.isfinite(host))
 
 
@@ -123,13 +113,4 @@ def test_run_dream_on_the_device_equals_the_oracle(tmp_path, multitry, hard, max
     starts = list(box[np.isfinite(multi.batch(box))][:N])
     assert len(starts) == N
     kw = dict(multitry=multitry, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=hard, history_file="mm_seed.npy")
-    sampled, log_ps = run_dream(params, multi, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: multi(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(multi, params, starts, 56, N, G, **kw)

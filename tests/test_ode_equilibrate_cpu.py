@@ -23,7 +23,7 @@ from . import ode_networks as NW
 from . import ode_reference as R
 from . import ode_wave_networks as WV
 from . import ode_wide_networks as W
-from .test_ode_likelihood_cpu import _max_rel_err
+from .ode_support import max_rel_err
 
 # sha256 of source() on the commit before the keyword existed
 PARENT_SOURCE_SHA256 = {
@@ -214,7 +214,7 @@ def test_trajectories_agree_with_radau_run_to_rest_and_restarted_at_t0(name, n, 
     for rtol in (1e-6, 1e-9):
         like = EQ.single(name, events=[bolus], rtol=rtol, atol=rtol, max_steps=20000, equilibrate=dict(max_steps=20000))
         assert like.equilibrate["horizon"] == horizon and like.equilibrate["rtol"] == rtol
-        errs.append(_max_rel_err(like, refs, X, rtol))
+        errs.append(max_rel_err(like, refs, X, rtol))
     print("%s equilibrated, then a bolus at t0, against Radau: max |sim - ref| / (rtol |ref| + rtol) at rtol 1e-6, 1e-9: %s" % (name, errs))
     assert errs[0] < 10 and errs[1] < 10
 

@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd.core import run_dream
 from pydream_amd.parameters import SampledParam
 
 from . import ode_equilibrate_networks as EQ
@@ -16,9 +15,7 @@ from . import ode_event_networks as EV
 from . import ode_networks as NW
 from . import ode_wave_networks as WV
 from . import ode_wide_networks as W
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_events_gpu import _device_equals_host
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_equals_host, device_logp, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +29,7 @@ def test_one_lane_items_in_and_out_of_the_phase_equal_the_host_build(starved):
     multi, _ = EQ.conditions("mm", **kw)
     assert multi.lanes_per_point == 1 and "EQUILIBRATE = true" in multi.source()
     X = NW.box_points(NW.MM_NOMINAL, 131, 21, width=1.0, outside=0.05)
-    host = _device_equals_host(multi, X, NW.MM_NOMINAL)
+    host = device_equals_host(multi, X, NW.MM_NOMINAL)
     count = np.sum(multi.batch_conditions(X) == -np.inf, axis=1)
     print("MM x 3 (phase off, on, on + bolus)%s: points failing in all / some / no conditions: %d / %d / %d"
           % (" starved" if starved else "", np.sum(count == 3), np.sum((count > 0) & (count < 3)), np.sum(count == 0)))
@@ -47,7 +44,7 @@ def test_group_items_in_and_out_of_the_phase_equal_the_host_twin():
     four groups of a wave are in different conditions, one of them outside the phase."""
     multi, _ = EQ.conditions("enzyme13")
     assert multi.lanes_per_point == 16 and "EQUILIBRATE = true" in multi.source()
-    host = _device_equals_host(multi, NW.box_points(W.ENZ.NOMINAL, 67, 21, width=1.0), W.ENZ.NOMINAL)
+    host = device_equals_host(multi, NW.box_points(W.ENZ.NOMINAL, 67, 21, width=1.0), W.ENZ.NOMINAL)
     assert np.all(np.isfinite(host))
 
 
@@ -58,7 +55,7 @@ def test_a_single_experiment_with_the_phase_equals_the_host_build(name, n):
     like = EQ.single(name, events=[EQ.BOLUS[name]])
     nominal = EQ.network(name)[5]
     assert like.lanes_per_point == (32 if name == "chain17" else 1) and like.conditions is None and "EQUILIBRATE = true" in like.source()
-    host = _device_equals_host(like, NW.box_points(nominal, n, 22, width=1.0, outside=0.05), nominal)
+    host = device_equals_host(like, NW.box_points(nominal, n, 22, width=1.0, outside=0.05), nominal)
     assert np.all(np.isfinite(host))
 
 
@@ -67,7 +64,7 @@ def test_a_wave_per_point_with_the_phase_equals_the_host_twin():
     name = EQ.smallest_wave_chain()
     like = EQ.single(name)
     assert like.lanes_per_point == 64 and like.n_species == min(c[3][0] for c in WV.CASES.values()) and "EQUILIBRATE = true" in like.source()
-    host = _device_equals_host(like, NW.box_points(WV.CHAIN_NOMINAL, 9, 23, width=1.0), WV.CHAIN_NOMINAL)
+    host = device_equals_host(like, NW.box_points(WV.CHAIN_NOMINAL, 9, 23, width=1.0), WV.CHAIN_NOMINAL)
     assert np.all(np.isfinite(host))
 
 
@@ -85,21 +82,12 @@ def test_run_dream_with_the_phase_on_the_device_equals_the_oracle(tmp_path):
     starts = list(box[np.isfinite(multi.batch(box))][:N])
     assert len(starts) == N
     kw = dict(multitry=3, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=False, history_file="mm_seed.npy")
-    sampled, log_ps = run_dream(params, multi, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=57, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: multi(x), N, G, starts, 57, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(multi, params, starts, 57, N, G, **kw)
 
 
 def test_an_object_built_without_the_phase_runs_the_kernel_it_always_ran():
     X = NW.box_points(NW.MM_NOMINAL, 259, 23, width=1.0)
     plain, none, off = NW.michaelis_menten(), NW.michaelis_menten(equilibrate=None), NW.michaelis_menten(equilibrate=False)
     assert none.code_object() == off.code_object() == plain.code_object()              # (the same unit: one entry of the kernel cache)
-    a, b = _device_logp(plain, X, NW.MM_NOMINAL - 1.0, 2.0)[1], _device_logp(none, X, NW.MM_NOMINAL - 1.0, 2.0)[1]
+    a, b = device_logp(plain, X, NW.MM_NOMINAL - 1.0, 2.0)[1], device_logp(none, X, NW.MM_NOMINAL - 1.0, 2.0)[1]
     assert a.tobytes() == b.tobytes() == plain.batch(X).tobytes() and np.all(np.isfinite(a))

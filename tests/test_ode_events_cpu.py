@@ -18,7 +18,7 @@ from . import ode_event_networks as EN
 from . import ode_networks as NW
 from . import ode_reference as R
 from . import ode_wide_networks as W
-from .test_ode_likelihood_cpu import _max_rel_err, _notes
+from .ode_support import max_rel_err, notes
 
 
 def _pool():
@@ -47,7 +47,7 @@ def test_host_build_with_events_is_accurate_against_piecewise_radau(name, n, see
     for rtol in (1e-6, 1e-9):
         like = EN.single(name, rtol=rtol, atol=rtol, max_steps=20000)
         assert like.lanes_per_point == lanes and "EVENTS = %d" % len(events) in like.source()
-        errs.append(_max_rel_err(like, refs, X, rtol))
+        errs.append(max_rel_err(like, refs, X, rtol))
     print(name, errs)
     assert errs[0] < 10 and errs[1] < 10
     abs_errs = [e * r for e, r in zip(errs, (1e-6, 1e-9))]
@@ -133,7 +133,7 @@ def test_a_bolus_after_a_long_pre_equilibration_agrees_with_a_start_from_the_equ
             y0[1] = y0[1] + 2.0
             short = MassActionODELogLike(4, NW.MM_REACTIONS, y0, NW.MM_T, obs, long_run.data, long_run.sd, **kw).simulate(x)[0]
             between = max(between, float(np.max(np.abs(sim[i] - short) / (rtol * np.abs(short) + rtol))))
-        errs.append((between, _max_rel_err(long_run, refs, X, rtol)))
+        errs.append((between, max_rel_err(long_run, refs, X, rtol)))
     print("pre-equilibration: (against the equilibrated start, against piecewise Radau) at rtol 1e-6, 1e-9:", errs)
     assert all(e < 10 for pair in errs for e in pair)
     assert errs[1][1] * 1e-9 < 1e-2 * errs[0][1] * 1e-6
@@ -267,7 +267,7 @@ def test_events_cross_compile_for_gfx950_without_more_scratch(model):
     else:
         with_events, without = EN.mm_conditions()[0], CN.mm()[0]
     assert "EVENTS = 3" in with_events.source() and "EVENTS" not in without.source()
-    a, b = _notes(with_events.code_object()), _notes(without.code_object())
+    a, b = notes(with_events.code_object()), notes(without.code_object())
     print("%s: with events %d VGPRs, %d AGPRs, scratch %d; without %d VGPRs, %d AGPRs, scratch %d"
           % (model, a["vgpr"], a["agpr"], a["scratch"], b["vgpr"], b["agpr"], b["scratch"]))
     assert a["scratch"] <= b["scratch"]

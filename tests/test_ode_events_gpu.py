@@ -8,25 +8,14 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd.core import run_dream
 from pydream_amd.parameters import SampledParam
 
 from . import ode_event_networks as EN
 from . import ode_networks as NW
 from . import ode_wide_networks as W
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_equals_host, device_logp, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _device_equals_host(like, X, nom):
-    pr, lk = _device_logp(like, X, nom - 1.0, 2.0)
-    host = like.batch(X)
-    assert lk.tobytes() == host.tobytes()
-    outside = np.any((X < nom - 1.0) | (X > nom + 1.0), axis=1)
-    assert np.all(pr[outside] == -np.inf) and np.all(np.isfinite(pr[~outside]))
-    return host
 
 
 @pytest.mark.parametrize("max_steps", [500, EN.MM_STARVED_MAX_STEPS])
@@ -35,7 +24,7 @@ def test_one_lane_items_with_different_event_counts_equal_the_host_build(max_ste
     different event counts.  At the small step limit there are points that fail in every condition, in some, in none."""
     multi, _ = EN.mm_conditions(max_steps=max_steps)
     X = NW.box_points(NW.MM_NOMINAL, 131, 21, width=1.0, outside=0.05)
-    host = _device_equals_host(multi, X, NW.MM_NOMINAL)
+    host = device_equals_host(multi, X, NW.MM_NOMINAL)
     count = np.sum(multi.batch_conditions(X) == -np.inf, axis=1)
     print("MM x 3 with 0, 1, 3 events at max_steps %d: points failing in all / some / no conditions: %d / %d / %d"
           % (max_steps, np.sum(count == 3), np.sum((count > 0) & (count < 3)), np.sum(count == 0)))
@@ -50,7 +39,7 @@ def test_group_items_with_different_event_counts_equal_the_host_twin():
     without an item, and the four groups of a wave hold different conditions."""
     multi, _ = EN.enzyme13_conditions()
     assert multi.lanes_per_point == 16 and "EVENTS = 3" in multi.source()
-    host = _device_equals_host(multi, NW.box_points(W.ENZ.NOMINAL, 67, 21, width=1.0), W.ENZ.NOMINAL)
+    host = device_equals_host(multi, NW.box_points(W.ENZ.NOMINAL, 67, 21, width=1.0), W.ENZ.NOMINAL)
     assert np.all(np.isfinite(host))
 
 
@@ -61,7 +50,7 @@ def test_a_single_experiment_with_events_equals_the_host_build(name, n):
     like = EN.single(name)
     nominal = EN._network(name)[5]
     assert like.lanes_per_point == (32 if name == "chain17" else 1) and like.conditions is None and "EVENTS" in like.source()
-    host = _device_equals_host(like, NW.box_points(nominal, n, 22, width=1.0, outside=0.05), nominal)
+    host = device_equals_host(like, NW.box_points(nominal, n, 22, width=1.0, outside=0.05), nominal)
     assert np.all(np.isfinite(host))
 
 
@@ -80,21 +69,12 @@ def test_run_dream_with_events_on_the_device_equals_the_oracle(tmp_path):
     starts = list(box[np.isfinite(multi.batch(box))][:N])
     assert len(starts) == N
     kw = dict(multitry=3, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=False, history_file="mm_seed.npy")
-    sampled, log_ps = run_dream(params, multi, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: multi(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(multi, params, starts, 56, N, G, **kw)
 
 
 def test_an_object_built_with_no_events_runs_the_kernel_it_always_ran():
     X = NW.box_points(NW.MM_NOMINAL, 259, 23, width=1.0)
     plain, empty = NW.michaelis_menten(), NW.michaelis_menten(events=[])
     assert empty.code_object() == plain.code_object()              # (the same unit: one entry of the kernel cache)
-    a, b = _device_logp(plain, X, NW.MM_NOMINAL - 1.0, 2.0)[1], _device_logp(empty, X, NW.MM_NOMINAL - 1.0, 2.0)[1]
+    a, b = device_logp(plain, X, NW.MM_NOMINAL - 1.0, 2.0)[1], device_logp(empty, X, NW.MM_NOMINAL - 1.0, 2.0)[1]
     assert a.tobytes() == b.tobytes() == plain.batch(X).tobytes() and np.all(np.isfinite(a))

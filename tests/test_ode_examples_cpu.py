@@ -22,7 +22,7 @@ from pydream_amd.likelihoods import Monomial
 from . import ode_condition_networks as CN
 from . import ode_monomial_networks as MN
 from . import ode_networks as NW
-from .test_ode_likelihood_cpu import _notes
+from .ode_support import notes
 
 BOUND = 1e-6
 
@@ -149,8 +149,8 @@ def test_the_combinations_cross_compile_for_gfx950_without_scratch(model):
         like, plain = example_spec(model)[0], None
     else:
         like, plain = MN.build(model)[0], MN.build(model[:-len("_events")])[0]
-    a = _notes(like.code_object())
+    a = notes(like.code_object())
     print("%s: %d VGPRs, %d AGPRs, scratch %d" % (model, a["vgpr"], a["agpr"], a["scratch"]))
     assert a["scratch"] == 0
     if plain is not None:
-        assert "EVENTS" not in plain.source() and a["scratch"] <= _notes(plain.code_object())["scratch"]
+        assert "EVENTS" not in plain.source() and a["scratch"] <= notes(plain.code_object())["scratch"]

@@ -8,15 +8,13 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd.core import run_dream
 from pydream_amd.examples.binding_cycle import binding_cycle_device as BC
 from pydream_amd.examples.washout import washout_device as WO
 from pydream_amd.parameters import SampledParam
 
 from . import ode_monomial_networks as MN
 from . import ode_networks as NW
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_events_gpu import _device_equals_host
+from .ode_support import device_equals_host, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +26,7 @@ def test_a_shipped_example_on_the_device_equals_the_host_build(name, n):
     M = WO if name == "washout" else BC
     like = M.make_likelihood()
     assert like.lanes_per_point == 1 and len(like.conditions) == len(M.DOSES)
-    host = _device_equals_host(like, NW.box_points(M.NOMINAL, n, 24, width=1.0, outside=0.05), M.NOMINAL)
+    host = device_equals_host(like, NW.box_points(M.NOMINAL, n, 24, width=1.0, outside=0.05), M.NOMINAL)
     assert np.isfinite(host).sum() > n // 2
 
 
@@ -39,7 +37,7 @@ def test_events_with_monomials_on_the_device_equal_the_host_build(name, lanes, n
     like, _ = MN.build(name, lanes_per_point=lanes)
     nominal = MN.nominal(name)
     assert like.lanes_per_point == lanes and "EVENTS" in like.source() and "MONOMIALS" in like.source()
-    host = _device_equals_host(like, NW.box_points(nominal, n, 25, width=1.0, outside=0.05), nominal)
+    host = device_equals_host(like, NW.box_points(nominal, n, 25, width=1.0, outside=0.05), nominal)
     assert np.isfinite(host).sum() > n // 2
 
 
@@ -57,16 +55,7 @@ def test_run_dream_with_washout_on_the_device_equals_the_oracle(tmp_path):
     starts = list(box[np.isfinite(like.batch(box))][:N])
     assert len(starts) == N
     kw = dict(multitry=3, history_thin=1, hardboundaries=False, history_file="washout_seed.npy")
-    sampled, log_ps = run_dream(params, like, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=57, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: like(x), N, G, starts, 57, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(like, params, starts, 57, N, G, **kw)
 
 
 @pytest.mark.parametrize("multitry", [1, 3])

@@ -14,7 +14,7 @@ import pytest
 from . import ode_grammar as G
 from . import ode_networks as NW
 from . import ode_wide_networks as W
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_logp
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +29,11 @@ LARGE_STEP = {1: (0, 1027), 16: (2, 515), 32: (4, 515), 64: (6, N_POINTS_WIDE)} 
 
 def _same_bits(like, X):
     lower = X.min(axis=0) - 1.0
-    pr, lk = _device_logp(like, X, lower, float(np.max(X.max(axis=0) - lower)) + 1.0)
+    pr, lk = device_logp(like, X, lower, float(np.max(X.max(axis=0) - lower)) + 1.0)
     host = like.batch(X)
     assert np.all(np.isfinite(pr))
     assert lk.tobytes() == host.tobytes(), (np.flatnonzero(lk != host)[:8], len(X))
-    one = _device_logp(like, X[:1], lower, float(np.max(X.max(axis=0) - lower)) + 1.0)[1]
+    one = device_logp(like, X[:1], lower, float(np.max(X.max(axis=0) - lower)) + 1.0)[1]
     assert one.shape == (1,) and one.tobytes() == host[:1].tobytes()
     return host
 

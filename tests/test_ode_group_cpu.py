@@ -14,15 +14,9 @@ from pydream_amd.likelihoods import MassActionODELogLike
 
 from . import ode_networks as NW
 from . import ode_wide_networks as W
+from .ode_support import READELF, max_rel_err, notes
 
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 NAMES = list(W.CASES)
-
-
-def _notes(path):
-    txt = subprocess.run([READELF, "--notes", path], capture_output=True, text=True).stdout
-    get = lambda key: int(txt.split(key)[1].split()[0])                     # noqa: E731
-    return dict(vgpr=get(".vgpr_count:"), agpr=get(".agpr_count:"), scratch=get(".private_segment_fixed_size:"), lds=get(".group_segment_fixed_size:"))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -33,7 +27,7 @@ def test_group_solver_cross_compiles_for_gfx950_without_scratch(name, tmp_path, 
     assert open(path, "rb").read(4) == b"\x7fELF" and like.code_object() == path
     syms = subprocess.run([READELF, "-s", path], capture_output=True, text=True).stdout
     assert "dz_ode_group_batch.kd" in syms
-    n = _notes(path)
+    n = notes(path)
     print("%s: S=%d R=%d: %d VGPRs (%d of them AGPRs), static LDS %d B, scratch %d"
           % (name, like.n_species, len(like.reactions), n["vgpr"], n["agpr"], n["lds"], n["scratch"]))
     assert n["scratch"] == 0
@@ -46,7 +40,7 @@ def test_networks_at_the_reaction_limit_compile_without_scratch(S, R, lanes, tmp
     are fenced every four terms, so what a lane holds at once hardly depends on R (measured: 32 species at 32 / 64 / 128 reactions
     374 / 401 / 407 registers)."""
     monkeypatch.setenv("DREAMZS_KERNEL_CACHE", str(tmp_path))
-    n = _notes(W.dense_network(S, R, lanes).code_object())
+    n = notes(W.dense_network(S, R, lanes).code_object())
     print("dense S=%d R=%d @%d: %d VGPRs (%d of them AGPRs), static LDS %d B, scratch %d" % (S, R, lanes, n["vgpr"], n["agpr"], n["lds"], n["scratch"]))
     assert n["scratch"] == 0
 
@@ -59,16 +53,9 @@ def test_one_lane_networks_at_the_reaction_limit_compile_without_scratch(S, R, l
     monkeypatch.setenv("DREAMZS_KERNEL_CACHE", str(tmp_path))
     like = W.dense_network(S, R, lanes)
     assert "DZODE_FENCE" in like.source() and "dz_ode_group" not in like.source()
-    n = _notes(like.code_object())
+    n = notes(like.code_object())
     print("dense S=%d R=%d @%d: %d VGPRs (%d of them AGPRs), scratch %d" % (S, R, lanes, n["vgpr"], n["agpr"], n["scratch"]))
     assert n["scratch"] == 0
-
-
-def _max_rel_err(like, refs, X, rtol):
-    """max over points, times and observables of |sim - ref| / (rtol |ref| + rtol)"""
-    sim = like.simulate(X)
-    assert np.all(np.isfinite(sim))
-    return max(float(np.max(np.abs(s - ref) / (rtol * np.abs(ref) + rtol))) for s, ref in zip(sim, refs))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -85,7 +72,7 @@ def test_host_twin_is_accurate_against_radau_and_error_shrinks_with_tolerance(na
     errs = []
     for rtol in (1e-6, 1e-9):
         like = make(rtol=rtol, atol=rtol, max_steps=20000)
-        errs.append(_max_rel_err(like, refs, X, rtol))
+        errs.append(max_rel_err(like, refs, X, rtol))
     print(name, errs)
     assert errs[0] < 10 and errs[1] < 10
     abs_errs = [e * r for e, r in zip(errs, (1e-6, 1e-9))]

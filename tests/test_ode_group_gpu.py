@@ -13,8 +13,7 @@ from pydream_amd.parameters import SampledParam
 
 from . import ode_networks as NW
 from . import ode_wide_networks as W
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_equals_host, device_logp, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +26,17 @@ def test_device_equals_host_twin_bit_for_bit(name, starved):
     make, nom, _ = W.CASES[name]
     like = make(max_steps=W.STARVED_MAX_STEPS[name]) if starved else make()
     X = NW.box_points(nom, N_POINTS, 21, width=1.0, outside=0.05 / len(nom))      # a few points outside the prior's support
-    pr, lk = _device_logp(like, X, nom - 1.0, 2.0)
-    host = like.batch(X)
+    host = device_equals_host(like, X, nom)
     failed = host == -np.inf
     print("%s: %d of %d points -inf" % (name, failed.sum(), len(X)))
-    assert lk.tobytes() == host.tobytes()
     outside = np.any((X < nom - 1.0) | (X > nom + 1.0), axis=1)
-    assert outside.any() and np.all(pr[outside] == -np.inf) and np.all(np.isfinite(pr[~outside]))
+    assert outside.any()
     if starved:                                                         # failed and finished points inside one wave
         per_wave = 64 // like.lanes_per_point
         waves = failed[:len(X) // per_wave * per_wave].reshape(-1, per_wave)
         assert np.any(waves.any(axis=1) & ~waves.all(axis=1))
     else:
-        assert np.all(np.isfinite(lk[~outside]))
+        assert np.all(np.isfinite(host[~outside]))
 
 
 @pytest.mark.parametrize("S,R,lanes", [(32, 128, 32), (16, 128, 16)])
@@ -47,7 +44,7 @@ def test_device_equals_host_twin_on_a_network_at_the_reaction_limit(S, R, lanes)
     """128 bimolecular reactions: the longest generated sums the class accepts, same bits on both sides."""
     like = W.dense_network(S, R, lanes)
     X = NW.box_points(np.zeros(20), 1027, 4, width=1.0)
-    pr, lk = _device_logp(like, X, np.full(20, -1.0), 2.0)
+    pr, lk = device_logp(like, X, np.full(20, -1.0), 2.0)
     host, steps = like.batch(X, return_steps=True)
     print("dense S=%d R=%d: %d of %d points -inf, median %d steps" % (S, R, np.sum(host == -np.inf), len(X), np.median(steps)))
     assert lk.tobytes() == host.tobytes()
@@ -70,16 +67,7 @@ def test_run_dream_on_the_device_equals_the_oracle(tmp_path, multitry, hard, max
         assert np.mean(like.batch(Z0) == -np.inf) > 0.2
     starts = [nom + 0.1 * rng.uniform(-1, 1, len(nom)) for _ in range(N)]
     kw = dict(multitry=multitry, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=hard, history_file="enz_seed.npy")
-    sampled, log_ps = run_dream(params, like, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: like(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(like, params, starts, 56, N, G, **kw)
 
 
 def test_the_trace_agrees_with_an_independent_radau_likelihood(tmp_path):

@@ -15,14 +15,7 @@ from pydream_amd import likelihoods as LK
 from pydream_amd.likelihoods import MassActionODELogLike
 
 from . import ode_networks as NW
-
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-
-
-def _notes(path):
-    txt = subprocess.run([READELF, "--notes", path], capture_output=True, text=True).stdout
-    get = lambda key: int(txt.split(key)[1].split()[0])                     # noqa: E731
-    return dict(vgpr=get(".vgpr_count:"), agpr=get(".agpr_count:"), scratch=get(".private_segment_fixed_size:"))
+from .ode_support import READELF, max_rel_err, notes
 
 
 @pytest.mark.parametrize("make", [NW.robertson, NW.chain8])
@@ -33,7 +26,7 @@ def test_generated_solver_cross_compiles_for_gfx950_without_scratch(make, tmp_pa
     assert open(path, "rb").read(4) == b"\x7fELF" and like.code_object() == path
     syms = subprocess.run([READELF, "-s", path], capture_output=True, text=True).stdout
     assert "dz_ode_batch.kd" in syms
-    n = _notes(path)
+    n = notes(path)
     print("S=%d: %d VGPRs, %d AGPRs, scratch %d" % (like.n_species, n["vgpr"], n["agpr"], n["scratch"]))
     assert n["scratch"] == 0
     assert MassActionODELogLike(**_robertson_kw(), path=path).code_object() == path          # a code object built beforehand
@@ -44,13 +37,6 @@ def _robertson_kw(**over):
               data=np.ones((1, 50)), sd=np.ones((1, 50)))
     kw.update(over)
     return kw
-
-
-def _max_rel_err(like, refs, X, rtol):
-    """max over points, times and observables of |sim - ref| / (rtol |ref| + rtol)"""
-    sim = like.simulate(X)
-    assert np.all(np.isfinite(sim))
-    return max(float(np.max(np.abs(s - ref) / (rtol * np.abs(ref) + rtol))) for s, ref in zip(sim, refs))
 
 
 @pytest.mark.parametrize("net", ["robertson", "mm", "chain8"])
@@ -70,7 +56,7 @@ def test_host_build_is_accurate_against_radau_and_error_shrinks_with_tolerance(n
     errs = []
     for rtol in (1e-6, 1e-9):
         like = make(rtol=rtol, atol=rtol, max_steps=20000)
-        errs.append(_max_rel_err(like, refs, X, rtol))
+        errs.append(max_rel_err(like, refs, X, rtol))
     print(net, errs)
     assert errs[0] < 10 and errs[1] < 10
     abs_errs = [e * r for e, r in zip(errs, (1e-6, 1e-9))]

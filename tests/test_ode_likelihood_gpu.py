@@ -6,23 +6,13 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd import _capi
 from pydream_amd.core import run_dream
 from pydream_amd.parameters import SampledParam
 
 from . import ode_networks as NW
-from .test_api_gpu import _oracle_run_dream
+from .ode_support import device_equals_host, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _device_logp(like, X, lower, width):
-    """(prior, likelihood) of the rows of X from the engine's eval_logp, under a uniform prior on [lower, lower + width]"""
-    d = X.shape[1]
-    eng = _capi.Engine(nchains=3, ndim=d, history_capacity=8)
-    eng.set_prior(np.full(d, 2, dtype=np.int32), np.asarray(lower, dtype=float), np.full(d, float(width)))
-    like._dz_apply(eng)
-    return eng.eval_logp(X)
 
 
 @pytest.mark.parametrize("net", ["robertson", "mm", "chain8"])
@@ -34,12 +24,9 @@ def test_device_equals_host_build_bit_for_bit(net):
     else:
         like, nom, n, w = NW.chain8(), NW.CHAIN_NOMINAL, 1024, 1.0
     X = NW.box_points(nom, n, 21, width=w, outside=0.05 * w)           # a few points outside the prior's support
-    pr, lk = _device_logp(like, X, nom - w, 2 * w)
-    host = like.batch(X)
-    assert lk.tobytes() == host.tobytes()
+    host = device_equals_host(like, X, nom, w)
     outside = np.any((X < nom - w) | (X > nom + w), axis=1)
-    assert outside.any() and np.all(pr[outside] == -np.inf) and np.all(np.isfinite(pr[~outside]))
-    assert np.all(np.isfinite(lk[~outside]))
+    assert outside.any() and np.all(np.isfinite(host[~outside]))
 
 
 @pytest.mark.parametrize("multitry,hard,max_steps", [(False, True, 500), (3, False, 30)])
@@ -58,16 +45,7 @@ def test_run_dream_on_the_device_equals_the_oracle(tmp_path, multitry, hard, max
         assert np.mean(like.batch(Z0) == -np.inf) > 0.2
     starts = [NW.ROB.NOMINAL + 0.3 * rng.uniform(-1, 1, 3) for _ in range(N)]
     kw = dict(multitry=multitry, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=hard, history_file="rob_seed.npy")
-    sampled, log_ps = run_dream(params, like, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: like(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(like, params, starts, 56, N, G, **kw)
 
 
 def test_the_trace_agrees_with_an_independent_radau_likelihood(tmp_path):

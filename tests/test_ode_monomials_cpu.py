@@ -16,9 +16,7 @@ from . import ode_condition_networks as CN
 from . import ode_monomial_networks as MN
 from . import ode_networks as NW
 from . import ode_wide_networks as W
-from .test_ode_group_cpu import _notes
-
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+from .ode_support import READELF, notes
 
 
 # ---------------------------------------------------------------------------------------------------- the value object
@@ -288,13 +286,13 @@ def test_kernels_cross_compile_for_gfx950_without_scratch(name, tmp_path, monkey
     like, single = MN.build(name)
     plain, stem = CROSS[name]
     builds = [(like, stem + ("_item_batch" if like.conditions else "_batch"))] + ([(single(0), stem + "_batch")] if like.conditions else [])
-    counterpart = _notes(plain().code_object())
+    counterpart = notes(plain().code_object())
     for obj, kernel in builds:
         path = obj.code_object()
         assert open(path, "rb").read(4) == b"\x7fELF" and obj.code_object() == path
         syms = subprocess.run([READELF, "-s", path], capture_output=True, text=True).stdout
         assert kernel + ".kd" in syms
-        n = _notes(path)
+        n = notes(path)
         print("%s %s: %d VGPRs (%d of them AGPRs), static LDS %d B, scratch %d; without monomials (%s): %d VGPRs (%d AGPRs), scratch %d"
               % (name, kernel, n["vgpr"], n["agpr"], n["lds"], n["scratch"], "the items kernel" if plain().conditions else "single",
                  counterpart["vgpr"], counterpart["agpr"], counterpart["scratch"]))

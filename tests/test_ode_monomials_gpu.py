@@ -7,24 +7,13 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd.core import run_dream
 from pydream_amd.parameters import SampledParam
 
 from . import ode_monomial_networks as MN
 from . import ode_networks as NW
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_equals_host, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _device_equals_host(like, X, nom):
-    pr, lk = _device_logp(like, X, nom - 1.0, 2.0)
-    host = like.batch(X)
-    assert lk.tobytes() == host.tobytes()
-    outside = np.any((X < nom - 1.0) | (X > nom + 1.0), axis=1)
-    assert np.all(pr[outside] == -np.inf) and np.all(np.isfinite(pr[~outside]))
-    return host
 
 
 @pytest.mark.parametrize("name,max_steps", [("mm_kd", 500), ("mm_kd", 60), ("mm_kd_doses", 60)])
@@ -35,7 +24,7 @@ def test_device_equals_host_build_one_lane_per_item(name, max_steps):
     multi, _ = MN.build(name, max_steps=max_steps)
     nom = MN.nominal(name)
     X = NW.box_points(nom, 1027, 21, width=1.0, outside=0.05)
-    host = _device_equals_host(multi, X, nom)
+    host = device_equals_host(multi, X, nom)
     count = (multi.batch_conditions(X) == -np.inf).sum(axis=1)
     print("%s at max_steps %d: points failing in all / some / no conditions: %d / %d / %d"
           % (name, max_steps, np.sum(count == 3), np.sum((count > 0) & (count < 3)), np.sum(count == 0)))
@@ -50,7 +39,7 @@ def test_device_equals_host_build_single_experiment_long_form():
     """dense8_m: 24 reactions (the reaction-by-reaction source), 515 points = 2 blocks and 3 points, the constraints in the one-experiment kernel"""
     like, _ = MN.build("dense8_m")
     nom = MN.nominal("dense8_m")
-    host = _device_equals_host(like, NW.box_points(nom, 515, 21, width=1.0), nom)
+    host = device_equals_host(like, NW.box_points(nom, 515, 21, width=1.0), nom)
     assert np.all(np.isfinite(host))
 
 
@@ -59,7 +48,7 @@ def test_device_equals_host_twin_a_lane_group_per_item(name, n):
     """enzyme13_m@16: 259 points x 3 = 777 items, 16 to a block: the last block has groups without an item; chain17_m@32: 131 x 2 = 262, 8 to a block."""
     multi, _ = MN.build(name)
     nom = MN.nominal(name)
-    host = _device_equals_host(multi, NW.box_points(nom, n, 21, width=1.0), nom)
+    host = device_equals_host(multi, NW.box_points(nom, n, 21, width=1.0), nom)
     assert np.all(np.isfinite(host))
 
 
@@ -81,13 +70,4 @@ def test_run_dream_on_the_device_equals_the_oracle(tmp_path, multitry, hard, max
     starts = list(box[np.isfinite(multi.batch(box))][:N])
     assert len(starts) == N
     kw = dict(multitry=multitry, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=hard, history_file="mm_kd_seed.npy")
-    sampled, log_ps = run_dream(params, multi, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: multi(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(multi, params, starts, 56, N, G, **kw)

@@ -18,7 +18,7 @@ from . import ode_condition_networks as CN
 from . import ode_networks as NW
 from . import ode_wave_networks as WN
 from . import ode_wide_networks as W
-from .test_ode_group_cpu import READELF, _max_rel_err, _notes
+from .ode_support import READELF, max_rel_err, notes
 
 COMPILE_CASES = {
     "chain33": (lambda: WN.chain(33), False),
@@ -45,7 +45,7 @@ def test_wave_solver_cross_compiles_for_gfx950_without_scratch(name, tmp_path, m
     assert open(path, "rb").read(4) == b"\x7fELF"
     syms = subprocess.run([READELF, "-s", path], capture_output=True, text=True).stdout
     assert ("dz_ode_group_item_batch.kd" if items else "dz_ode_group_batch.kd") in syms
-    n = _notes(path)
+    n = notes(path)
     print("%s: S=%d R=%d: %d VGPRs (%d of them AGPRs), static LDS %d B, scratch %d"
           % (name, like.n_species, len(like.reactions), n["vgpr"], n["agpr"], n["lds"], n["scratch"]))
     assert n["scratch"] == 0
@@ -99,7 +99,7 @@ def test_host_twin_is_accurate_against_radau_and_error_shrinks_with_tolerance(na
         refs = [y @ obs.T for y in ex.map(NW.radau, *zip(*[(S, rx, y0, t, x) for x in X]), chunksize=2)]
     errs = []
     for rtol in (1e-6, 1e-9):
-        errs.append(_max_rel_err(make(rtol=rtol, atol=rtol, max_steps=20000), refs, X, rtol))
+        errs.append(max_rel_err(make(rtol=rtol, atol=rtol, max_steps=20000), refs, X, rtol))
     print(name, errs)
     assert errs[0] < 10 and errs[1] < 10
     abs_errs = [e * r for e, r in zip(errs, (1e-6, 1e-9))]

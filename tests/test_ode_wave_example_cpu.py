@@ -1,15 +1,12 @@
 """The shipped cascade example (pydream_amd/examples/cascade: 49 species, a wave per point) without a GPU: its network is the one its
-docstring describes, and its data are scipy Radau's (its prior box never fails: test_ode_wave_cpu).  N_ITER, N_CHAINS: the reduced size the GPU half
-(test_ode_wave_example_gpu) runs main() at, on the device and through the host twin."""
+docstring describes, and its data are scipy Radau's (its prior box never fails: test_ode_wave_cpu).  The GPU half (test_ode_wave_example_gpu) runs main() at a
+reduced size, ode_wave_networks.N_ITER and N_CHAINS, on the device and through the host twin."""
 import numpy as np
 
 from pydream_amd.examples.cascade import cascade_device as CAS
 
 from . import ode_networks as NW
 from . import ode_wave_networks as WN
-
-N_ITER, N_CHAINS = 6, 8
-
 
 def test_the_cascade_is_six_tiers_of_eight_species_and_twelve_reactions():
     assert CAS.N_SPECIES == 49 and len(CAS.REACTIONS) == 72 and CAS.LANES == 64 and len(CAS.NOMINAL) == 12

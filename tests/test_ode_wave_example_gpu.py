@@ -8,7 +8,6 @@ import pytest
 from pydream_amd.examples.cascade import cascade_device as CAS
 
 from . import ode_wave_networks as WN
-from .test_ode_wave_example_cpu import N_CHAINS, N_ITER
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +15,9 @@ pytestmark = pytest.mark.gpu
 def test_the_example_on_the_device_equals_its_host_twin_run(tmp_path, capsys):
     os.chdir(tmp_path)
     like = WN.cascade()
-    sampled, log_ps = CAS.main(N_ITER, N_CHAINS, like=like)
+    sampled, log_ps = CAS.main(WN.N_ITER, WN.N_CHAINS, like=like)
     assert "the device (64 lanes per point)" in capsys.readouterr().out
-    h_sampled, h_log_ps = CAS.main(N_ITER, N_CHAINS, host=True, like=like)
-    assert np.all(np.isfinite(np.array(log_ps))) and len(np.unique(np.concatenate(sampled)[:, 0])) > N_CHAINS
+    h_sampled, h_log_ps = CAS.main(WN.N_ITER, WN.N_CHAINS, host=True, like=like)
+    assert np.all(np.isfinite(np.array(log_ps))) and len(np.unique(np.concatenate(sampled)[:, 0])) > WN.N_CHAINS
     np.testing.assert_array_equal(np.array(sampled), np.array(h_sampled))
     np.testing.assert_array_equal(np.array(log_ps), np.array(h_log_ps))

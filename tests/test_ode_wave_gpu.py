@@ -8,14 +8,12 @@ import numpy as np
 import pytest
 from scipy.stats import uniform
 
-from pydream_amd.core import run_dream
 from pydream_amd.parameters import SampledParam
 
 from . import ode_networks as NW
 from . import ode_wave_networks as WN
 from . import ode_wide_networks as W
-from .test_api_gpu import _oracle_run_dream
-from .test_ode_likelihood_gpu import _device_logp
+from .ode_support import device_logp, run_dream_equals_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +38,7 @@ def test_device_equals_host_twin_bit_for_bit(name, starved, n):
     """n = 1 and n = 5: a block with three idle waves; 259: 64 full blocks and one with an idle wave"""
     like, X, host = _host(name, starved)
     nom, width = WN.CASES[name][1:3]
-    pr, lk = _device_logp(like, X[:n], nom - width, 2 * width)
+    pr, lk = device_logp(like, X[:n], nom - width, 2 * width)
     failed = host == -np.inf
     print("%s: %d of %d points -inf" % (name, failed[:n].sum(), n))
     assert lk.tobytes() == host[:n].tobytes()
@@ -59,7 +57,7 @@ def test_device_equals_host_twin_on_a_network_at_the_reaction_limit():
     """64 species, 256 bimolecular reactions: the longest generated sums the class accepts, same bits on both sides"""
     like = W.dense_network(64, 256, 64)
     X = NW.box_points(np.zeros(20), 67, 4, width=1.0)
-    pr, lk = _device_logp(like, X, np.full(20, -1.0), 2.0)
+    pr, lk = device_logp(like, X, np.full(20, -1.0), 2.0)
     host, steps = like.batch(X, return_steps=True)
     print("dense S=64 R=256: %d of %d points -inf, median %d steps" % (np.sum(host == -np.inf), len(X), np.median(steps)))
     assert lk.tobytes() == host.tobytes()
@@ -74,7 +72,7 @@ def test_everything_through_the_item_kernel_equals_the_host_build():
     assert [len(c["events"]) for c in like.conditions] == [0, 2, 0] and len(like.constraints) == 1
     nom = WN.CHAIN_NOMINAL
     X = NW.box_points(nom, 67, 25, width=1.0, outside=0.05 / len(nom))
-    pr, lk = _device_logp(like, X, nom - 1.0, 2.0)
+    pr, lk = device_logp(like, X, nom - 1.0, 2.0)
     host = like.batch(X)
     assert lk.tobytes() == host.tobytes()
     assert np.isfinite(host).sum() > len(X) // 2
@@ -99,13 +97,4 @@ def test_run_dream_on_the_device_equals_the_oracle(tmp_path, multitry, hard, max
     starts = [nom + 0.05 * rng.uniform(-1, 1, len(nom)) for _ in range(N)]
     assert np.all(np.isfinite(like.batch(np.array(starts))))
     kw = dict(multitry=multitry, gamma_levels=4, adapt_gamma=True, history_thin=1, hardboundaries=hard, history_file="cascade_seed.npy")
-    sampled, log_ps = run_dream(params, like, nchains=N, niterations=G, verbose=False, start=starts, save_history=False, seed=56, **kw)
-    os.environ["DREAMZS_HOST_WORKERS"] = "1"
-    try:
-        o_s, o_l = _oracle_run_dream(params, lambda x: like(x), N, G, starts, 56, **kw)
-    finally:
-        del os.environ["DREAMZS_HOST_WORKERS"]
-    S = np.concatenate(sampled)
-    assert np.all(np.isfinite(np.concatenate(log_ps))) and len(np.unique(S[:, 0])) > N
-    np.testing.assert_array_equal(np.array(sampled), np.array(o_s))
-    np.testing.assert_array_equal(np.array(log_ps), np.array(o_l))
+    run_dream_equals_oracle(like, params, starts, 56, N, G, **kw)
