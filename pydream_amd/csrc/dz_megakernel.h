@@ -24,6 +24,7 @@
 // block's adaptation sums made, the previous generation's totals applied in the prologue; the swap kernel follows).
 #pragma once
 #include "dz_kernels.h"
+#include "dz_draw_groups.h"
 
 namespace dz {
 
@@ -543,6 +544,61 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
         }
         return q;
     };
+    // (CUR) Draw groups.  Every slot draw is addressed by (slot, stream, global chain, generation), never by the chain's state, and in a plain launch the
+    // probabilities the decisions are made with are launch constants: so ONE Philox pass over the wave makes the draws of GRP = 64 / nslots consecutive
+    // generations -- lane nslots j + s holds slot s of generation index gi0 + j -- and what the loop reads from them is finished in the lanes that hold the
+    // words, once per group instead of once per generation in every lane:
+    //   slot 0: .x = the snooker flag (set_snooker :542-554), .y = the CR index (set_CR :556-569);  slot 1: .x = the gamma level (set_gamma_level :585-599);
+    //   slot 2: .x/.y = the bits of u_sel, .z/.w = those of u_acc;  the point-stream slots: finish_draws with the row count of the lane's OWN generation
+    //   (draw_group_rows: an append inside the group) and its own generation's snooker flag.
+    // The loop reads a generation's slots in lanes 0 .. nslots-1, as every other instantiation does: between two generations of a group the four registers move
+    // down by nslots lanes (group_shift: four ds_bpermute_b32, no LDS, no barrier).  [Addressing lane nslots (gi mod GRP) + slot through DrawSrc::base instead
+    // was built first and measured: the compiler forms every `slot + offset` at the top of the generation and keeps the sums in scalar registers -- 53 SGPR
+    // spills against 43, 13 spill-lane writes per generation against 7; profiles/headline_drawgroups_ab.txt.]  Mg / na: the row count generation gi0 samples
+    // from and the generation index of the next append at or behind it (-1: none).
+    constexpr int NSL = nslots_c<KCC>(), GRP = CUR ? 64 / NSL : 1;
+    auto group_draws = [&](int gi0, uint32_t Mg, int na) {
+        DrawSrc q; q.have = true; q.mine = make_uint4(0, 0, 0, 0);
+        int ln = lane;
+        asm volatile("" : "+v"(ln));      // (the lane's place in the group is made here, once per group: hoisted out of the generation loop it would take registers across it)
+        int gj = 0;
+#pragma unroll
+        for (int t = 1; t <= GRP; ++t) gj += ln >= t * NSL ? 1 : 0;
+        const int s = ln - NSL * gj;
+        // (every lane, no predicate: the words of generations past the launch's last, and lane GRP nslots and up, are never read -- uniform_draw addresses the
+        //  slots of a generation the loop runs -- and a draw is arithmetic only, no load and no store)
+        { const u32x4 w = slot_counter_draw<KCC>(p, s, gc, g0 + (uint32_t)(gi0 + gj)); q.mine = make_uint4(w.x, w.y, w.z, w.w); }
+        const bool sk = u53_below(q.mine.x, q.mine.y, p.snk_thr);      // (slot-0 lanes: set_snooker's draw)
+        const unsigned long long skb = __ballot(sk);
+        uint32_t Mv = Mg; bool snk_l = (skb & 1ull) != 0;
+        const int thin = p.thin; const uint32_t Nrows = (uint32_t)p.N;
+#pragma unroll
+        for (int t = 1; t < GRP; ++t) {
+            Mv = gj == t ? draw_group_rows(Mg, Nrows, na, thin, gi0, t) : Mv;
+            snk_l = gj == t ? ((skb >> (NSL * t)) & 1ull) != 0 : snk_l;
+        }
+        const double ua = u53(q.mine.x, q.mine.y), ub = u53(q.mine.z, q.mine.w);
+        // invcdf (slot 0: u_cr among the CR values; slot 1: u_glev among the gamma levels) without a lane-dependent trip count: the same running sum, the first
+        // m < n with u < c_m, else n - 1 (a read past a lane's table stays inside the block's LDS and is not used)
+        const int ncr = p.ncr, ngm = p.ngamma;
+        const double* tb = s == 1 ? probs + ncr : probs; const int nb = s == 1 ? ngm : ncr;
+        double cs = 0.0; int idx = -1;
+        for (int m = 0; m < max(ncr, ngm); ++m) { cs = cs + tb[m]; idx = (idx < 0 && m < nb && ub < cs) ? m : idx; }
+        idx = idx < 0 ? nb - 1 : idx;
+        const unsigned long long ba = (unsigned long long)__double_as_longlong(ua), bb = (unsigned long long)__double_as_longlong(ub);
+        if (s == 0) { q.mine.x = sk ? 1u : 0u; q.mine.y = (uint32_t)idx; }
+        if (s == 1) q.mine.x = (uint32_t)(1 + idx);
+        if (s == 2) { q.mine.x = (uint32_t)ba; q.mine.y = (uint32_t)(ba >> 32); q.mine.z = (uint32_t)bb; q.mine.w = (uint32_t)(bb >> 32); }
+        finish_draws<KC>(p, q, snk_l, Mv, s);
+        return q;
+    };
+    auto group_shift = [&](const uint4& m) {      // lane l takes lane l + nslots' words (the lanes that wrap hold nothing a generation reads)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));              // (as above: the address is made here, not kept across the loop)
+        const int a = ((ln + NSL) & 63) << 2;
+        return make_uint4((uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)m.x), (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)m.y),
+                          (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)m.z), (uint32_t)__builtin_amdgcn_ds_bpermute(a, (int)m.w));
+    };
     RowPair RA, RB, RC;
     RA.a = double2{0.0, 0.0}; RA.b = RA.a; RB = RA; RC = RA;
     auto prefetch_first = [&](const DrawSrc& q, int phase_, uint32_t g_, uint32_t M) {          // rows of this wave's first two tries of (g_, phase_)
@@ -553,6 +609,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     };
     auto draws_say_snooker = [&](const DrawSrc& q, uint32_t g_) {                   // set_snooker :542-554 on the integer form of the draw
         const u32x4 w0 = uniform_draw(p, q, 0, gc, g_);
+        if (CUR) return w0.x != 0u;                                                 // (group_draws left the flag there)
         return u53_below(w0.x, w0.y, p.snk_thr);
     };
     // The full-code instantiations live at the register limit (128 per wave at 16 waves per block: they spill): there the rows of a
@@ -560,7 +617,10 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
     // the barriers -- and two row buffers rotate instead of three (propose_de_pf).  Measured together: uniform priors + hard boundaries
     // 508 -> 612 M proposals/s, normal priors 522 -> 572 (spilled registers are reloaded on the generation's critical path).
     constexpr bool PF_AHEAD = !PB;
-    DrawSrc dsn = generation_draws(g0, M0);
+    DrawSrc dsn;
+    if constexpr (CUR) dsn = group_draws(0, M0, zappend >= 0 ? seg0 - 1 : -1);
+    else dsn = generation_draws(g0, M0);
+    int gpos = 0;      // (CUR) this generation's place in its group: cycles 0 .. GRP-1 (a scalar, no division)
     if (PF_AHEAD && !multipair && !draws_say_snooker(dsn, g0)) prefetch_first(dsn, 0, g0, M0);
     // History appends inside the launch (history_lag >= 1 on one GPU: the rows an append writes are not sampled before `lag` more appends
     // have been made, so a launch may run on past it): generation index next_app makes the next one, into rows zappend + (M - M0) + global chain; the
@@ -588,9 +648,15 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
             if (phase == 0) {
                 Ctrl u;
                 const u32x4 w0 = uniform_draw(p, ds, 0, gc, g), w1 = uniform_draw(p, ds, 1, gc, g), w2 = uniform_draw(p, ds, 2, gc, g);
+                if (CUR) {      // the decisions were made with the group's draws (group_draws): fetch this generation's
+                    f.snk = w0.x != 0u; f.cr_idx = (int)w0.y; f.delta = 1; f.glev = (int)w1.x;
+                    u.u_sel = __longlong_as_double((long long)(((unsigned long long)w2.y << 32) | (unsigned long long)w2.x));
+                    u.u_acc = __longlong_as_double((long long)(((unsigned long long)w2.w << 32) | (unsigned long long)w2.z));
+                } else {
                 u.u_snk = u53(w0.x, w0.y); u.u_cr = u53(w0.z, w0.w); u.u_de = u53(w1.x, w1.y); u.u_glev = u53(w1.z, w1.w);
                 u.u_sel = u53(w2.x, w2.y); u.u_acc = u53(w2.z, w2.w);
                 f = step_flags_from(p, u, pr_g, pr_g + p.ncr);                       // Dream.py:246-256
+                }
                 if (lane == 0 && sub == 0) {
                     double* dc = dec + 8 * cl;
                     dc[0] = u.u_sel; dc[1] = u.u_acc; dc[2] = f.snk ? 1.0 : 0.0; dc[3] = (double)f.cr_idx; dc[4] = (double)f.glev;
@@ -669,6 +735,10 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                     if (PF_AHEAD && phase == 0 && round == 0 && !snk_s && !multipair) prefetch_first(ds, 1, g, M);  // the reference set's first rows, ahead of the likelihood pass
                 }
                 if (round == 0 && phase == nph - 1 && !last) {                       // the next generation's draws and first rows
+                    if constexpr (CUR) {      // the next generation's slots come down to lanes 0 .. nslots-1 of the group's registers, or a new group is made
+                        if (++gpos == GRP) { gpos = 0; dsn = group_draws(gi + 1, Mn, app ? next_app + p.thin : next_app); }
+                        else dsn.mine = group_shift(ds.mine);
+                    } else
                     dsn = generation_draws(g + 1u, Mn);
                     if (PF_AHEAD && !multipair && !draws_say_snooker(dsn, g + 1u)) prefetch_first(dsn, 0, g + 1u, Mn);
                 }
