@@ -83,6 +83,34 @@
 // and the entry points below pass the point's row x to the shape.  g is added to the value of a single experiment (l + g) and, with
 // conditions, to the term of condition 0 (l_0 + g); a network without these members compiles to what it compiled to before they existed.
 //
+// RATE LAWS (likelihoods.RateLaw, likelihoods.Hill): a reaction's rate may be
+//     v = k * prod_s y_s^order_s * prod_m h_m(y)
+// with kinetic orders that are the reactants' coefficients or the RateLaw's own, and up to 4 Hill factors of one species each,
+//     h = y^n / (K^n + y^n) (activation)   or   h = K^n / (K^n + y^n) (repression),     n = 1..8,
+// K a parameter (10**x[i] under "log10": dexp(x[i] * 2.302585092994046); x[i] under "linear"), a fixed number > 0 or a monomial.  dy/dt
+// stays N v.  The arithmetic, the same on device and host and in every shape, written once per generator (likelihoods._hill_value,
+// _hill_slope, _rate_product, _rate_slope):
+//   * SLOTS: every distinct (K, n) pair of the network is evaluated once per point, when its rate constants are, in the order of first
+//     use: Kn = K * K * ... * K, n factors multiplied left to right.  Slot m lives behind the rate constants: k[R + m] (the one-lane
+//     long form: behind its distinct parameters; the lane group and the wave: entry R + m of the point's LDS row, evaluated by lane
+//     (R + m) % L).  A network with at least one carries
+//         static constexpr int SLOTS = H;                              and R + H stays within the shape's reaction limit
+//         static double slot(int m, const double* x, bool& good);      (the group form; the one-lane rates() fills its slots itself)
+//   * LIVENESS: a point is not live (-inf) if a coordinate that a K reads is not finite, a K is not finite, or a Kn is not finite or
+//     not > 0.  Under "linear" a sampled K <= 0 rejects the point; nothing divides by zero.
+//   * THE FACTOR at y:  yn = y * y * ... * y (n factors, left to right);  den = Kn + yn;  h = yn / den  or  h = Kn / den.
+//   * ITS DERIVATIVE:  num = ((n * Kn) * y) * ... * y  (n - 1 factors of y, left to right; n = 1: num = Kn);  h' = num / (den * den),
+//     for repression (-num) / (den * den).
+//   * THE PRODUCT v is taken left to right: k, the mass-action factors y_s (order_s times each) in ascending species, then the Hill
+//     factors in the order given.
+//   * THE PRODUCT RULE: dv / dy_q is the sum, in that same order, of the mass-action term (if q has a kinetic order c: the product with
+//     c * y_q^(c-1) in y_q^c's place, as for plain mass action) and one term per Hill factor on q (the product with h' in h's place);
+//     with more than one term: ((t_0) + (t_1)) + ...  A species may be in `order` and in a factor, or in two factors.
+//   * Nothing is clamped: a slightly negative amount (one the negativity rule admits) passes through odd powers with its sign; a den that
+//     is 0 or not finite makes a rate that is not finite, a failed integration.
+// The Jacobian stays analytic, straight-line code with every entry written.  A network without a RateLaw generates the source it always
+// did, and compiles to what it compiled to before the member existed.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -199,6 +227,16 @@ template <class Net> struct has_events<Net, decltype((void)Net::EVENTS)> {
 // ... and the equilibration phase (the head of the file): the network of an object that equilibrates in at least one experiment
 template <class Net, class = void> struct has_equilibrate { static constexpr bool value = false; };
 template <class Net> struct has_equilibrate<Net, decltype((void)Net::EQUILIBRATE)> { static constexpr bool value = Net::EQUILIBRATE; };
+
+// ... and rate laws (the head of the file): SLOTS is the number of distinct Hill (K, n) pairs, the doubles behind the rate constants
+template <class Net, class = void> struct has_slots { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_slots<Net, decltype((void)Net::SLOTS)> {
+    static constexpr bool value = true;
+    static constexpr int count = Net::SLOTS;
+    static_assert(Net::SLOTS >= 1 && Net::R + Net::SLOTS <= 256, "reactions plus slots within the shape's reaction limit");
+};
+// the doubles of a point's rate constants and slots (an array of at least one)
+template <class Net> constexpr int rate_doubles() { return Net::R + has_slots<Net>::count > 0 ? Net::R + has_slots<Net>::count : 1; }
 
 template <class Net>
 DZO_HD bool monomials_live(const double* x)
@@ -640,7 +678,7 @@ struct Array {
 template <class Alg>
 DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out, bool first = true)
 {
-    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    double k[rate_doubles<typename Alg::Net>()];
     if (nsteps_out) *nsteps_out = 0;
     if (!Alg::rates(x, k)) return -__builtin_huge_val();
     return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
@@ -653,7 +691,7 @@ template <class Alg>
 DZO_HD void equilibrate_point(const double* x, const double* blk, double* yss, int* attempts)
 {
     constexpr int S = Alg::Net::S;
-    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    double k[rate_doubles<typename Alg::Net>()];
     const Array<Alg> sh{k, x};
     typename Array<Alg>::State y;
     bool ok = Alg::rates(x, k);
@@ -672,7 +710,7 @@ DZO_HD void equilibrate_point(const double* x, const double* blk, double* yss, i
 template <class Alg>
 DZO_HD double constraint_term(const double* x)
 {
-    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    double k[rate_doubles<typename Alg::Net>()];
     return Alg::rates(x, k) ? add_constraints<typename Alg::Net>(0.0, x, true) : -__builtin_huge_val();
 }
 
@@ -684,7 +722,7 @@ DZO_HD double integrate_conditions(const double* x, const double* hdr, double* t
 {
     const int C = (int)hdr[0];
     const long long stride = (long long)hdr[1], per = (long long)(int)hdr[2 + 5] * Alg::Net::O;
-    double k[Alg::Net::R > 0 ? Alg::Net::R : 1];
+    double k[rate_doubles<typename Alg::Net>()];
     const bool live = Alg::rates(x, k);
     double total = 0.0;
     int steps = 0;
@@ -706,7 +744,7 @@ template <class Alg>
 DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int nsteps, int which, double* y)
 {
     constexpr int S = Alg::Net::S;
-    double k[Alg::Net::R > 0 ? Alg::Net::R : 1], yn[S], ye[S];
+    double k[rate_doubles<typename Alg::Net>()], yn[S], ye[S];
     if (!Alg::rates(x, k)) return false;
 #pragma unroll
     for (int s = 0; s < S; ++s) y[s] = start_amount<typename Alg::Net>(s, x, blk[6 + s]);

@@ -39,6 +39,8 @@
 //     static void obs(const double* y, double* o);
 // and, for a network with monomials (dz_ode.h's head: the construct, its arithmetic and the members live, y0_row, scale, constraints),
 //     static double rate_mono(int j, const double* x, bool& good);    the rate constant of a reaction whose rate_index is -2
+// and, for a network with rate laws (dz_ode.h's head, RATE LAWS: Hill factors and kinetic orders inside rhs_row / jac_entry),
+//     static constexpr int SLOTS;  static double slot(int m, const double* x, bool& good);    Kn of the distinct (K, n) pair m: entry R + m of k
 // Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd; with the
 // equilibration phase: its six doubles at the end.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
 // the group's norm, a group-wide value).
@@ -93,6 +95,9 @@ DZO_HD double pivot_key(double a)          // |a|, a NaN as +inf: the arg-max is
 template <class Net>
 DZO_HD double rate_constant(int j, const double* x, bool& good)
 {
+    if constexpr (has_slots<Net>::value) {      // (entry R + m of the row: the Hill slot m, dz_ode.h's RATE LAWS)
+        if (j >= Net::R) return Net::slot(j - Net::R, x, good);
+    }
     const int pi = Net::rate_index(j);
     if constexpr (has_monomials<Net>::value) {
         if (pi == -2) return Net::rate_mono(j, x, good);
@@ -177,9 +182,9 @@ __device__ __forceinline__ int uniform_index(int v)
     return v;
 }
 
-// The wave's copy of the state in LDS, behind its R + 1 rate constants.
+// The wave's copy of the state in LDS, behind its R + 1 rate constants (a network with rate laws: R + SLOTS + 1).
 template <class Net>
-__device__ __forceinline__ double* wave_state(double* ks) { return ks + Net::R + 1; }
+__device__ __forceinline__ double* wave_state(double* ks) { return ks + Net::R + has_slots<Net>::count + 1; }
 
 // Lane r's entry into the wave's copy.  The fences keep the compiler from moving the reads of the previous copy below the write and the
 // reads of this copy above it; the hardware executes one wave's LDS operations in order.
@@ -220,7 +225,7 @@ template <class Net, int L>
 __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
 {
     bool good = true;
-    for (int j = r; j < Net::R; j += L) {
+    for (int j = r; j < Net::R + has_slots<Net>::count; j += L) {
         bool g;
         ks[j] = rate_constant<Net>(j, x, g);
         good = good && g;
@@ -411,9 +416,10 @@ struct Group {
     }
 };
 
-// The doubles of static LDS a point's lanes share: R + 1 rate constants, and for a wave per point the S doubles of its state behind them.
+// The doubles of static LDS a point's lanes share: R + 1 rate constants (with rate laws: R + SLOTS + 1, the Hill slots behind the rate
+// constants), and for a wave per point the S doubles of its state behind them.
 template <class Net, int L>
-constexpr int group_lds_row() { return Net::R + 1 + (L == 64 ? Net::S : 0); }
+constexpr int group_lds_row() { return Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0); }
 #endif
 
 #if !defined(__HIP__)
@@ -434,7 +440,7 @@ struct HostGroup {
     static bool rates(const double* x, double* k)
     {
         bool good = true;
-        for (int j = 0; j < R; ++j) {
+        for (int j = 0; j < R + has_slots<Net>::count; ++j) {
             bool g;
             k[j] = rate_constant<Net>(j, x, g);
             good = good && g;

@@ -429,6 +429,207 @@ class Monomial:
 
 
 _INT = (int, np.integer)
+_REAL = (int, np.integer, float, np.floating)
+ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated products
+ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction
+
+
+def _checked_constant(v, what):
+    """A rate constant or a Hill constant as the generators take it: a parameter index (int), a float or a Monomial."""
+    if isinstance(v, Monomial):
+        return v
+    if isinstance(v, bool) or not isinstance(v, _REAL):
+        raise ValueError("MassActionODELogLike: %s is a parameter index (int), a fixed constant (float) or a Monomial (got %r)" % (what, v))
+    if isinstance(v, _INT):
+        if v < 0:
+            raise ValueError("MassActionODELogLike: %s: parameter index %d is negative" % (what, v))
+        return int(v)
+    return float(v)
+
+
+class Hill:
+    """A saturating factor of one species in a RateLaw: y^n / (K^n + y^n) for kind "activation", K^n / (K^n + y^n) for "repression".
+    species: the species' index; K: a parameter index (10**x[i] under rate_scale "log10", x[i] under "linear"), a finite float > 0 or a
+    Monomial; n: an integer 1..8 (ODE_MAX_HILL_EXPONENT; powers are repeated products).  An immutable value."""
+    __slots__ = ("species", "K", "n", "kind")
+
+    def __init__(self, species, K, n=1, kind="activation"):
+        if isinstance(species, bool) or not isinstance(species, _INT) or species < 0:
+            raise ValueError("MassActionODELogLike: a Hill factor's species must be a non-negative integer (got %r)" % (species,))
+        K = _checked_constant(K, "a Hill factor's K")
+        if isinstance(K, float) and not (np.isfinite(K) and K > 0):
+            raise ValueError("MassActionODELogLike: a Hill factor's fixed K must be finite and > 0 (got %r)" % (K,))
+        if isinstance(n, bool) or not isinstance(n, _INT) or not 1 <= n <= ODE_MAX_HILL_EXPONENT:
+            raise ValueError("MassActionODELogLike: a Hill factor's n must be an integer 1..%d (got %r)" % (ODE_MAX_HILL_EXPONENT, n))
+        if kind not in ("activation", "repression"):
+            raise ValueError('MassActionODELogLike: a Hill factor\'s kind must be "activation" or "repression" (got %r)' % (kind,))
+        for name, v in zip(self.__slots__, (int(species), K, int(n), kind)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Hill factor is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a Hill factor is immutable")
+
+    def _key(self):
+        return (self.species, type(self.K).__name__, self.K, self.n, self.kind)
+
+    def __eq__(self, other):
+        return isinstance(other, Hill) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return Hill, (self.species, self.K, self.n, self.kind)
+
+    def __repr__(self):
+        return "Hill(%r, %r, %r, %r)" % (self.species, self.K, self.n, self.kind)
+
+
+class RateLaw:
+    """A reaction's rate beyond mass action, where its third element stands: v = k * prod_s y_s^order_s * prod_m h_m(y).
+    rate: what the third element may be without it (a parameter index, a float, a Monomial); factors: at most 4 (ODE_MAX_RATE_FACTORS)
+    Hill objects, multiplied in the order given; order: None -- the kinetic orders are the reactants' coefficients -- or a mapping
+    {species: non-negative integer} that replaces them (kinetics apart from stoichiometry; {}: no mass-action factor).  An immutable
+    value: `factors` is a tuple, `order` None or the tuple of (species, order) pairs in ascending species, zeros dropped."""
+    __slots__ = ("rate", "factors", "order")
+
+    def __init__(self, rate, factors=(), order=None):
+        if isinstance(rate, RateLaw):
+            raise ValueError("MassActionODELogLike: a RateLaw's rate is a parameter index, a float or a Monomial, not another RateLaw")
+        rate = _checked_constant(rate, "a RateLaw's rate")
+        if isinstance(rate, float) and not np.isfinite(rate):
+            raise ValueError("MassActionODELogLike: a RateLaw's fixed rate constant must be finite (got %r)" % (rate,))
+        try:
+            factors = tuple(factors)
+        except TypeError:
+            factors = (factors,)
+        if not all(isinstance(f, Hill) for f in factors):
+            raise ValueError("MassActionODELogLike: a RateLaw's factors must be Hill objects (got %r)" % (factors,))
+        if len(factors) > ODE_MAX_RATE_FACTORS:
+            raise ValueError("MassActionODELogLike: a RateLaw has at most %d factors (got %d)" % (ODE_MAX_RATE_FACTORS, len(factors)))
+        if order is not None:
+            if not hasattr(order, "items"):
+                raise ValueError("MassActionODELogLike: a RateLaw's order must be None or a mapping {species: order} (got %r)" % (order,))
+            pairs = []
+            for s, c in order.items():
+                if isinstance(s, bool) or not isinstance(s, _INT) or s < 0:
+                    raise ValueError("MassActionODELogLike: a RateLaw's order names species %r (a non-negative integer)" % (s,))
+                if isinstance(c, bool) or not isinstance(c, _INT) or c < 0:
+                    raise ValueError("MassActionODELogLike: a RateLaw's kinetic orders must be non-negative integers (got %r for species %d)" % (c, s))
+                if c:
+                    pairs.append((int(s), int(c)))
+            order = tuple(sorted(pairs))
+        for name, v in zip(self.__slots__, (rate, factors, order)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a RateLaw is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a RateLaw is immutable")
+
+    def _key(self):
+        return (type(self.rate).__name__, self.rate, self.factors, self.order)
+
+    def __eq__(self, other):
+        return isinstance(other, RateLaw) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return RateLaw, (self.rate, self.factors, None if self.order is None else dict(self.order))
+
+    def __repr__(self):
+        return "RateLaw(%r, %r, %r)" % (self.rate, list(self.factors), None if self.order is None else dict(self.order))
+
+
+def _rate(rate):
+    """A reaction's rate constant: the third element itself, or a RateLaw's rate."""
+    return rate.rate if isinstance(rate, RateLaw) else rate
+
+
+def _orders(reaction):
+    """A reaction's kinetic orders {species: order}: the reactants' coefficients unless a RateLaw's order replaces them."""
+    law = reaction[2]
+    return dict(law.order) if isinstance(law, RateLaw) and law.order is not None else reaction[0]
+
+
+def _factors(reaction):
+    return reaction[2].factors if isinstance(reaction[2], RateLaw) else ()
+
+
+def _kinetic_species(reaction):
+    """The species a reaction's rate depends on, ascending: those with a kinetic order and those of its Hill factors."""
+    return sorted(set(_orders(reaction)) | {f.species for f in _factors(reaction)})
+
+
+def _hill_slots(reactions):
+    """The distinct (K, n) pairs of the network's Hill factors, in the order of their first use: one slot each (csrc/dz_ode.h)."""
+    slots = []
+    for rx in reactions:
+        for f in _factors(rx):
+            if not any(type(K) is type(f.K) and K == f.K and n == f.n for K, n in slots):
+                slots.append((f.K, f.n))
+    return slots
+
+
+def _slot_of(slots, f):
+    return next(m for m, (K, n) in enumerate(slots) if type(K) is type(f.K) and K == f.K and n == f.n)
+
+
+def _slot_indices(slots):
+    """The parameter indices the slots' K read, bare or inside a monomial, ascending."""
+    return sorted({K for K, _ in slots if isinstance(K, _INT)} | {i for K, _ in slots if isinstance(K, Monomial) for i in K.indices})
+
+
+def _slot_code(K, log10):
+    """(the C++ expression of a slot's K, the parameter indices it reads)"""
+    if isinstance(K, Monomial):
+        kv, idx = _mono_value(K), K.indices
+    elif isinstance(K, _INT):
+        kv, idx = ("dzode::dexp(x[%d] * 2.302585092994046)" % K) if log10 else "x[%d]" % K, (K,)
+    else:
+        kv, idx = _hexlit(K), ()
+    return kv, idx
+
+
+def _hill_value(f, kn):
+    """A Hill factor at y: yn the repeated product of y, den = Kn + yn, yn / den (activation) or Kn / den (repression).  kn: Kn's name."""
+    yn = " * ".join(["y[%d]" % f.species] * f.n)
+    return "((%s) / (%s + %s))" % (yn if f.kind == "activation" else kn, kn, yn)
+
+
+def _hill_slope(f, kn):
+    """Its derivative: num = ((n * Kn) * y) * y ... (n - 1 factors of y, left to right; n = 1: Kn itself), den = Kn + yn,
+    +-num / (den * den): the sign is applied to the quotient."""
+    yn = " * ".join(["y[%d]" % f.species] * f.n)
+    num = " * ".join((["%d.0" % f.n] if f.n > 1 else []) + [kn] + ["y[%d]" % f.species] * (f.n - 1))
+    return "(%s(%s) / ((%s + %s) * (%s + %s)))" % ("" if f.kind == "activation" else "-", num, kn, yn, kn, yn)
+
+
+def _rate_product(kname, reaction, slotname):
+    """v = k * prod y^order (ascending species) * prod h_m (in the order given), left to right."""
+    return _product([kname] + _rate_factors(_orders(reaction)) + [_hill_value(f, slotname(f)) for f in _factors(reaction)])
+
+
+def _rate_slope(kname, reaction, q, slotname):
+    """dv / dy_q: the product rule's sum in the order of the product -- the mass-action term (q has a kinetic order), then one term per
+    Hill factor on q, each the product v with that one factor replaced by its derivative.  A reaction without factors: the one product
+    it always was."""
+    order, hills = _orders(reaction), _factors(reaction)
+    values = [_hill_value(f, slotname(f)) for f in hills]
+    terms = []
+    if q in order:
+        c = order[q]
+        terms.append(_product([kname] + (["%d.0" % c] if c > 1 else []) + _rate_factors(order, skip=q) + values))
+    for m, f in enumerate(hills):
+        if f.species == q:
+            terms.append(_product([kname] + _rate_factors(order) + values[:m] + [_hill_slope(f, slotname(f))] + values[m + 1:]))
+    return terms[0] if len(terms) == 1 else " + ".join("(%s)" % t for t in terms)
 
 
 def _mono_value(m):
@@ -441,7 +642,18 @@ def _mono_value(m):
 
 def _rate_indices(reactions):
     """The parameter indices the rate constants read, bare or inside a monomial, ascending: those whose x is tested for finiteness."""
-    return sorted({r for _, _, r in reactions if isinstance(r, _INT)} | {i for _, _, r in reactions if isinstance(r, Monomial) for i in r.indices})
+    rates = [_rate(r) for _, _, r in reactions]
+    return sorted({r for r in rates if isinstance(r, _INT)} | {i for r in rates if isinstance(r, Monomial) for i in r.indices})
+
+
+def _slot_lines(slots, log10, first):
+    """The one-lane rates()' statements for the Hill slots, k[first + m] = Kn, and their liveness tests (csrc/dz_ode.h, RATE LAWS)."""
+    L, tests = [], ["dzode::finite(x[%d])" % i for i in _slot_indices(slots)]
+    for m, (K, n) in enumerate(slots):
+        L.append("        const double K%d = %s;" % (m, _slot_code(K, log10)[0]))
+        L.append("        k[%d] = %s;" % (first + m, " * ".join(["K%d" % m] * n)))
+        tests += ["dzode::finite(K%d)" % m, "dzode::finite(k[%d])" % (first + m), "k[%d] > 0.0" % (first + m)]
+    return L, tests
 
 
 def _monomial_members(mono):
@@ -533,11 +745,15 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
     integration is the number of distinct parameters."""
     R, O = len(reactions), len(observables)
     N = _stoichiometry(S, reactions)
-    used = sorted({rate for _, _, rate in reactions if isinstance(rate, _INT)})
-    for _, _, rate in reactions:                # (then a slot per distinct monomial, in the order of their first reactions)
+    rates = [_rate(rate) for _, _, rate in reactions]
+    used = sorted({rate for rate in rates if isinstance(rate, _INT)})
+    for rate in rates:                          # (then a slot per distinct monomial, in the order of their first reactions)
         if isinstance(rate, Monomial) and rate not in used:
             used.append(rate)
-    kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for _, _, rate in reactions]
+    kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for rate in rates]
+    slots = _hill_slots(reactions)              # (then the Hill slots: k[len(used) + m] = Kn)
+    slotname = lambda f: "k[%d]" % (len(used) + _slot_of(slots, f))      # noqa: E731
+    slot_lines, slot_tests = _slot_lines(slots, log10, len(used))
 
     def add(target, started, c, e):
         t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
@@ -546,28 +762,31 @@ def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Ne
         started.add(target)
         return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
 
-    L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L = ["    static constexpr int SLOTS = %d;" % len(slots)] if slots else []
+    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     L += ["        k[%d] = %s;" % (i, _mono_value(p) if isinstance(p, Monomial) else ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p)
           for i, p in enumerate(used)]
-    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in _rate_indices(reactions)] + ["dzode::finite(k[%d])" % i for i in range(len(used))]) or "true"))
+    L += slot_lines
+    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in _rate_indices(reactions)] + ["dzode::finite(k[%d])" % i for i in range(len(used))]
+                                                 + slot_tests) or "true"))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     started = set()
-    for r, (reac, _, _) in enumerate(reactions):
+    for r, reaction in enumerate(reactions):
         rows = [s for s in range(S) if N[s, r] != 0]
         if not rows:
             continue
-        L.append("        const double v%d = %s;" % (r, _product([kname[r]] + _rate_factors(reac))))
+        L.append("        const double v%d = %s;" % (r, _rate_product(kname[r], reaction, slotname)))
         L += [add("f[%d]" % s, started, int(N[s, r]), "v%d" % r) for s in rows]
         L.append("        " + " ".join("DZODE_FENCE(f[%d]);" % s for s in rows))
     L += ["        f[%d] = 0.0;" % s for s in range(S) if "f[%d]" % s not in started]
     L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
     started = set()
-    for r, (reac, _, _) in enumerate(reactions):        # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
+    for r, reaction in enumerate(reactions):            # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: _rate_slope)
         rows = [s for s in range(S) if N[s, r] != 0]
-        for q, c in sorted(reac.items()):
+        for q in _kinetic_species(reaction):
             if not rows:
                 continue
-            L.append("        const double d%d_%d = %s;" % (r, q, _product([kname[r]] + (["%d.0" % c] if c > 1 else []) + _rate_factors(reac, skip=q))))
+            L.append("        const double d%d_%d = %s;" % (r, q, _rate_slope(kname[r], reaction, q, slotname)))
             L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
             L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
     L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
@@ -582,8 +801,12 @@ def _ode_source(S, reactions, observables, log10, items=False, mono=None, events
     if R > _ODE_WHOLE_SUMS:
         return _ode_long_source(S, reactions, observables, log10, entries, mono, events, equilibrate)
     N = _stoichiometry(S, reactions)
-    L = ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
-    for r, (_, _, rate) in enumerate(reactions):
+    slots = _hill_slots(reactions)              # (the Hill slots behind the rate constants: k[R + m] = Kn)
+    slotname = lambda f: "k[%d]" % (R + _slot_of(slots, f))      # noqa: E731
+    slot_lines, slot_tests = _slot_lines(slots, log10, R)
+    L = ["    static constexpr int SLOTS = %d;" % len(slots)] if slots else []
+    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    for r, rate in enumerate(_rate(rate) for _, _, rate in reactions):
         if isinstance(rate, _INT):
             L.append("        k[%d] = %s;" % (r, ("dzode::dexp(x[%d] * 2.302585092994046)" % rate) if log10 else "x[%d]" % rate))
         elif isinstance(rate, Monomial):
@@ -591,19 +814,21 @@ def _ode_source(S, reactions, observables, log10, items=False, mono=None, events
         else:
             L.append("        k[%d] = %s;" % (r, _hexlit(rate)))
     used = _rate_indices(reactions)             # (10**-inf is a finite 0: test x itself)
-    L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)]))
+    L += slot_lines
+    L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)] + slot_tests))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
-    for r, (reac, _, _) in enumerate(reactions):
-        L.append("        const double v%d = %s;" % (r, _product(["k[%d]" % r] + _rate_factors(reac))))
+    for r, reaction in enumerate(reactions):
+        L.append("        const double v%d = %s;" % (r, _rate_product("k[%d]" % r, reaction, slotname)))
     for s in range(S):
         L.append("        f[%d] = %s;" % (s, _combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
     L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
-    for r, (reac, _, _) in enumerate(reactions):        # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
-        for q, c in sorted(reac.items()):
-            L.append("        const double d%d_%d = %s;" % (r, q, _product(["k[%d]" % r] + (["%d.0" % c] if c > 1 else []) + _rate_factors(reac, skip=q))))
+    for r, reaction in enumerate(reactions):            # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: _rate_slope)
+        for q in _kinetic_species(reaction):
+            L.append("        const double d%d_%d = %s;" % (r, q, _rate_slope("k[%d]" % r, reaction, q, slotname)))
+    kinetic = [_kinetic_species(reaction) for reaction in reactions]
     for s in range(S):
         for q in range(S):
-            terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in reactions[r][0]]
+            terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in kinetic[r]]
             L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
     return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events, equilibrate)
 
@@ -633,25 +858,34 @@ def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono
             out.append(indent + "v = v + %s * (%s);" % (coefficient(j), e))
         return out + [indent + "return v;"]
 
+    rates = [_rate(rate) for _, _, rate in reactions]
+    slots = _hill_slots(reactions)              # (the Hill slots behind the rate constants: k[R + m] = Kn, by lane (R + m) % L once per point)
+    slotname = lambda f: "k[z + %d]" % (R + _slot_of(slots, f))      # noqa: E731
     L = ["    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
          "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %d;" % (j, -2 if isinstance(rate, Monomial) else rate) for j, (_, _, rate) in enumerate(reactions) if isinstance(rate, _INT + (Monomial,))]
+    L += ["        case %d: return %d;" % (j, -2 if isinstance(rate, Monomial) else rate) for j, rate in enumerate(rates) if isinstance(rate, _INT + (Monomial,))]
     L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, (_, _, rate) in enumerate(reactions) if not isinstance(rate, _INT + (Monomial,))]
+    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, rate in enumerate(rates) if not isinstance(rate, _INT + (Monomial,))]
     L += ["        default: return 0.0;", "        }", "    }"]
+    if slots:
+        L += ["    static constexpr int SLOTS = %d;" % len(slots), "    DZO_HD static double slot(int m, const double* x, bool& good)", "    {", "        switch (m) {"]
+        for m, (K, n) in enumerate(slots):
+            kv, idx = _slot_code(K, log10)
+            L.append("        case %d: { const double K = %s; const double v = %s; good = %s; return v; }"
+                     % (m, kv, " * ".join(["K"] * n), " && ".join(["dzode::finite(x[%d])" % i for i in idx] + ["dzode::finite(K)", "dzode::finite(v)", "v > 0.0"])))
+        L += ["        default: good = false; return 0.0;", "        }", "    }"]
     if mono:                                             # (rate_index -2: the reaction's own expression, by lane j % L once per point)
         L += ["    DZO_HD static double rate_mono(int j, const double* x, bool& good)", "    {", "        switch (j) {"]
-        for j, (_, _, rate) in enumerate(reactions):
+        for j, rate in enumerate(rates):
             if isinstance(rate, Monomial):
                 L.append("        case %d: { const double v = %s; good = %s; return v; }"
                          % (j, _mono_value(rate), " && ".join(["dzode::finite(x[%d])" % i for i in rate.indices] + ["dzode::finite(v)"])))
         L += ["        default: good = false; return 0.0;", "        }", "    }"]
     L += ["    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
-    L += weighted_sum([(j, _product(["k[z + %d]" % j] + _rate_factors(reactions[j][0]))) for j in range(R) if np.any(N[:, j] != 0)], "        ")
+    L += weighted_sum([(j, _rate_product("k[z + %d]" % j, reactions[j], slotname)) for j in range(R) if np.any(N[:, j] != 0)], "        ")
     L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
     for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
-        terms = [(j, _product(["k[z + %d]" % j] + (["%d.0" % reactions[j][0][q]] if reactions[j][0][q] > 1 else []) + _rate_factors(reactions[j][0], skip=q)))
-                 for j in range(R) if q in reactions[j][0] and np.any(N[:, j] != 0)]
+        terms = [(j, _rate_slope("k[z + %d]" % j, reactions[j], q, slotname)) for j in range(R) if q in _kinetic_species(reactions[j]) and np.any(N[:, j] != 0)]
         L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
     L += ["        default: return 0.0;", "        }", "    }"] + (_monomial_members(mono) if mono else [])
     return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes, events, equilibrate)
@@ -763,7 +997,28 @@ class MassActionODELogLike:
     Its value is computed the same way on the device and the host (csrc/dz_ode.h: the sum in ascending index, then dzode::dexp) and
     does not depend on rate_scale; Monomial({i: 1}) as a rate gives the bits of the bare index i under "log10".  A point at which a
     coordinate read by a monomial, or a monomial's value, is not finite is -inf.  ndim is inferred over every index read, bare or
-    inside a monomial.  A model that uses none of this generates the source, and runs the kernels, it always did."""
+    inside a monomial.  A model that uses none of this generates the source, and runs the kernels, it always did.
+
+    Saturating rate laws: a RateLaw(rate, factors=(), order=None) may stand where a reaction's third element stands, for a rate that is
+    not mass action: v = k * prod_s y_s^order_s * prod_m h_m(y), dy/dt = N v as before.  `rate` is what the third element may be
+    without it; `order` None keeps the reactants' coefficients as kinetic orders, a mapping {species: non-negative integer} replaces
+    them ({}: no mass-action factor); `factors` are up to 4 (ODE_MAX_RATE_FACTORS) Hill(species, K, n=1, kind="activation"):
+    y^n / (K^n + y^n), or K^n / (K^n + y^n) for kind "repression", with K a parameter index (10**x[i] or x[i], by rate_scale), a
+    finite float > 0 or a Monomial and n an integer 1..8 (ODE_MAX_HILL_EXPONENT; powers are repeated products):
+        ({S: 1}, {P: 1}, RateLaw(iV, [Hill(S, iKm)], order={}))             # Michaelis-Menten: Vmax S / (Km + S)
+        ({S: 1}, {P: 1}, RateLaw(ikcat, [Hill(S, iKm)], order={E: 1}))      # kcat E S / (Km + S)
+        ({}, {M: 1}, RateLaw(ialpha, [Hill(Prot, iK, 2, "repression")]))    # repressed synthesis
+    The contract (csrc/dz_ode.h's head, RATE LAWS), the same in both builds and every shape: each distinct (K, n) pair is evaluated
+    once per point into a SLOT beside the rate constants, Kn = K * K * ... (n factors, left to right), and reactions plus slots stay
+    within the shape's reaction limit (64 / 128 / 256); a point is -inf if a coordinate that a K reads or a K is not finite, or a Kn is
+    not finite or not > 0 (under "linear" a sampled K <= 0 rejects the point); a factor is yn / (Kn + yn) or Kn / (Kn + yn) with yn the
+    repeated product of y, its derivative +-(n Kn y^(n-1)) / ((Kn + yn) (Kn + yn)); v is the product of k, the mass-action factors in
+    ascending species and the Hill factors in the order given, and a Jacobian column is the product rule's sum in that order (a
+    species may be in `order` and in a factor, or in two factors).  Nothing is clamped; the Jacobian stays analytic.  ndim covers
+    the indices every K reads.  A RateLaw with no factors and order=None is the plain reaction, source and bits; a model without a
+    RateLaw generates the source and the data block it always did.  Conditions, Monomials, events, equilibration, fixed_steps,
+    simulate and steady_state work with it unchanged.  Not supported: a non-integer or sampled Hill exponent, arbitrary rate
+    expressions, time-dependent inputs, rate laws in event amounts."""
 
     conditions = None       # (an object pickled before the keyword existed)
     events = None           # (likewise)
@@ -798,9 +1053,15 @@ class MassActionODELogLike:
                         raise ValueError("MassActionODELogLike: reaction %d names species %r (0..%d)" % (r, s, S - 1))
                     if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
                         raise ValueError("MassActionODELogLike: reaction %d: stoichiometric coefficients must be non-negative integers (got %r)" % (r, c))
-            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating, Monomial)):
-                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int), a fixed rate constant (float) or a Monomial" % r)
-            if isinstance(rate, Monomial):
+            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating, Monomial, RateLaw)):
+                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int), a fixed rate constant (float), a Monomial or a RateLaw" % r)
+            if isinstance(rate, RateLaw):
+                for s in [s for s, _ in rate.order or ()] + [f.species for f in rate.factors]:
+                    if not 0 <= s < S:
+                        raise ValueError("MassActionODELogLike: reaction %d: its RateLaw names species %r (0..%d)" % (r, s, S - 1))
+                if not rate.factors and rate.order is None:          # (nothing beyond its rate: the plain reaction, source and bits)
+                    rate = rate.rate
+            elif isinstance(rate, Monomial):
                 pass
             elif isinstance(rate, (int, np.integer)):
                 if rate < 0:
@@ -811,7 +1072,10 @@ class MassActionODELogLike:
             else:
                 rate = float(rate)
             rx.append(({int(s): int(c) for s, c in dict(reac).items() if c}, {int(s): int(c) for s, c in dict(prod).items() if c}, rate))
-        idx = [r[2] for r in rx if isinstance(r[2], int)] + [i for r in rx if isinstance(r[2], Monomial) for i in r[2].indices]
+        slots = _hill_slots(rx)
+        if len(rx) + len(slots) > lim["reactions"]:
+            raise ValueError("MassActionODELogLike: reactions plus distinct Hill (K, n) pairs must stay within %d (got %d + %d)" % (lim["reactions"], len(rx), len(slots)))
+        idx = _rate_indices(rx) + _slot_indices(slots)
         if conditions is not None:
             conditions = list(conditions)
             if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
@@ -1034,7 +1298,7 @@ class MassActionODELogLike:
     def _monomials(self):
         """What the generated network needs beyond rate constants of one parameter each, or None: then the source is what it always was
         (a scale factor of exactly 1.0 multiplies nothing)."""
-        if (self.y0_monomials or self.constraints or any(isinstance(r[2], Monomial) for r in self.reactions)
+        if (self.y0_monomials or self.constraints or any(isinstance(_rate(r[2]), Monomial) for r in self.reactions)
                 or (self.scale is not None and any(f != 1.0 for f in self.scale))):
             return dict(y0=self.y0_monomials, scale=self.scale, constraints=self.constraints)
         return None
