@@ -1,0 +1,374 @@
+"""The C++ text pydream_amd.likelihoods.MassActionODELogLike generates for csrc/dz_ode.h and csrc/dz_ode_group.h: one description of the
+checked network (_Network) and the three emitters that read it -- one lane with every sum whole, one lane reaction by reaction, and the
+lane group.  The text is the interface to both builds and the key of the kernel cache: it does not change with the code that writes it."""
+import numpy as np
+
+from ._ode_values import _INT, Monomial, RateLaw
+
+_LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
+
+
+def _hexlit(v):
+    """A C++17 hexadecimal floating literal: the double exactly."""
+    v = float(v)
+    return "(%s)" % v.hex() if np.isfinite(v) else ("(__builtin_huge_val())" if v > 0 else "(-__builtin_huge_val())")
+
+
+def _rate(rate):
+    """A reaction's rate constant: the third element itself, or a RateLaw's rate."""
+    return rate.rate if isinstance(rate, RateLaw) else rate
+
+
+def _orders(reaction):
+    """A reaction's kinetic orders {species: order}: the reactants' coefficients unless a RateLaw's order replaces them."""
+    law = reaction[2]
+    return dict(law.order) if isinstance(law, RateLaw) and law.order is not None else reaction[0]
+
+
+def _factors(reaction):
+    return reaction[2].factors if isinstance(reaction[2], RateLaw) else ()
+
+
+def _kinetic_species(reaction):
+    """The species a reaction's rate depends on, ascending: those with a kinetic order and those of its Hill factors."""
+    return sorted(set(_orders(reaction)) | {f.species for f in _factors(reaction)})
+
+
+def _hill_slots(reactions):
+    """The distinct (K, n) pairs of the network's Hill factors, in the order of their first use: one slot each (csrc/dz_ode.h).
+    A mapping from (type(K), K, n) -- the index 1 and the constant 1.0 are two -- to the slot's number."""
+    slots = {}
+    for rx in reactions:
+        for f in _factors(rx):
+            slots.setdefault((type(f.K), f.K, f.n), len(slots))
+    return slots
+
+
+def _indices_read(constants):
+    """The parameter indices the constants read, bare or inside a monomial, ascending: those whose x is tested for finiteness."""
+    return sorted({c for c in constants if isinstance(c, _INT)} | {i for c in constants if isinstance(c, Monomial) for i in c.indices})
+
+
+def _rate_indices(reactions):
+    return _indices_read([_rate(r) for _, _, r in reactions])
+
+
+def _slot_indices(slots):
+    return _indices_read([K for _, K, _ in slots])
+
+
+def _dexp10(arg):
+    return "dzode::dexp(%s * 2.302585092994046)" % arg
+
+
+def _mono_value(m):
+    """The C++ expression of a monomial's value: the sum in ascending index, an exponent of +-1 as a plain add or subtract."""
+    out = _hexlit(m.log10_factor)
+    for i, e in m.exponents:
+        out += " + x[%d]" % i if e == 1.0 else " - x[%d]" % i if e == -1.0 else " + %s * x[%d]" % (_hexlit(e), i)
+    return _dexp10("(%s)" % out)
+
+
+def _finite(indices, values=()):
+    """The liveness tests of the coordinates x[i] and of the named values."""
+    return ["dzode::finite(x[%d])" % i for i in indices] + ["dzode::finite(%s)" % v for v in values]
+
+
+class _Network:
+    """What the emitters read, made once per source() from the checked MassActionODELogLike: S, the reactions, the observables and
+    log10; the stoichiometry N, the rate constants (`rates`: a RateLaw's own) and the kinetic species per reaction; the Hill slots
+    (_hill_slots); mono (MassActionODELogLike._monomials), the largest event count, the equilibrate flag; items (the entry points for
+    several conditions per point) and lanes."""
+
+    def __init__(self, like):
+        self.S, self.reactions, self.observables, self.log10 = like.n_species, like.reactions, like.observables, like.log10
+        self.mono, self.events, self.equilibrate = like._monomials(), like._max_events(), like._equilibrates()
+        self.items, self.lanes = like.conditions is not None, like.lanes_per_point
+        self.R = len(self.reactions)
+        self.N = np.zeros((self.S, self.R), dtype=np.int64)
+        for r, (reac, prod, _) in enumerate(self.reactions):
+            for s, c in reac.items():
+                self.N[s, r] -= c
+            for s, c in prod.items():
+                self.N[s, r] += c
+        self.rates = [_rate(rate) for _, _, rate in self.reactions]
+        self.kinetic = [_kinetic_species(reaction) for reaction in self.reactions]
+        self.slots = _hill_slots(self.reactions)
+
+    def constant(self, c):
+        """(the C++ expression of a rate constant or a slot's K, the parameter indices it reads): a Monomial, a sampled constant under
+        the rate scale, or a literal"""
+        if isinstance(c, Monomial):
+            return _mono_value(c), c.indices
+        if isinstance(c, _INT):
+            return _dexp10("x[%d]" % c) if self.log10 else "x[%d]" % c, (c,)
+        return _hexlit(c), ()
+
+    def slot_of(self, f):
+        return self.slots[type(f.K), f.K, f.n]
+
+    def rate_code(self, kname, first):
+        """(v(r), dv(r, q)): the expressions of reaction r's rate and of its derivative by y_q under an emitter's names -- kname[r] for
+        the rate constant, k[first + m] (the lane group: k[z + first + m]) for slot m."""
+        slotname = "k[%d]" if self.lanes == 1 else "k[z + %d]"
+        kn = lambda f: slotname % (first + self.slot_of(f))      # noqa: E731
+
+        def v(r):
+            """v = k * prod y^order (ascending species) * prod h_m (in the order given), left to right."""
+            reaction = self.reactions[r]
+            return _product([kname[r]] + _rate_factors(_orders(reaction)) + [_hill_value(f, kn(f)) for f in _factors(reaction)])
+
+        def dv(r, q):
+            """dv / dy_q: the product rule's sum in the order of the product -- the mass-action term (q has a kinetic order), then one term per
+            Hill factor on q, each the product v with that one factor replaced by its derivative.  A reaction without factors: the one product
+            it always was."""
+            reaction = self.reactions[r]
+            order, hills = _orders(reaction), _factors(reaction)
+            values = [_hill_value(f, kn(f)) for f in hills]
+            terms = []
+            if q in order:
+                c = order[q]
+                terms.append(_product([kname[r]] + (["%d.0" % c] if c > 1 else []) + _rate_factors(order, skip=q) + values))
+            for m, f in enumerate(hills):
+                if f.species == q:
+                    terms.append(_product([kname[r]] + _rate_factors(order) + values[:m] + [_hill_slope(f, kn(f))] + values[m + 1:]))
+            return terms[0] if len(terms) == 1 else " + ".join("(%s)" % t for t in terms)
+        return v, dv
+
+
+def _hill_value(f, kn):
+    """A Hill factor at y: yn the repeated product of y, den = Kn + yn, yn / den (activation) or Kn / den (repression).  kn: Kn's name."""
+    yn = " * ".join(["y[%d]" % f.species] * f.n)
+    return "((%s) / (%s + %s))" % (yn if f.kind == "activation" else kn, kn, yn)
+
+
+def _hill_slope(f, kn):
+    """Its derivative: num = ((n * Kn) * y) * y ... (n - 1 factors of y, left to right; n = 1: Kn itself), den = Kn + yn,
+    +-num / (den * den): the sign is applied to the quotient."""
+    yn = " * ".join(["y[%d]" % f.species] * f.n)
+    num = " * ".join((["%d.0" % f.n] if f.n > 1 else []) + [kn] + ["y[%d]" % f.species] * (f.n - 1))
+    return "(%s(%s) / ((%s + %s) * (%s + %s)))" % ("" if f.kind == "activation" else "-", num, kn, yn, kn, yn)
+
+
+def _slot_lines(net, first):
+    """The one-lane rates()' statements for the Hill slots, k[first + m] = Kn, and their liveness tests (csrc/dz_ode.h, RATE LAWS)."""
+    L, tests = [], _finite(_slot_indices(net.slots))
+    for (_, K, n), m in net.slots.items():
+        L.append("        const double K%d = %s;" % (m, net.constant(K)[0]))
+        L.append("        k[%d] = %s;" % (first + m, " * ".join(["K%d" % m] * n)))
+        tests += _finite((), ["K%d" % m, "k[%d]" % (first + m)]) + ["k[%d] > 0.0" % (first + m)]
+    return L, tests
+
+
+def _monomial_members(mono):
+    """The members of a generated network that has monomials (csrc/dz_ode.h's head), for the one-lane and the lane-group source alike.
+    mono: dict(y0={species: Monomial}, scale=[float | Monomial] or None, constraints=[(Monomial, loc, sd)])."""
+    y0, scale, cons = mono["y0"], mono["scale"] or [], mono["constraints"]
+    outside = [m for _, m in sorted(y0.items())] + [f for f in scale if isinstance(f, Monomial)] + [m for m, _, _ in cons]
+    tests = _finite(_indices_read(outside), [_mono_value(m) for m in outside])
+    L = ["    static constexpr bool MONOMIALS = true;", "    DZO_HD static bool live(const double* x)", "    {",
+         "        return %s;" % (" && ".join(tests) or "true"), "    }",
+         "    DZO_HD static double y0_row(int r, const double* x, double b)", "    {"]
+    if y0:
+        L += ["        const double m%d = %s;" % (s, _mono_value(m)) for s, m in sorted(y0.items())]
+        sel = "0.0"
+        for s in sorted(y0, reverse=True):
+            sel = "r == %d ? m%d : %s" % (s, s, sel)
+        L += ["        const double m = %s;" % sel, "        return b != b ? m : b;"]
+    else:
+        L.append("        return b;")
+    L += ["    }", "    DZO_HD static void scale(const double* x, double* o)", "    {"]
+    L += ["        o[%d] = %s * o[%d];" % (q, _mono_value(f) if isinstance(f, Monomial) else _hexlit(f), q) for q, f in enumerate(scale) if f != 1.0]
+    L.append("    }")
+    if cons:
+        G0 = float(sum(-np.log(sd) - _LOG_2PI_HALF for _, _, sd in cons))
+        L += ["    DZO_HD static double constraints(const double* x)", "    {", "        double acc = 0.0;"]
+        L += ["        { const double r = (%s - %s) / %s; acc = acc - 0.5 * r * r; }" % (_mono_value(m), _hexlit(loc), _hexlit(sd)) for m, loc, sd in cons]
+        L += ["        return %s + acc;" % _hexlit(G0), "    }"]
+    return L
+
+
+def _product(factors):
+    return " * ".join(factors) if factors else "1.0"
+
+
+def _rate_factors(reac, skip=None):
+    out = []
+    for s, c in sorted(reac.items()):
+        out += ["y[%d]" % s] * (c - (1 if s == skip else 0))
+    return out
+
+
+def _combine(terms):                        # [(integer coefficient, expression)] -> a sum in this order
+    out = ""
+    for c, e in terms:
+        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
+        out += ("-" if c < 0 else "") + t if not out else (" - " if c < 0 else " + ") + t
+    return out or "0.0"
+
+
+def _obs_lines(S, observables):
+    L = []
+    for o, row in enumerate(observables):
+        terms = ["y[%d]" % s if row[s] == 1.0 else "%s * y[%d]" % (_hexlit(row[s]), s) for s in range(S) if row[s] != 0.0]
+        L.append("        o[%d] = %s;" % (o, " + ".join(terms) if terms else "0.0"))
+    return L
+
+
+def _net_source(net, body):
+    """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
+    closing brace of the last one), the members of a network with monomials, the observables and the entry macro.  net.events: the
+    largest event count over the object's experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  net.equilibrate: some
+    experiment equilibrates first; the member EQUILIBRATE only then."""
+    if net.lanes == 1:
+        header, entries = "dz_ode.h", "DZODE_ITEM_ENTRIES(Net)" if net.items else "DZODE_ENTRIES(Net)"
+    else:
+        header, entries = "dz_ode_group.h", ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if net.items else "DZODE_GROUP_ENTRIES(Net, %d)") % net.lanes
+    L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (net.S, net.R, len(net.observables))]
+    L += ["    static constexpr int EVENTS = %d;" % net.events] if net.events else []
+    L += ["    static constexpr bool EQUILIBRATE = true;"] if net.equilibrate else []
+    L += body + (_monomial_members(net.mono) if net.mono else [])
+    L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(net.S, net.observables) + ["    }", "};", entries, ""]
+    return '#include "%s"\n' % header + "\n".join(L)
+
+
+_ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
+
+
+def _ode_long_source(net):
+    """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
+    order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
+    reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
+    used, not one per reaction, and a fixed rate constant is a literal where it is used: what stays in registers through the
+    integration is the number of distinct parameters."""
+    S, N = net.S, net.N
+    used = sorted({rate for rate in net.rates if isinstance(rate, _INT)})
+    for rate in net.rates:                      # (then a slot per distinct monomial, in the order of their first reactions)
+        if isinstance(rate, Monomial) and rate not in used:
+            used.append(rate)
+    kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for rate in net.rates]
+    v, dv = net.rate_code(kname, len(used))
+    slot_lines, slot_tests = _slot_lines(net, len(used))    # (then the Hill slots: k[len(used) + m] = Kn)
+    started = set()
+
+    def add(target, c, e):
+        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
+        if target in started:
+            return "        %s = %s %s %s;" % (target, target, "-" if c < 0 else "+", t)
+        started.add(target)
+        return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
+
+    L = ["    static constexpr int SLOTS = %d;" % len(net.slots)] if net.slots else []
+    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L += ["        k[%d] = %s;" % (i, net.constant(p)[0]) for i, p in enumerate(used)]
+    L += slot_lines
+    L.append("        return %s;" % (" && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % i for i in range(len(used))]) + slot_tests) or "true"))
+    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
+    for r in range(net.R):
+        rows = [s for s in range(S) if N[s, r] != 0]
+        if not rows:
+            continue
+        L.append("        const double v%d = %s;" % (r, v(r)))
+        L += [add("f[%d]" % s, int(N[s, r]), "v%d" % r) for s in rows]
+        L.append("        " + " ".join("DZODE_FENCE(f[%d]);" % s for s in rows))
+    L += ["        f[%d] = 0.0;" % s for s in range(S) if "f[%d]" % s not in started]
+    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
+    for r in range(net.R):                              # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: rate_code's dv)
+        rows = [s for s in range(S) if N[s, r] != 0]
+        for q in net.kinetic[r]:
+            if not rows:
+                continue
+            L.append("        const double d%d_%d = %s;" % (r, q, dv(r, q)))
+            L += [add("J[%d]" % (s * S + q), int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
+            L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
+    L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
+    return _net_source(net, L + ["    }"])
+
+
+def _ode_source(net):
+    """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
+    straight-line code with constant indices; powers as repeated products.  net.items: the entry points for several conditions per point."""
+    S, R, N = net.S, net.R, net.N
+    if R > _ODE_WHOLE_SUMS:
+        return _ode_long_source(net)
+    v, dv = net.rate_code(["k[%d]" % r for r in range(R)], R)
+    slot_lines, slot_tests = _slot_lines(net, R)        # (the Hill slots behind the rate constants: k[R + m] = Kn)
+    L = ["    static constexpr int SLOTS = %d;" % len(net.slots)] if net.slots else []
+    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
+    L += ["        k[%d] = %s;" % (r, net.constant(rate)[0]) for r, rate in enumerate(net.rates)]
+    L += slot_lines                             # (10**-inf is a finite 0: test x itself)
+    L.append("        return %s;" % " && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % r for r in range(R)]) + slot_tests))
+    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
+    L += ["        const double v%d = %s;" % (r, v(r)) for r in range(R)]
+    for s in range(S):
+        L.append("        f[%d] = %s;" % (s, _combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
+    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
+    for r in range(R):                                  # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: rate_code's dv)
+        L += ["        const double d%d_%d = %s;" % (r, q, dv(r, q)) for q in net.kinetic[r]]
+    for s in range(S):
+        for q in range(S):
+            terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in net.kinetic[r]]
+            L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
+    return _net_source(net, L + ["    }"])
+
+
+def _ode_group_source(net):
+    """The generated network struct for the lane-group solver and, with lanes=64, the wave-per-point one (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
+    its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
+    stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
+    diverge inside the right-hand side.  Every f[r] and J[r][q] is the sum over the reactions (for J: those with q among the reactants)
+    in ascending reaction index of coefficient(r) * (k[j] * (nu) * y...) -- written here once, compiled for both sides."""
+    S, R, N = net.S, net.R, net.N
+
+    def coefficient(j):                     # N[r][j] as a function of r
+        out = "0.0"
+        for s in reversed([s for s in range(S) if N[s, j] != 0]):
+            out = "r == %d ? %d.0 : %s" % (s, N[s, j], out)
+        return "(%s)" % out
+
+    def weighted_sum(terms, indent):        # [(j, expression)] -> statements that leave the sum in v
+        if not terms:
+            return [indent + "return 0.0;"]
+        out = [indent + "int z = 0;", indent + "double v = %s * (%s);" % (coefficient(terms[0][0]), terms[0][1])]
+        for t, (j, e) in enumerate(terms[1:], 1):
+            if t % 4 == 0:                  # (a long sum in groups of four terms: see DZODE_SUM_FENCE in csrc/dz_ode_group.h)
+                out.append(indent + "DZODE_SUM_FENCE(v, r, z);")
+            out.append(indent + "v = v + %s * (%s);" % (coefficient(j), e))
+        return out + [indent + "return v;"]
+
+    # (the Hill slots behind the rate constants: k[R + m] = Kn, by lane (R + m) % L once per point)
+    v, dv = net.rate_code(["k[z + %d]" % j for j in range(R)], R)
+    sampled = _INT + (Monomial,)
+    L = ["    static constexpr bool LOG10 = %s;" % ("true" if net.log10 else "false"),
+         "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
+    L += ["        case %d: return %d;" % (j, -2 if isinstance(rate, Monomial) else rate) for j, rate in enumerate(net.rates) if isinstance(rate, sampled)]
+    L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
+    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, rate in enumerate(net.rates) if not isinstance(rate, sampled)]
+    L += ["        default: return 0.0;", "        }", "    }"]
+    if net.slots:
+        L += ["    static constexpr int SLOTS = %d;" % len(net.slots), "    DZO_HD static double slot(int m, const double* x, bool& good)", "    {", "        switch (m) {"]
+        for (_, K, n), m in net.slots.items():
+            kv, idx = net.constant(K)
+            L.append("        case %d: { const double K = %s; const double v = %s; good = %s; return v; }"
+                     % (m, kv, " * ".join(["K"] * n), " && ".join(_finite(idx, ["K", "v"]) + ["v > 0.0"])))
+        L += ["        default: good = false; return 0.0;", "        }", "    }"]
+    if net.mono:                                         # (rate_index -2: the reaction's own expression, by lane j % L once per point)
+        L += ["    DZO_HD static double rate_mono(int j, const double* x, bool& good)", "    {", "        switch (j) {"]
+        for j, rate in enumerate(net.rates):
+            if isinstance(rate, Monomial):
+                kv, idx = net.constant(rate)
+                L.append("        case %d: { const double v = %s; good = %s; return v; }" % (j, kv, " && ".join(_finite(idx, ["v"]))))
+        L += ["        default: good = false; return 0.0;", "        }", "    }"]
+    L += ["    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
+    L += weighted_sum([(j, v(j)) for j in range(R) if np.any(N[:, j] != 0)], "        ")
+    L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
+    for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
+        terms = [(j, dv(j, q)) for j in range(R) if q in net.kinetic[j] and np.any(N[:, j] != 0)]
+        L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
+    return _net_source(net, L + ["        default: return 0.0;", "        }", "    }"])
+
+
+def generate(like):
+    """The source of a checked MassActionODELogLike: the one-lane struct, or the lane group's."""
+    net = _Network(like)
+    return _ode_source(net) if net.lanes == 1 else _ode_group_source(net)

@@ -1,0 +1,193 @@
+"""The limits of pydream_amd.likelihoods.MassActionODELogLike, the predicates its checks are made of, and the immutable values a network
+is written with: Monomial, Hill, RateLaw."""
+import numpy as np
+
+ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
+ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
+ODE_WAVE_LIMITS = dict(species=64, reactions=256, observables=16, times=4096, lanes=(64,), conditions=64)            # lanes_per_point=64: 33..64 species
+ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
+ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
+ODE_EQUILIBRATE_MAX_STEPS = 2000    # equilibrate=...: the attempted steps of the phase before the experiment, unless its "max_steps" says otherwise
+ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
+ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated products
+ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction
+_INT = (int, np.integer)
+_REAL = (int, np.integer, float, np.floating)
+
+
+def _is_int(v, lo=None, hi=None):
+    """v is an integer and no bool, with lo <= v and v <= hi where they are given."""
+    return not isinstance(v, bool) and isinstance(v, _INT) and (lo is None or v >= lo) and (hi is None or v <= hi)
+
+
+def _is_real(v):
+    """v is a finite real number and no bool."""
+    return not isinstance(v, bool) and isinstance(v, _REAL) and bool(np.isfinite(v))
+
+
+class Monomial:
+    """10**(log10_factor + sum_i exponents[i] * x[i]): a product of powers of the sampled constants 10**x[i] times a fixed factor, for
+    MassActionODELogLike -- a reaction's rate constant (kr = KD kf: Monomial({i: 1}, log10(kf)); a rate closed by a thermodynamic cycle,
+    k4 = k1 k2 / k3: Monomial({0: 1, 1: 1, 2: -1})), a sampled start amount, an observable's scale factor, or the argument of a Gaussian
+    constraint.  exponents: a non-empty mapping from parameter index to a finite, non-zero float; log10_factor: finite.  An immutable
+    value: `exponents` is the tuple of (index, exponent) pairs in ascending index, the order in which the device and the host build add
+    them (csrc/dz_ode.h)."""
+    __slots__ = ("exponents", "log10_factor")
+
+    def __init__(self, exponents, log10_factor=0.0):
+        if not hasattr(exponents, "items") or len(exponents) == 0:
+            raise ValueError("MassActionODELogLike: a Monomial's exponents must be a non-empty mapping {parameter index: exponent}")
+        pairs = []
+        for i, e in exponents.items():
+            if not _is_int(i, 0):
+                raise ValueError("MassActionODELogLike: a Monomial's parameter index must be a non-negative integer (got %r)" % (i,))
+            if not _is_real(e) or e == 0:
+                raise ValueError("MassActionODELogLike: a Monomial's exponent must be a finite, non-zero number (got %r for index %d)" % (e, i))
+            pairs.append((int(i), float(e)))
+        if not _is_real(log10_factor):
+            raise ValueError("MassActionODELogLike: a Monomial's log10_factor must be finite (got %r)" % (log10_factor,))
+        object.__setattr__(self, "exponents", tuple(sorted(pairs)))
+        object.__setattr__(self, "log10_factor", float(log10_factor))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Monomial is immutable")
+
+    __delattr__ = __setattr__
+
+    @property
+    def indices(self):
+        return tuple(i for i, _ in self.exponents)
+
+    def value(self, x):
+        """10.0**(log10_factor + sum e_i x[i]) in numpy (the solvers' own arithmetic: csrc/dz_ode.h), for the rows of x"""
+        x = np.asarray(x, dtype=float)
+        s = self.log10_factor
+        for i, e in self.exponents:
+            s = s + e * x[..., i]
+        return 10.0 ** s
+
+    def __eq__(self, other):
+        return isinstance(other, Monomial) and self.exponents == other.exponents and self.log10_factor == other.log10_factor
+
+    def __hash__(self):
+        return hash((self.exponents, self.log10_factor))
+
+    def __reduce__(self):
+        return Monomial, (dict(self.exponents), self.log10_factor)
+
+    def __repr__(self):
+        return "Monomial(%r, %r)" % (dict(self.exponents), self.log10_factor)
+
+
+def _checked_constant(v, what, wrong_type=None):
+    """A rate constant or a Hill constant as the generators take it: a parameter index (int), a float or a Monomial.  wrong_type: the
+    caller's own words for a value that is none of them."""
+    if isinstance(v, Monomial):
+        return v
+    if _is_int(v):
+        if v < 0:
+            raise ValueError("MassActionODELogLike: %s: parameter index %d is negative" % (what, v))
+        return int(v)
+    if isinstance(v, (float, np.floating)):
+        return float(v)
+    raise ValueError("MassActionODELogLike: " + (wrong_type or "%s is a parameter index (int), a fixed constant (float) or a Monomial (got %r)" % (what, v)))
+
+
+class Hill:
+    """A saturating factor of one species in a RateLaw: y^n / (K^n + y^n) for kind "activation", K^n / (K^n + y^n) for "repression".
+    species: the species' index; K: a parameter index (10**x[i] under rate_scale "log10", x[i] under "linear"), a finite float > 0 or a
+    Monomial; n: an integer 1..8 (ODE_MAX_HILL_EXPONENT; powers are repeated products).  An immutable value."""
+    __slots__ = ("species", "K", "n", "kind")
+
+    def __init__(self, species, K, n=1, kind="activation"):
+        if not _is_int(species, 0):
+            raise ValueError("MassActionODELogLike: a Hill factor's species must be a non-negative integer (got %r)" % (species,))
+        K = _checked_constant(K, "a Hill factor's K")
+        if isinstance(K, float) and not (np.isfinite(K) and K > 0):
+            raise ValueError("MassActionODELogLike: a Hill factor's fixed K must be finite and > 0 (got %r)" % (K,))
+        if not _is_int(n, 1, ODE_MAX_HILL_EXPONENT):
+            raise ValueError("MassActionODELogLike: a Hill factor's n must be an integer 1..%d (got %r)" % (ODE_MAX_HILL_EXPONENT, n))
+        if kind not in ("activation", "repression"):
+            raise ValueError('MassActionODELogLike: a Hill factor\'s kind must be "activation" or "repression" (got %r)' % (kind,))
+        for name, v in zip(self.__slots__, (int(species), K, int(n), kind)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Hill factor is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a Hill factor is immutable")
+
+    def _key(self):
+        return (self.species, type(self.K).__name__, self.K, self.n, self.kind)
+
+    def __eq__(self, other):
+        return isinstance(other, Hill) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return Hill, (self.species, self.K, self.n, self.kind)
+
+    def __repr__(self):
+        return "Hill(%r, %r, %r, %r)" % (self.species, self.K, self.n, self.kind)
+
+
+class RateLaw:
+    """A reaction's rate beyond mass action, where its third element stands: v = k * prod_s y_s^order_s * prod_m h_m(y).
+    rate: what the third element may be without it (a parameter index, a float, a Monomial); factors: at most 4 (ODE_MAX_RATE_FACTORS)
+    Hill objects, multiplied in the order given; order: None -- the kinetic orders are the reactants' coefficients -- or a mapping
+    {species: non-negative integer} that replaces them (kinetics apart from stoichiometry; {}: no mass-action factor).  An immutable
+    value: `factors` is a tuple, `order` None or the tuple of (species, order) pairs in ascending species, zeros dropped."""
+    __slots__ = ("rate", "factors", "order")
+
+    def __init__(self, rate, factors=(), order=None):
+        if isinstance(rate, RateLaw):
+            raise ValueError("MassActionODELogLike: a RateLaw's rate is a parameter index, a float or a Monomial, not another RateLaw")
+        rate = _checked_constant(rate, "a RateLaw's rate")
+        if isinstance(rate, float) and not np.isfinite(rate):
+            raise ValueError("MassActionODELogLike: a RateLaw's fixed rate constant must be finite (got %r)" % (rate,))
+        try:
+            factors = tuple(factors)
+        except TypeError:
+            factors = (factors,)
+        if not all(isinstance(f, Hill) for f in factors):
+            raise ValueError("MassActionODELogLike: a RateLaw's factors must be Hill objects (got %r)" % (factors,))
+        if len(factors) > ODE_MAX_RATE_FACTORS:
+            raise ValueError("MassActionODELogLike: a RateLaw has at most %d factors (got %d)" % (ODE_MAX_RATE_FACTORS, len(factors)))
+        if order is not None:
+            if not hasattr(order, "items"):
+                raise ValueError("MassActionODELogLike: a RateLaw's order must be None or a mapping {species: order} (got %r)" % (order,))
+            pairs = []
+            for s, c in order.items():
+                if not _is_int(s, 0):
+                    raise ValueError("MassActionODELogLike: a RateLaw's order names species %r (a non-negative integer)" % (s,))
+                if not _is_int(c, 0):
+                    raise ValueError("MassActionODELogLike: a RateLaw's kinetic orders must be non-negative integers (got %r for species %d)" % (c, s))
+                if c:
+                    pairs.append((int(s), int(c)))
+            order = tuple(sorted(pairs))
+        for name, v in zip(self.__slots__, (rate, factors, order)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a RateLaw is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a RateLaw is immutable")
+
+    def _key(self):
+        return (type(self.rate).__name__, self.rate, self.factors, self.order)
+
+    def __eq__(self, other):
+        return isinstance(other, RateLaw) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return RateLaw, (self.rate, self.factors, None if self.order is None else dict(self.order))
+
+    def __repr__(self):
+        return "RateLaw(%r, %r, %r)" % (self.rate, list(self.factors), None if self.order is None else dict(self.order))

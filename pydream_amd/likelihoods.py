@@ -6,6 +6,13 @@ evaluation happens inside the HIP kernels instead of on the host.
 """
 import numpy as np
 
+from . import _kernel_cache, _ode_source      # noqa: F401
+from ._kernel_cache import _build_cached, _compiler_version, compile_device_kernel, csrc_dir, kernel_cache_dir      # noqa: F401
+from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate_indices, _slot_indices
+from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
+                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS, Hill, Monomial, RateLaw,
+                          _checked_constant, _is_int, _is_real)
+
 
 class MVNormalLogLike:
     """log_F - 1/2 (x-mu)^T P (x-mu)  (pydream/examples/ndim_gaussian/dream_ex_ndim_gaussian.py:49-52).
@@ -58,116 +65,6 @@ class GaussianMixtureLogLike:
 
 KERNEL_SIGNATURE = 'extern "C" __global__ void NAME(const double* X, long long n, int d, int ld, double* like, const void* data)'
 
-
-_COMPILER_VERSION = {}
-_FALLBACK_DIR = []
-
-
-def _hipcc():
-    import os
-    return next((c for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), "hipcc")
-
-
-def _compiler_version(cc):
-    """`cc --version` (memoised per process), part of the cache key: an object is only as current as the compiler that made it."""
-    import subprocess
-    if cc not in _COMPILER_VERSION:
-        try:
-            _COMPILER_VERSION[cc] = subprocess.run([cc, "--version"], capture_output=True, text=True).stdout
-        except OSError:
-            _COMPILER_VERSION[cc] = ""
-    return _COMPILER_VERSION[cc]
-
-
-def _private_dir(path):
-    """path is a directory (not a link) owned by this user and writable by nobody else."""
-    import os
-    import stat
-    try:
-        st = os.lstat(path)
-    except OSError:
-        return False
-    return stat.S_ISDIR(st.st_mode) and st.st_uid == os.getuid() and not (st.st_mode & (stat.S_IWGRP | stat.S_IWOTH))
-
-
-def kernel_cache_dir():
-    """Where compiled likelihood objects are kept: $DREAMZS_KERNEL_CACHE (default ~/.cache/dreamzs_kernels) if it can be written, else
-    <tmpdir>/dreamzs_kernels_<uid>.  The last one has a predictable name in a shared directory, so it is created with mode 0700 and
-    used only while it is a directory owned by this user and not group- or world-writable; otherwise a fresh private directory
-    (mkdtemp) serves this process.  Objects found in the cache are loaded and run, so nobody else may be able to write there."""
-    import os
-    import tempfile
-    cdir = os.environ.get("DREAMZS_KERNEL_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "dreamzs_kernels")
-    try:
-        os.makedirs(cdir, exist_ok=True)
-        if not os.access(cdir, os.W_OK):
-            raise OSError("not writable")
-        return cdir
-    except OSError:
-        pass
-    cdir = os.path.join(tempfile.gettempdir(), "dreamzs_kernels_%d" % os.getuid())
-    try:
-        os.mkdir(cdir, 0o700)
-    except OSError:
-        pass
-    if _private_dir(cdir):
-        return cdir
-    if not _FALLBACK_DIR or not _private_dir(_FALLBACK_DIR[0]):
-        _FALLBACK_DIR[:] = [tempfile.mkdtemp(prefix="dreamzs_kernels_")]
-    return _FALLBACK_DIR[0]
-
-
-def _build_cached(text, suffix, src_ext, cmd_for, what, cached_key_parts, out_path=None):
-    # what: (the compiler's name, what it was building) for the error messages
-    """Compile `text` with the command cmd_for(src, out) into out_path or, without one, into the kernel cache under a key of
-    (cached_key_parts, text).  Built beside the target under a name unique to the process and thread, then renamed into place:
-    concurrent builders never see half a file."""
-    import hashlib
-    import os
-    import subprocess
-    import threading
-    cached = out_path is None
-    if cached:
-        key = hashlib.sha256(("\0".join(cached_key_parts) + "\0" + text).encode()).hexdigest()[:32]
-        out_path = os.path.join(kernel_cache_dir(), key + suffix)
-        if os.path.exists(out_path) and os.path.getsize(out_path) > 0:
-            return out_path
-    tmp = "%s.%d.%d.tmp" % (out_path, os.getpid(), threading.get_ident())
-    src = tmp + src_ext
-    with open(src, "w") as f:
-        f.write(text)
-    cmd = cmd_for(src, tmp)
-    try:
-        res = subprocess.run(cmd, capture_output=True, text=True)
-    except OSError as ex:          # (no compiler on this machine: say so -- a code object built elsewhere can be given by path)
-        os.remove(src)
-        raise Exception("%s failed%s: cannot run %r (%s); set HIPCC, or build the code object where ROCm is installed and pass its path" % (what + (cmd[0], ex)))
-    try:
-        os.remove(src) if cached else os.replace(src, out_path + src_ext)
-    except OSError:
-        pass
-    if res.returncode != 0:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        raise Exception("%s failed%s:\n%s" % (what + (res.stderr[-4000:],)))
-    os.replace(tmp, out_path)
-    return out_path
-
-
-def compile_device_kernel(source, out_path=None, extra_flags=(), arch="gfx950"):
-    """HIP source text -> a code object (.hsaco) for DeviceKernelLogLike: `hipcc --offload-arch=<arch> --genco` (arch: the engine is built
-    for gfx950, the MI355X; the argument is there so that an error names what was asked for).
-    -ffp-contract=off is on by default so that a density written with + and * rounds like the same expression in numpy (a host
-    likelihood and its device twin then make the same accept / reject decisions bit for bit); pass extra_flags=("-ffp-contract=fast",)
-    to let the compiler fuse.  Without out_path the code object is CACHED under a key of (source, flags, arch, `hipcc --version`) in
-    kernel_cache_dir(): the same source is compiled once, by whichever process or unpickled copy asks first (advisor, round 5: a fresh
-    temporary directory and a fresh hipcc run per call).  Returns the path."""
-    text = source if "hip_runtime.h" in source else "#include <hip/hip_runtime.h>\n" + source
-    flags = ["--offload-arch=%s" % arch, "--genco", "--no-gpu-bundle-output", "-O3", "-std=c++17", "-ffp-contract=off"] + list(extra_flags)
-    hipcc = _hipcc()
-    key = flags + ([_compiler_version(hipcc)] if out_path is None else [])
-    return _build_cached(text, ".hsaco", ".hip", lambda src, out: [hipcc] + flags + ["-o", out, src],
-                         ("hipcc", " for the device likelihood (--offload-arch=%s)" % arch), key, out_path)
 
 
 FUNCTION_SIGNATURE = '__device__ double NAME(const double* x, int d, const void* data, int lane)'
@@ -232,12 +129,25 @@ extern "C" __global__ __launch_bounds__(256) void dz_user_batch(const double* X,
 """
 
 
-def csrc_dir():
-    import os
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+class _UserKernelLogLike:
+    """What the two likelihoods written by the user share: a call on the host goes to the Python twin `host` or, without one, evaluates
+    the point on the device with an engine of the object's own, made on first use."""
+
+    def __call__(self, x):
+        if self.host is not None:
+            return self.host(np.asarray(x, dtype=float))
+        if self._eval_engine is None:
+            from . import _capi
+            self._eval_engine = _capi.Engine(nchains=3, ndim=self.d, history_capacity=8)
+            self._dz_apply(self._eval_engine)
+        return float(self._eval_engine.eval_logp(np.asarray(x, dtype=float).reshape(1, self.d))[1][0])
+
+    def __getstate__(self):                      # (the evaluation engine is a device handle: not part of the object's value)
+        st = dict(self.__dict__); st["_eval_engine"] = None
+        return st
 
 
-class DeviceFunctionLogLike:
+class DeviceFunctionLogLike(_UserKernelLogLike):
     """A user-written HIP DEVICE FUNCTION as the likelihood, evaluated by one wave per point -- and INSIDE the persistent generation kernel:
 
         SRC = '''
@@ -286,21 +196,8 @@ class DeviceFunctionLogLike:
     def _dz_apply(self, engine):
         engine.set_likelihood_module(self.code_object(), "dz_user_batch", 64, self.data, self.always_finite)
 
-    def __call__(self, x):
-        if self.host is not None:
-            return self.host(np.asarray(x, dtype=float))
-        if self._eval_engine is None:
-            from . import _capi
-            self._eval_engine = _capi.Engine(nchains=3, ndim=self.d, history_capacity=8)
-            self._dz_apply(self._eval_engine)
-        return float(self._eval_engine.eval_logp(np.asarray(x, dtype=float).reshape(1, self.d))[1][0])
 
-    def __getstate__(self):
-        st = dict(self.__dict__); st["_eval_engine"] = None
-        return st
-
-
-class DeviceKernelLogLike:
+class DeviceKernelLogLike(_UserKernelLogLike):
     """A user-written HIP kernel as the likelihood -- the batched device callback for ANY model (the reference accepts any callable,
     pydream/model.py:17-32; a Python callable runs through the host callback at ~40 k proposals/s, this runs where the built-in
     densities' kernels run).
@@ -342,553 +239,6 @@ class DeviceKernelLogLike:
     def _dz_apply(self, engine):
         engine.set_likelihood_module(self.code_object(), self.name, self.lanes_per_point, self.data, self.always_finite,
                                      items_per_point=self.items_per_point)
-
-    def __call__(self, x):
-        if self.host is not None:
-            return self.host(np.asarray(x, dtype=float))
-        if self._eval_engine is None:
-            from . import _capi
-            self._eval_engine = _capi.Engine(nchains=3, ndim=self.d, history_capacity=8)
-            self._dz_apply(self._eval_engine)
-        return float(self._eval_engine.eval_logp(np.asarray(x, dtype=float).reshape(1, self.d))[1][0])
-
-    def __getstate__(self):                      # (the evaluation engine is a device handle: not part of the object's value)
-        st = dict(self.__dict__); st["_eval_engine"] = None
-        return st
-
-
-# ---------------------------------------------------------------------------------------------------- mass-action ODE models
-ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
-ODE_GROUP_LIMITS = dict(species=32, reactions=128, observables=16, times=4096, lanes=(16, 32), conditions=64)      # lanes_per_point=16 | 32: species <= lanes
-ODE_WAVE_LIMITS = dict(species=64, reactions=256, observables=16, times=4096, lanes=(64,), conditions=64)            # lanes_per_point=64: 33..64 species
-ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
-ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
-ODE_EQUILIBRATE_MAX_STEPS = 2000    # equilibrate=...: the attempted steps of the phase before the experiment, unless its "max_steps" says otherwise
-ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
-_LOG_2PI_HALF = 0.5 * np.log(2.0 * np.pi)
-
-
-def _hexlit(v):
-    """A C++17 hexadecimal floating literal: the double exactly."""
-    v = float(v)
-    return "(%s)" % v.hex() if np.isfinite(v) else ("(__builtin_huge_val())" if v > 0 else "(-__builtin_huge_val())")
-
-
-class Monomial:
-    """10**(log10_factor + sum_i exponents[i] * x[i]): a product of powers of the sampled constants 10**x[i] times a fixed factor, for
-    MassActionODELogLike -- a reaction's rate constant (kr = KD kf: Monomial({i: 1}, log10(kf)); a rate closed by a thermodynamic cycle,
-    k4 = k1 k2 / k3: Monomial({0: 1, 1: 1, 2: -1})), a sampled start amount, an observable's scale factor, or the argument of a Gaussian
-    constraint.  exponents: a non-empty mapping from parameter index to a finite, non-zero float; log10_factor: finite.  An immutable
-    value: `exponents` is the tuple of (index, exponent) pairs in ascending index, the order in which the device and the host build add
-    them (csrc/dz_ode.h)."""
-    __slots__ = ("exponents", "log10_factor")
-
-    def __init__(self, exponents, log10_factor=0.0):
-        if not hasattr(exponents, "items") or len(exponents) == 0:
-            raise ValueError("MassActionODELogLike: a Monomial's exponents must be a non-empty mapping {parameter index: exponent}")
-        pairs = []
-        for i, e in exponents.items():
-            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or i < 0:
-                raise ValueError("MassActionODELogLike: a Monomial's parameter index must be a non-negative integer (got %r)" % (i,))
-            if isinstance(e, bool) or not isinstance(e, (int, np.integer, float, np.floating)) or not np.isfinite(e) or e == 0:
-                raise ValueError("MassActionODELogLike: a Monomial's exponent must be a finite, non-zero number (got %r for index %d)" % (e, i))
-            pairs.append((int(i), float(e)))
-        if isinstance(log10_factor, bool) or not isinstance(log10_factor, (int, np.integer, float, np.floating)) or not np.isfinite(log10_factor):
-            raise ValueError("MassActionODELogLike: a Monomial's log10_factor must be finite (got %r)" % (log10_factor,))
-        object.__setattr__(self, "exponents", tuple(sorted(pairs)))
-        object.__setattr__(self, "log10_factor", float(log10_factor))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a Monomial is immutable")
-
-    __delattr__ = __setattr__
-
-    @property
-    def indices(self):
-        return tuple(i for i, _ in self.exponents)
-
-    def value(self, x):
-        """10.0**(log10_factor + sum e_i x[i]) in numpy (the solvers' own arithmetic: csrc/dz_ode.h), for the rows of x"""
-        x = np.asarray(x, dtype=float)
-        s = self.log10_factor
-        for i, e in self.exponents:
-            s = s + e * x[..., i]
-        return 10.0 ** s
-
-    def __eq__(self, other):
-        return isinstance(other, Monomial) and self.exponents == other.exponents and self.log10_factor == other.log10_factor
-
-    def __hash__(self):
-        return hash((self.exponents, self.log10_factor))
-
-    def __reduce__(self):
-        return Monomial, (dict(self.exponents), self.log10_factor)
-
-    def __repr__(self):
-        return "Monomial(%r, %r)" % (dict(self.exponents), self.log10_factor)
-
-
-_INT = (int, np.integer)
-_REAL = (int, np.integer, float, np.floating)
-ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated products
-ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction
-
-
-def _checked_constant(v, what):
-    """A rate constant or a Hill constant as the generators take it: a parameter index (int), a float or a Monomial."""
-    if isinstance(v, Monomial):
-        return v
-    if isinstance(v, bool) or not isinstance(v, _REAL):
-        raise ValueError("MassActionODELogLike: %s is a parameter index (int), a fixed constant (float) or a Monomial (got %r)" % (what, v))
-    if isinstance(v, _INT):
-        if v < 0:
-            raise ValueError("MassActionODELogLike: %s: parameter index %d is negative" % (what, v))
-        return int(v)
-    return float(v)
-
-
-class Hill:
-    """A saturating factor of one species in a RateLaw: y^n / (K^n + y^n) for kind "activation", K^n / (K^n + y^n) for "repression".
-    species: the species' index; K: a parameter index (10**x[i] under rate_scale "log10", x[i] under "linear"), a finite float > 0 or a
-    Monomial; n: an integer 1..8 (ODE_MAX_HILL_EXPONENT; powers are repeated products).  An immutable value."""
-    __slots__ = ("species", "K", "n", "kind")
-
-    def __init__(self, species, K, n=1, kind="activation"):
-        if isinstance(species, bool) or not isinstance(species, _INT) or species < 0:
-            raise ValueError("MassActionODELogLike: a Hill factor's species must be a non-negative integer (got %r)" % (species,))
-        K = _checked_constant(K, "a Hill factor's K")
-        if isinstance(K, float) and not (np.isfinite(K) and K > 0):
-            raise ValueError("MassActionODELogLike: a Hill factor's fixed K must be finite and > 0 (got %r)" % (K,))
-        if isinstance(n, bool) or not isinstance(n, _INT) or not 1 <= n <= ODE_MAX_HILL_EXPONENT:
-            raise ValueError("MassActionODELogLike: a Hill factor's n must be an integer 1..%d (got %r)" % (ODE_MAX_HILL_EXPONENT, n))
-        if kind not in ("activation", "repression"):
-            raise ValueError('MassActionODELogLike: a Hill factor\'s kind must be "activation" or "repression" (got %r)' % (kind,))
-        for name, v in zip(self.__slots__, (int(species), K, int(n), kind)):
-            object.__setattr__(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a Hill factor is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("a Hill factor is immutable")
-
-    def _key(self):
-        return (self.species, type(self.K).__name__, self.K, self.n, self.kind)
-
-    def __eq__(self, other):
-        return isinstance(other, Hill) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __reduce__(self):
-        return Hill, (self.species, self.K, self.n, self.kind)
-
-    def __repr__(self):
-        return "Hill(%r, %r, %r, %r)" % (self.species, self.K, self.n, self.kind)
-
-
-class RateLaw:
-    """A reaction's rate beyond mass action, where its third element stands: v = k * prod_s y_s^order_s * prod_m h_m(y).
-    rate: what the third element may be without it (a parameter index, a float, a Monomial); factors: at most 4 (ODE_MAX_RATE_FACTORS)
-    Hill objects, multiplied in the order given; order: None -- the kinetic orders are the reactants' coefficients -- or a mapping
-    {species: non-negative integer} that replaces them (kinetics apart from stoichiometry; {}: no mass-action factor).  An immutable
-    value: `factors` is a tuple, `order` None or the tuple of (species, order) pairs in ascending species, zeros dropped."""
-    __slots__ = ("rate", "factors", "order")
-
-    def __init__(self, rate, factors=(), order=None):
-        if isinstance(rate, RateLaw):
-            raise ValueError("MassActionODELogLike: a RateLaw's rate is a parameter index, a float or a Monomial, not another RateLaw")
-        rate = _checked_constant(rate, "a RateLaw's rate")
-        if isinstance(rate, float) and not np.isfinite(rate):
-            raise ValueError("MassActionODELogLike: a RateLaw's fixed rate constant must be finite (got %r)" % (rate,))
-        try:
-            factors = tuple(factors)
-        except TypeError:
-            factors = (factors,)
-        if not all(isinstance(f, Hill) for f in factors):
-            raise ValueError("MassActionODELogLike: a RateLaw's factors must be Hill objects (got %r)" % (factors,))
-        if len(factors) > ODE_MAX_RATE_FACTORS:
-            raise ValueError("MassActionODELogLike: a RateLaw has at most %d factors (got %d)" % (ODE_MAX_RATE_FACTORS, len(factors)))
-        if order is not None:
-            if not hasattr(order, "items"):
-                raise ValueError("MassActionODELogLike: a RateLaw's order must be None or a mapping {species: order} (got %r)" % (order,))
-            pairs = []
-            for s, c in order.items():
-                if isinstance(s, bool) or not isinstance(s, _INT) or s < 0:
-                    raise ValueError("MassActionODELogLike: a RateLaw's order names species %r (a non-negative integer)" % (s,))
-                if isinstance(c, bool) or not isinstance(c, _INT) or c < 0:
-                    raise ValueError("MassActionODELogLike: a RateLaw's kinetic orders must be non-negative integers (got %r for species %d)" % (c, s))
-                if c:
-                    pairs.append((int(s), int(c)))
-            order = tuple(sorted(pairs))
-        for name, v in zip(self.__slots__, (rate, factors, order)):
-            object.__setattr__(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a RateLaw is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("a RateLaw is immutable")
-
-    def _key(self):
-        return (type(self.rate).__name__, self.rate, self.factors, self.order)
-
-    def __eq__(self, other):
-        return isinstance(other, RateLaw) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __reduce__(self):
-        return RateLaw, (self.rate, self.factors, None if self.order is None else dict(self.order))
-
-    def __repr__(self):
-        return "RateLaw(%r, %r, %r)" % (self.rate, list(self.factors), None if self.order is None else dict(self.order))
-
-
-def _rate(rate):
-    """A reaction's rate constant: the third element itself, or a RateLaw's rate."""
-    return rate.rate if isinstance(rate, RateLaw) else rate
-
-
-def _orders(reaction):
-    """A reaction's kinetic orders {species: order}: the reactants' coefficients unless a RateLaw's order replaces them."""
-    law = reaction[2]
-    return dict(law.order) if isinstance(law, RateLaw) and law.order is not None else reaction[0]
-
-
-def _factors(reaction):
-    return reaction[2].factors if isinstance(reaction[2], RateLaw) else ()
-
-
-def _kinetic_species(reaction):
-    """The species a reaction's rate depends on, ascending: those with a kinetic order and those of its Hill factors."""
-    return sorted(set(_orders(reaction)) | {f.species for f in _factors(reaction)})
-
-
-def _hill_slots(reactions):
-    """The distinct (K, n) pairs of the network's Hill factors, in the order of their first use: one slot each (csrc/dz_ode.h)."""
-    slots = []
-    for rx in reactions:
-        for f in _factors(rx):
-            if not any(type(K) is type(f.K) and K == f.K and n == f.n for K, n in slots):
-                slots.append((f.K, f.n))
-    return slots
-
-
-def _slot_of(slots, f):
-    return next(m for m, (K, n) in enumerate(slots) if type(K) is type(f.K) and K == f.K and n == f.n)
-
-
-def _slot_indices(slots):
-    """The parameter indices the slots' K read, bare or inside a monomial, ascending."""
-    return sorted({K for K, _ in slots if isinstance(K, _INT)} | {i for K, _ in slots if isinstance(K, Monomial) for i in K.indices})
-
-
-def _slot_code(K, log10):
-    """(the C++ expression of a slot's K, the parameter indices it reads)"""
-    if isinstance(K, Monomial):
-        kv, idx = _mono_value(K), K.indices
-    elif isinstance(K, _INT):
-        kv, idx = ("dzode::dexp(x[%d] * 2.302585092994046)" % K) if log10 else "x[%d]" % K, (K,)
-    else:
-        kv, idx = _hexlit(K), ()
-    return kv, idx
-
-
-def _hill_value(f, kn):
-    """A Hill factor at y: yn the repeated product of y, den = Kn + yn, yn / den (activation) or Kn / den (repression).  kn: Kn's name."""
-    yn = " * ".join(["y[%d]" % f.species] * f.n)
-    return "((%s) / (%s + %s))" % (yn if f.kind == "activation" else kn, kn, yn)
-
-
-def _hill_slope(f, kn):
-    """Its derivative: num = ((n * Kn) * y) * y ... (n - 1 factors of y, left to right; n = 1: Kn itself), den = Kn + yn,
-    +-num / (den * den): the sign is applied to the quotient."""
-    yn = " * ".join(["y[%d]" % f.species] * f.n)
-    num = " * ".join((["%d.0" % f.n] if f.n > 1 else []) + [kn] + ["y[%d]" % f.species] * (f.n - 1))
-    return "(%s(%s) / ((%s + %s) * (%s + %s)))" % ("" if f.kind == "activation" else "-", num, kn, yn, kn, yn)
-
-
-def _rate_product(kname, reaction, slotname):
-    """v = k * prod y^order (ascending species) * prod h_m (in the order given), left to right."""
-    return _product([kname] + _rate_factors(_orders(reaction)) + [_hill_value(f, slotname(f)) for f in _factors(reaction)])
-
-
-def _rate_slope(kname, reaction, q, slotname):
-    """dv / dy_q: the product rule's sum in the order of the product -- the mass-action term (q has a kinetic order), then one term per
-    Hill factor on q, each the product v with that one factor replaced by its derivative.  A reaction without factors: the one product
-    it always was."""
-    order, hills = _orders(reaction), _factors(reaction)
-    values = [_hill_value(f, slotname(f)) for f in hills]
-    terms = []
-    if q in order:
-        c = order[q]
-        terms.append(_product([kname] + (["%d.0" % c] if c > 1 else []) + _rate_factors(order, skip=q) + values))
-    for m, f in enumerate(hills):
-        if f.species == q:
-            terms.append(_product([kname] + _rate_factors(order) + values[:m] + [_hill_slope(f, slotname(f))] + values[m + 1:]))
-    return terms[0] if len(terms) == 1 else " + ".join("(%s)" % t for t in terms)
-
-
-def _mono_value(m):
-    """The C++ expression of a monomial's value: the sum in ascending index, an exponent of +-1 as a plain add or subtract."""
-    out = _hexlit(m.log10_factor)
-    for i, e in m.exponents:
-        out += " + x[%d]" % i if e == 1.0 else " - x[%d]" % i if e == -1.0 else " + %s * x[%d]" % (_hexlit(e), i)
-    return "dzode::dexp((%s) * 2.302585092994046)" % out
-
-
-def _rate_indices(reactions):
-    """The parameter indices the rate constants read, bare or inside a monomial, ascending: those whose x is tested for finiteness."""
-    rates = [_rate(r) for _, _, r in reactions]
-    return sorted({r for r in rates if isinstance(r, _INT)} | {i for r in rates if isinstance(r, Monomial) for i in r.indices})
-
-
-def _slot_lines(slots, log10, first):
-    """The one-lane rates()' statements for the Hill slots, k[first + m] = Kn, and their liveness tests (csrc/dz_ode.h, RATE LAWS)."""
-    L, tests = [], ["dzode::finite(x[%d])" % i for i in _slot_indices(slots)]
-    for m, (K, n) in enumerate(slots):
-        L.append("        const double K%d = %s;" % (m, _slot_code(K, log10)[0]))
-        L.append("        k[%d] = %s;" % (first + m, " * ".join(["K%d" % m] * n)))
-        tests += ["dzode::finite(K%d)" % m, "dzode::finite(k[%d])" % (first + m), "k[%d] > 0.0" % (first + m)]
-    return L, tests
-
-
-def _monomial_members(mono):
-    """The members of a generated network that has monomials (csrc/dz_ode.h's head), for the one-lane and the lane-group source alike.
-    mono: dict(y0={species: Monomial}, scale=[float | Monomial] or None, constraints=[(Monomial, loc, sd)])."""
-    y0, scale, cons = mono["y0"], mono["scale"] or [], mono["constraints"]
-    outside = [m for _, m in sorted(y0.items())] + [f for f in scale if isinstance(f, Monomial)] + [m for m, _, _ in cons]
-    tests = ["dzode::finite(x[%d])" % i for i in sorted({i for m in outside for i in m.indices})] + ["dzode::finite(%s)" % _mono_value(m) for m in outside]
-    L = ["    static constexpr bool MONOMIALS = true;", "    DZO_HD static bool live(const double* x)", "    {",
-         "        return %s;" % (" && ".join(tests) or "true"), "    }",
-         "    DZO_HD static double y0_row(int r, const double* x, double b)", "    {"]
-    if y0:
-        L += ["        const double m%d = %s;" % (s, _mono_value(m)) for s, m in sorted(y0.items())]
-        sel = "0.0"
-        for s in sorted(y0, reverse=True):
-            sel = "r == %d ? m%d : %s" % (s, s, sel)
-        L += ["        const double m = %s;" % sel, "        return b != b ? m : b;"]
-    else:
-        L.append("        return b;")
-    L += ["    }", "    DZO_HD static void scale(const double* x, double* o)", "    {"]
-    L += ["        o[%d] = %s * o[%d];" % (q, _mono_value(f) if isinstance(f, Monomial) else _hexlit(f), q) for q, f in enumerate(scale) if f != 1.0]
-    L.append("    }")
-    if cons:
-        G0 = float(sum(-np.log(sd) - _LOG_2PI_HALF for _, _, sd in cons))
-        L += ["    DZO_HD static double constraints(const double* x)", "    {", "        double acc = 0.0;"]
-        L += ["        { const double r = (%s - %s) / %s; acc = acc - 0.5 * r * r; }" % (_mono_value(m), _hexlit(loc), _hexlit(sd)) for m, loc, sd in cons]
-        L += ["        return %s + acc;" % _hexlit(G0), "    }"]
-    return L
-
-
-def _stoichiometry(S, reactions):
-    N = np.zeros((S, len(reactions)), dtype=np.int64)
-    for r, (reac, prod, _) in enumerate(reactions):
-        for s, c in reac.items():
-            N[s, r] -= c
-        for s, c in prod.items():
-            N[s, r] += c
-    return N
-
-
-def _product(factors):
-    return " * ".join(factors) if factors else "1.0"
-
-
-def _rate_factors(reac, skip=None):
-    out = []
-    for s, c in sorted(reac.items()):
-        out += ["y[%d]" % s] * (c - (1 if s == skip else 0))
-    return out
-
-
-def _combine(terms):                        # [(integer coefficient, expression)] -> a sum in this order
-    out = ""
-    for c, e in terms:
-        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
-        out += ("-" if c < 0 else "") + t if not out else (" - " if c < 0 else " + ") + t
-    return out or "0.0"
-
-
-def _obs_lines(S, observables):
-    L = []
-    for o, row in enumerate(observables):
-        terms = ["y[%d]" % s if row[s] == 1.0 else "%s * y[%d]" % (_hexlit(row[s]), s) for s in range(S) if row[s] != 0.0]
-        L.append("        o[%d] = %s;" % (o, " + ".join(terms) if terms else "0.0"))
-    return L
-
-
-def _net_source(header, S, R, O, body, observables, entries, events=0, equilibrate=False):
-    """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
-    closing brace of the last one), the observables and the entry macro.  events: the largest event count over the object's
-    experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  equilibrate: some experiment equilibrates first; the member
-    EQUILIBRATE only then."""
-    L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (S, R, O)]
-    L += ["    static constexpr int EVENTS = %d;" % events] if events else []
-    L += ["    static constexpr bool EQUILIBRATE = true;"] if equilibrate else []
-    L += body
-    L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(S, observables) + ["    }", "};", entries, ""]
-    return '#include "%s"\n' % header + "\n".join(L)
-
-
-_ODE_WHOLE_SUMS = 16        # up to this many reactions the one-lane source names every rate and writes each f[s] and J[i] as one sum
-
-
-def _ode_long_source(S, reactions, observables, log10, entries="DZODE_ENTRIES(Net)", mono=None, events=0, equilibrate=False):
-    """The one-lane source for more than _ODE_WHOLE_SUMS reactions.  Every f[s] and J[i] is the same sum in the same (ascending reaction)
-    order as in the short form, but built up reaction by reaction, so one rate is live at a time and not all R; DZODE_FENCE between the
-    reactions keeps the compiler from starting them all at once (see csrc/dz_ode.h).  k holds one rate constant per parameter that is
-    used, not one per reaction, and a fixed rate constant is a literal where it is used: what stays in registers through the
-    integration is the number of distinct parameters."""
-    R, O = len(reactions), len(observables)
-    N = _stoichiometry(S, reactions)
-    rates = [_rate(rate) for _, _, rate in reactions]
-    used = sorted({rate for rate in rates if isinstance(rate, _INT)})
-    for rate in rates:                          # (then a slot per distinct monomial, in the order of their first reactions)
-        if isinstance(rate, Monomial) and rate not in used:
-            used.append(rate)
-    kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for rate in rates]
-    slots = _hill_slots(reactions)              # (then the Hill slots: k[len(used) + m] = Kn)
-    slotname = lambda f: "k[%d]" % (len(used) + _slot_of(slots, f))      # noqa: E731
-    slot_lines, slot_tests = _slot_lines(slots, log10, len(used))
-
-    def add(target, started, c, e):
-        t = e if abs(c) == 1 else "%d.0 * %s" % (abs(c), e)
-        if target in started:
-            return "        %s = %s %s %s;" % (target, target, "-" if c < 0 else "+", t)
-        started.add(target)
-        return "        %s = %s%s;" % (target, "-" if c < 0 else "", t)
-
-    L = ["    static constexpr int SLOTS = %d;" % len(slots)] if slots else []
-    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
-    L += ["        k[%d] = %s;" % (i, _mono_value(p) if isinstance(p, Monomial) else ("dzode::dexp(x[%d] * 2.302585092994046)" % p) if log10 else "x[%d]" % p)
-          for i, p in enumerate(used)]
-    L += slot_lines
-    L.append("        return %s;" % (" && ".join(["dzode::finite(x[%d])" % p for p in _rate_indices(reactions)] + ["dzode::finite(k[%d])" % i for i in range(len(used))]
-                                                 + slot_tests) or "true"))
-    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
-    started = set()
-    for r, reaction in enumerate(reactions):
-        rows = [s for s in range(S) if N[s, r] != 0]
-        if not rows:
-            continue
-        L.append("        const double v%d = %s;" % (r, _rate_product(kname[r], reaction, slotname)))
-        L += [add("f[%d]" % s, started, int(N[s, r]), "v%d" % r) for s in rows]
-        L.append("        " + " ".join("DZODE_FENCE(f[%d]);" % s for s in rows))
-    L += ["        f[%d] = 0.0;" % s for s in range(S) if "f[%d]" % s not in started]
-    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
-    started = set()
-    for r, reaction in enumerate(reactions):            # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: _rate_slope)
-        rows = [s for s in range(S) if N[s, r] != 0]
-        for q in _kinetic_species(reaction):
-            if not rows:
-                continue
-            L.append("        const double d%d_%d = %s;" % (r, q, _rate_slope(kname[r], reaction, q, slotname)))
-            L += [add("J[%d]" % (s * S + q), started, int(N[s, r]), "d%d_%d" % (r, q)) for s in rows]
-            L.append("        " + " ".join("DZODE_FENCE(J[%d]);" % (s * S + q) for s in rows))
-    L += ["        J[%d] = 0.0;" % i for i in range(S * S) if "J[%d]" % i not in started]
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events, equilibrate)
-
-
-def _ode_source(S, reactions, observables, log10, items=False, mono=None, events=0, equilibrate=False):
-    """The generated network struct (see csrc/dz_ode.h; the scaffolding around it: _net_source): rate constants, right-hand side, analytic Jacobian and observables as
-    straight-line code with constant indices; powers as repeated products.  items: the entry points for several conditions per point."""
-    R, O = len(reactions), len(observables)
-    entries = "DZODE_ITEM_ENTRIES(Net)" if items else "DZODE_ENTRIES(Net)"
-    if R > _ODE_WHOLE_SUMS:
-        return _ode_long_source(S, reactions, observables, log10, entries, mono, events, equilibrate)
-    N = _stoichiometry(S, reactions)
-    slots = _hill_slots(reactions)              # (the Hill slots behind the rate constants: k[R + m] = Kn)
-    slotname = lambda f: "k[%d]" % (R + _slot_of(slots, f))      # noqa: E731
-    slot_lines, slot_tests = _slot_lines(slots, log10, R)
-    L = ["    static constexpr int SLOTS = %d;" % len(slots)] if slots else []
-    L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
-    for r, rate in enumerate(_rate(rate) for _, _, rate in reactions):
-        if isinstance(rate, _INT):
-            L.append("        k[%d] = %s;" % (r, ("dzode::dexp(x[%d] * 2.302585092994046)" % rate) if log10 else "x[%d]" % rate))
-        elif isinstance(rate, Monomial):
-            L.append("        k[%d] = %s;" % (r, _mono_value(rate)))
-        else:
-            L.append("        k[%d] = %s;" % (r, _hexlit(rate)))
-    used = _rate_indices(reactions)             # (10**-inf is a finite 0: test x itself)
-    L += slot_lines
-    L.append("        return %s;" % " && ".join(["dzode::finite(x[%d])" % i for i in used] + ["dzode::finite(k[%d])" % r for r in range(R)] + slot_tests))
-    L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
-    for r, reaction in enumerate(reactions):
-        L.append("        const double v%d = %s;" % (r, _rate_product("k[%d]" % r, reaction, slotname)))
-    for s in range(S):
-        L.append("        f[%d] = %s;" % (s, _combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
-    L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
-    for r, reaction in enumerate(reactions):            # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: _rate_slope)
-        for q in _kinetic_species(reaction):
-            L.append("        const double d%d_%d = %s;" % (r, q, _rate_slope("k[%d]" % r, reaction, q, slotname)))
-    kinetic = [_kinetic_species(reaction) for reaction in reactions]
-    for s in range(S):
-        for q in range(S):
-            terms = [(int(N[s, r]), "d%d_%d" % (r, q)) for r in range(R) if N[s, r] != 0 and q in kinetic[r]]
-            L.append("        J[%d] = %s;" % (s * S + q, _combine(terms)))
-    return _net_source("dz_ode.h", S, R, O, L + ["    }"] + (_monomial_members(mono) if mono else []), observables, entries, events, equilibrate)
-
-
-def _ode_group_source(S, reactions, observables, log10, lanes, items=False, mono=None, events=0, equilibrate=False):
-    """The generated network struct for the lane-group solver and, with lanes=64, the wave-per-point one (csrc/dz_ode_group.h).  Lane r (or the host build's loop iteration r) gets
-    its own f[r] and J[r][q] WITHOUT a branch on r: every reaction's rate is evaluated by every lane and multiplied by that lane's
-    stoichiometric coefficient, a select over constants (0 for a species the reaction does not touch), so the lanes of a wave never
-    diverge inside the right-hand side.  Every f[r] and J[r][q] is the sum over the reactions (for J: those with q among the reactants)
-    in ascending reaction index of coefficient(r) * (k[j] * (nu) * y...) -- written here once, compiled for both sides."""
-    R, O = len(reactions), len(observables)
-    N = _stoichiometry(S, reactions)
-
-    def coefficient(j):                     # N[r][j] as a function of r
-        out = "0.0"
-        for s in reversed([s for s in range(S) if N[s, j] != 0]):
-            out = "r == %d ? %d.0 : %s" % (s, N[s, j], out)
-        return "(%s)" % out
-
-    def weighted_sum(terms, indent):        # [(j, expression)] -> statements that leave the sum in v
-        if not terms:
-            return [indent + "return 0.0;"]
-        out = [indent + "int z = 0;", indent + "double v = %s * (%s);" % (coefficient(terms[0][0]), terms[0][1])]
-        for t, (j, e) in enumerate(terms[1:], 1):
-            if t % 4 == 0:                  # (a long sum in groups of four terms: see DZODE_SUM_FENCE in csrc/dz_ode_group.h)
-                out.append(indent + "DZODE_SUM_FENCE(v, r, z);")
-            out.append(indent + "v = v + %s * (%s);" % (coefficient(j), e))
-        return out + [indent + "return v;"]
-
-    rates = [_rate(rate) for _, _, rate in reactions]
-    slots = _hill_slots(reactions)              # (the Hill slots behind the rate constants: k[R + m] = Kn, by lane (R + m) % L once per point)
-    slotname = lambda f: "k[z + %d]" % (R + _slot_of(slots, f))      # noqa: E731
-    L = ["    static constexpr bool LOG10 = %s;" % ("true" if log10 else "false"),
-         "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %d;" % (j, -2 if isinstance(rate, Monomial) else rate) for j, rate in enumerate(rates) if isinstance(rate, _INT + (Monomial,))]
-    L += ["        default: return -1;", "        }", "    }", "    DZO_HD static double rate_fixed(int j)", "    {", "        switch (j) {"]
-    L += ["        case %d: return %s;" % (j, _hexlit(rate)) for j, rate in enumerate(rates) if not isinstance(rate, _INT + (Monomial,))]
-    L += ["        default: return 0.0;", "        }", "    }"]
-    if slots:
-        L += ["    static constexpr int SLOTS = %d;" % len(slots), "    DZO_HD static double slot(int m, const double* x, bool& good)", "    {", "        switch (m) {"]
-        for m, (K, n) in enumerate(slots):
-            kv, idx = _slot_code(K, log10)
-            L.append("        case %d: { const double K = %s; const double v = %s; good = %s; return v; }"
-                     % (m, kv, " * ".join(["K"] * n), " && ".join(["dzode::finite(x[%d])" % i for i in idx] + ["dzode::finite(K)", "dzode::finite(v)", "v > 0.0"])))
-        L += ["        default: good = false; return 0.0;", "        }", "    }"]
-    if mono:                                             # (rate_index -2: the reaction's own expression, by lane j % L once per point)
-        L += ["    DZO_HD static double rate_mono(int j, const double* x, bool& good)", "    {", "        switch (j) {"]
-        for j, rate in enumerate(rates):
-            if isinstance(rate, Monomial):
-                L.append("        case %d: { const double v = %s; good = %s; return v; }"
-                         % (j, _mono_value(rate), " && ".join(["dzode::finite(x[%d])" % i for i in rate.indices] + ["dzode::finite(v)"])))
-        L += ["        default: good = false; return 0.0;", "        }", "    }"]
-    L += ["    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
-    L += weighted_sum([(j, _rate_product("k[z + %d]" % j, reactions[j], slotname)) for j in range(R) if np.any(N[:, j] != 0)], "        ")
-    L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
-    for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
-        terms = [(j, _rate_slope("k[z + %d]" % j, reactions[j], q, slotname)) for j in range(R) if q in _kinetic_species(reactions[j]) and np.any(N[:, j] != 0)]
-        L += ["        case %d: {" % q] + weighted_sum(terms, "            ") + ["        }"]
-    L += ["        default: return 0.0;", "        }", "    }"] + (_monomial_members(mono) if mono else [])
-    return _net_source("dz_ode_group.h", S, R, O, L, observables, ("DZODE_GROUP_ITEM_ENTRIES(Net, %d)" if items else "DZODE_GROUP_ENTRIES(Net, %d)") % lanes, events, equilibrate)
 
 
 class MassActionODELogLike:
@@ -1028,6 +378,32 @@ class MassActionODELogLike:
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
                  equilibrate=None):
+        self.n_species, self.lanes_per_point, lim = self._checked_shape(n_species, lanes_per_point, len(reactions))
+        if rate_scale not in ("log10", "linear"):
+            raise ValueError('MassActionODELogLike: rate_scale must be "log10" or "linear"')
+        self.rate_scale, self.log10 = rate_scale, rate_scale == "log10"
+        self.reactions = self._checked_reactions(reactions, self.n_species, lim["reactions"])
+        conditions = self._checked_condition_keys(conditions, dict(y0=y0, data=data, sd=sd))
+        self.y0_monomials = {}                  # species -> the Monomial its start amount is, wherever a y0 says so (the same in all)
+        self.y0 = y0 if y0 is None else self._checked_y0(y0, "")
+        self.t, self.t0, self.observables = self._checked_times(t, t0, observables, self.n_species, lim)
+        self.data, self.sd = self._checked_data(data, sd, "") if data is not None and sd is not None else (data, sd)
+        events = self._checked_events(events, "")
+        if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
+            raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
+        self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
+        self.events = events or None            # None, or the checked (time, species, factor, amount) tuples sorted by time
+        self.equilibrate = self._checked_equilibrate(equilibrate, "")       # None, or dict(rtol, atol, horizon, max_step, max_steps), every default filled in
+        # None, or a list of dict(y0, data, sd, events[, equilibrate]): checked, the fallbacks filled in -- every condition as the single
+        # experiment: its own values, else the constructor's (checked above)
+        self.conditions = conditions and [self._checked_condition(cond, "condition %d: " % c, events) for c, cond in enumerate(conditions)]
+        self.scale, self.constraints = self._checked_scale(scale, len(self.observables)), self._checked_constraints(constraints)
+        self.d = self._checked_ndim(ndim)
+        self.path, self._host = path, None
+
+    @staticmethod
+    def _checked_shape(n_species, lanes_per_point, R):
+        """(S, lanes, the limits of that shape) of a network of R reactions"""
         S = int(n_species)
         lanes = int(lanes_per_point)
         if lanes != 1 and lanes not in ODE_GROUP_LIMITS["lanes"] + ODE_WAVE_LIMITS["lanes"]:
@@ -1038,10 +414,14 @@ class MassActionODELogLike:
         if lim is ODE_WAVE_LIMITS and S <= ODE_GROUP_LIMITS["species"]:          # (half the wave would idle)
             raise ValueError("MassActionODELogLike: lanes_per_point=%d is for networks of %d..%d species; use 16 or 32 (got %d species)"
                              % (lanes, ODE_GROUP_LIMITS["species"] + 1, lim["species"], S))
-        if not 1 <= len(reactions) <= lim["reactions"]:
-            raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (lim["reactions"], len(reactions)))
-        if rate_scale not in ("log10", "linear"):
-            raise ValueError('MassActionODELogLike: rate_scale must be "log10" or "linear"')
+        if not 1 <= R <= lim["reactions"]:
+            raise ValueError("MassActionODELogLike: 1..%d reactions are supported (got %d)" % (lim["reactions"], R))
+        return S, lanes, lim
+
+    @staticmethod
+    def _checked_reactions(reactions, S, limit):
+        """The reactions as (reactants, products, rate): {species: coefficient > 0} with plain ints, the rate an int, a float, a Monomial
+        or a RateLaw that says more than its rate."""
         rx = []
         for r, reaction in enumerate(reactions):
             if len(reaction) != 3:
@@ -1049,48 +429,49 @@ class MassActionODELogLike:
             reac, prod, rate = reaction
             for side in (reac, prod):
                 for s, c in dict(side).items():
-                    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < S:
+                    if not _is_int(s, 0, S - 1):
                         raise ValueError("MassActionODELogLike: reaction %d names species %r (0..%d)" % (r, s, S - 1))
-                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
+                    if not _is_int(c, 0):
                         raise ValueError("MassActionODELogLike: reaction %d: stoichiometric coefficients must be non-negative integers (got %r)" % (r, c))
-            if isinstance(rate, bool) or not isinstance(rate, (int, np.integer, float, np.floating, Monomial, RateLaw)):
-                raise ValueError("MassActionODELogLike: reaction %d: the rate is a parameter index (int), a fixed rate constant (float), a Monomial or a RateLaw" % r)
             if isinstance(rate, RateLaw):
                 for s in [s for s, _ in rate.order or ()] + [f.species for f in rate.factors]:
                     if not 0 <= s < S:
                         raise ValueError("MassActionODELogLike: reaction %d: its RateLaw names species %r (0..%d)" % (r, s, S - 1))
                 if not rate.factors and rate.order is None:          # (nothing beyond its rate: the plain reaction, source and bits)
                     rate = rate.rate
-            elif isinstance(rate, Monomial):
-                pass
-            elif isinstance(rate, (int, np.integer)):
-                if rate < 0:
-                    raise ValueError("MassActionODELogLike: reaction %d: parameter index %d is negative" % (r, rate))
-                rate = int(rate)
-            elif not np.isfinite(rate):
-                raise ValueError("MassActionODELogLike: reaction %d: the fixed rate constant must be finite" % r)
             else:
-                rate = float(rate)
+                rate = _checked_constant(rate, "reaction %d" % r, "reaction %d: the rate is a parameter index (int), a fixed rate constant (float), "
+                                                                    "a Monomial or a RateLaw" % r)
+                if isinstance(rate, float) and not np.isfinite(rate):
+                    raise ValueError("MassActionODELogLike: reaction %d: the fixed rate constant must be finite" % r)
             rx.append(({int(s): int(c) for s, c in dict(reac).items() if c}, {int(s): int(c) for s, c in dict(prod).items() if c}, rate))
         slots = _hill_slots(rx)
-        if len(rx) + len(slots) > lim["reactions"]:
-            raise ValueError("MassActionODELogLike: reactions plus distinct Hill (K, n) pairs must stay within %d (got %d + %d)" % (lim["reactions"], len(rx), len(slots)))
-        idx = _rate_indices(rx) + _slot_indices(slots)
-        if conditions is not None:
-            conditions = list(conditions)
-            if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
-                raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
-            for c, cond in enumerate(conditions):
-                if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate"}:
-                    raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate" (each optional)' % c)
-                for key, top in (("y0", y0), ("data", data), ("sd", sd)):
-                    if cond.get(key) is None and top is None:
-                        raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
-        elif y0 is None or data is None or sd is None:
-            raise ValueError("MassActionODELogLike: y0, data and sd may be None only when every one of the conditions gives its own")
-        y0m = {}                                 # species -> the Monomial its start amount is, wherever a y0 says so (the same in all)
-        if y0 is not None:
-            y0 = self._checked_y0(y0, S, "", y0m)
+        if len(rx) + len(slots) > limit:
+            raise ValueError("MassActionODELogLike: reactions plus distinct Hill (K, n) pairs must stay within %d (got %d + %d)" % (limit, len(rx), len(slots)))
+        return rx
+
+    @staticmethod
+    def _checked_condition_keys(conditions, own):
+        """None, or the conditions as a list of mappings with known keys -- every one of y0, data and sd given by the condition or by the
+        constructor (own)."""
+        if conditions is None:
+            if any(v is None for v in own.values()):
+                raise ValueError("MassActionODELogLike: y0, data and sd may be None only when every one of the conditions gives its own")
+            return None
+        conditions = list(conditions)
+        if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
+            raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
+        for c, cond in enumerate(conditions):
+            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate"}:
+                raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate" (each optional)' % c)
+            for key, top in own.items():
+                if cond.get(key) is None and top is None:
+                    raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
+        return conditions
+
+    @staticmethod
+    def _checked_times(t, t0, observables, S, lim):
+        """(the output times, t0, the O x S observables)"""
         t = np.asarray(t, dtype=float).reshape(-1)
         if not 1 <= len(t) <= lim["times"]:
             raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (lim["times"], len(t)))
@@ -1099,32 +480,32 @@ class MassActionODELogLike:
         obs = np.atleast_2d(np.asarray(observables, dtype=float))
         if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= lim["observables"] or not np.all(np.isfinite(obs)):
             raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, lim["observables"]))
-        O, T = len(obs), len(t)
-        if data is not None and sd is not None:
-            data, sd = self._checked_data(data, sd, O, T, "")
-        events = self._checked_events(events, S, float(t0), t, "")
-        if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
-            raise ValueError("MassActionODELogLike: rtol and atol must be > 0, max_steps >= 1")
-        span = max(float(t[-1]) - float(t0), 1e-300)
-        equilibrate = self._checked_equilibrate(equilibrate, float(rtol), float(atol), span, "")
-        if conditions is not None:              # every condition as the single experiment: its own values, else the constructor's (checked above)
-            full = []
-            for c, cond in enumerate(conditions):
-                who = "condition %d: " % c
-                cy0 = y0 if cond.get("y0") is None else self._checked_y0(cond["y0"], S, who, y0m)
-                cdata, csd = (data if cond.get("data") is None else cond["data"]), (sd if cond.get("sd") is None else cond["sd"])
-                if cond.get("data") is not None or cond.get("sd") is not None or data is None or sd is None:
-                    cdata, csd = self._checked_data(cdata, csd, O, T, who)
-                cev = events if "events" not in cond or cond["events"] is None else self._checked_events(cond["events"], S, float(t0), t, who)
-                ceq = equilibrate if cond.get("equilibrate") is None else self._checked_equilibrate(cond["equilibrate"], float(rtol), float(atol), span, who)
-                full.append(dict(y0=cy0, data=cdata, sd=csd, events=cev, **({"equilibrate": ceq} if ceq else {})))
-            conditions = full
-        if scale is not None:
-            scale = list(scale) if hasattr(scale, "__len__") or hasattr(scale, "__iter__") else [scale]
-            if len(scale) != O or not all(isinstance(f, Monomial) or (not isinstance(f, bool) and isinstance(f, (int, np.integer, float, np.floating)) and np.isfinite(f))
-                                          for f in scale):
-                raise ValueError("MassActionODELogLike: scale must hold O = %d finite numbers or Monomials" % O)
-            scale = [f if isinstance(f, Monomial) else float(f) for f in scale]
+        return t, float(t0), obs
+
+    def _checked_condition(self, cond, who, events):
+        """A condition as the single experiment: dict(y0, data, sd, events[, equilibrate]); events: the constructor's, checked."""
+        y0 = self.y0 if cond.get("y0") is None else self._checked_y0(cond["y0"], who)
+        data, sd = (self.data if cond.get("data") is None else cond["data"]), (self.sd if cond.get("sd") is None else cond["sd"])
+        if cond.get("data") is not None or cond.get("sd") is not None or self.data is None or self.sd is None:
+            data, sd = self._checked_data(data, sd, who)
+        if cond.get("events") is not None:
+            events = self._checked_events(cond["events"], who)
+        eq = self.equilibrate if cond.get("equilibrate") is None else self._checked_equilibrate(cond["equilibrate"], who)
+        return dict(y0=y0, data=data, sd=sd, events=events, **({"equilibrate": eq} if eq else {}))
+
+    @staticmethod
+    def _checked_scale(scale, O):
+        """None, or the O scale factors: floats and Monomials"""
+        if scale is None:
+            return None
+        scale = list(scale) if hasattr(scale, "__len__") or hasattr(scale, "__iter__") else [scale]
+        if len(scale) != O or not all(isinstance(f, Monomial) or _is_real(f) for f in scale):
+            raise ValueError("MassActionODELogLike: scale must hold O = %d finite numbers or Monomials" % O)
+        return [f if isinstance(f, Monomial) else float(f) for f in scale]
+
+    @staticmethod
+    def _checked_constraints(constraints):
+        """The constraints as a tuple of (Monomial, loc, sd)"""
         cons = []
         for m, entry in enumerate(() if constraints is None else constraints):
             if not isinstance(entry, (tuple, list)) or len(entry) != 3 or not isinstance(entry[0], Monomial):
@@ -1133,30 +514,26 @@ class MassActionODELogLike:
                 loc, csd = float(entry[1]), float(entry[2])
             except (TypeError, ValueError):
                 loc = csd = np.nan
-            if not (np.isfinite(loc) and np.isfinite(csd) and csd > 0):
+            if not (_is_real(loc) and _is_real(csd) and csd > 0):
                 raise ValueError("MassActionODELogLike: constraint %d: loc must be finite and sd finite and > 0" % m)
             cons.append((entry[0], loc, csd))
         if len(cons) > ODE_MAX_CONSTRAINTS:
             raise ValueError("MassActionODELogLike: at most %d constraints are supported (got %d)" % (ODE_MAX_CONSTRAINTS, len(cons)))
-        idx += [i for m in list(y0m.values()) + [f for f in scale or [] if isinstance(f, Monomial)] + [c[0] for c in cons] for i in m.indices]
-        self.d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
-        if idx and max(idx) >= self.d:
-            raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), self.d))
-        self.scale, self.constraints, self.y0_monomials = scale, tuple(cons), y0m
-        self.n_species, self.reactions, self.observables, self.log10 = S, rx, obs, rate_scale == "log10"
-        self.rate_scale, self.y0, self.t, self.t0 = rate_scale, y0, t, float(t0)
-        self.data, self.sd = data, sd
-        self.events = events or None            # None, or the checked (time, species, factor, amount) tuples sorted by time
-        self.equilibrate = equilibrate          # None, or dict(rtol, atol, horizon, max_step, max_steps), every default filled in
-        self.conditions = conditions            # None, or a list of dict(y0, data, sd, events[, equilibrate]): checked, the fallbacks filled in
-        self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
-        self.path, self.lanes_per_point = path, lanes
-        self._host = None
+        return tuple(cons)
 
-    @staticmethod
-    def _checked_y0(y0, S, who, monomials):
-        """The start amounts as S doubles, NaN where the entry is a Monomial (csrc/dz_ode.h: "take the network's monomial"); monomials:
-        species -> Monomial, filled in here -- a species has the same one wherever a y0 gives it one."""
+    def _checked_ndim(self, ndim):
+        """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K or a Monomial reads."""
+        outside = list(self.y0_monomials.values()) + [f for f in self.scale or [] if isinstance(f, Monomial)] + [c[0] for c in self.constraints]
+        idx = _rate_indices(self.reactions) + _slot_indices(_hill_slots(self.reactions)) + _indices_read(outside)
+        d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
+        if idx and max(idx) >= d:
+            raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), d))
+        return d
+
+    def _checked_y0(self, y0, who):
+        """The start amounts as S doubles, NaN where the entry is a Monomial (csrc/dz_ode.h: "take the network's monomial");
+        self.y0_monomials: species -> Monomial, filled in here -- a species has the same one wherever a y0 gives it one."""
+        S, monomials = self.n_species, self.y0_monomials
         entries = list(y0) if isinstance(y0, (list, tuple)) or (isinstance(y0, np.ndarray) and y0.dtype == object) else None
         given = {s: m for s, m in enumerate(entries or ()) if isinstance(m, Monomial)}
         if given:
@@ -1174,10 +551,8 @@ class MassActionODELogLike:
             y0[s] = np.nan
         return y0
 
-    @staticmethod
-    def _checked_equilibrate(eq, rtol, atol, span, who):
+    def _checked_equilibrate(self, eq, who):
         """None (no phase) or the phase's settings, every default filled in: dict(rtol, atol, horizon, max_step, max_steps)."""
-        real = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer, float, np.floating)) and np.isfinite(v)      # noqa: E731
         if eq is None or eq is False:
             return None
         if eq is True:
@@ -1186,25 +561,22 @@ class MassActionODELogLike:
         if not hasattr(eq, "keys") or set(eq.keys()) - set(keys):
             raise ValueError('MassActionODELogLike: %sequilibrate must be None, False, True or a mapping with the keys "rtol", "atol", "horizon", '
                              '"max_step", "max_steps" (each optional; got %r)' % (who, eq))
-        out = dict(rtol=eq.get("rtol", rtol), atol=eq.get("atol", atol), horizon=eq.get("horizon", span))
-        for key in ("rtol", "atol", "horizon"):
-            if not real(out[key]) or not out[key] > 0:
+        out = dict(rtol=eq.get("rtol", self.rtol), atol=eq.get("atol", self.atol), horizon=eq.get("horizon", max(float(self.t[-1]) - self.t0, 1e-300)))
+        for key in ("rtol", "atol", "horizon", "max_step"):
+            if key == "max_step":
+                out[key] = eq.get(key, 1e6 * out["horizon"])
+            if not _is_real(out[key]) or not out[key] > 0:
                 raise ValueError("MassActionODELogLike: %sequilibrate: %s must be finite and > 0 (got %r)" % (who, key, out[key]))
             out[key] = float(out[key])
-        out["max_step"] = eq.get("max_step", 1e6 * out["horizon"])
-        if not real(out["max_step"]) or not out["max_step"] > 0:
-            raise ValueError("MassActionODELogLike: %sequilibrate: max_step must be finite and > 0 (got %r)" % (who, out["max_step"]))
-        out["max_step"] = float(out["max_step"])
         n = eq.get("max_steps", ODE_EQUILIBRATE_MAX_STEPS)
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        if not _is_int(n, 1):
             raise ValueError("MassActionODELogLike: %sequilibrate: max_steps must be an integer >= 1 (got %r)" % (who, n))
         out["max_steps"] = int(n)
         return out
 
-    @staticmethod
-    def _checked_events(events, S, t0, t, who):
+    def _checked_events(self, events, who):
         """The events as a tuple of (time, species, factor, amount), stably sorted by time (events at one time keep the order given)."""
-        real = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer, float, np.floating)) and np.isfinite(v)      # noqa: E731
+        S, t0, t = self.n_species, self.t0, self.t
         if events is None:
             return ()
         try:
@@ -1218,20 +590,20 @@ class MassActionODELogLike:
             if not isinstance(event, (tuple, list)) or len(event) != 4:
                 raise ValueError("MassActionODELogLike: %sevent %d must be (time, species, factor, amount)" % (who, e))
             time, species, factor, amount = event
-            if not real(time) or not t0 <= time <= t[-1]:
+            if not _is_real(time) or not t0 <= time <= t[-1]:
                 raise ValueError("MassActionODELogLike: %sevent %d: the time must be finite and lie in t0 = %r <= time <= t[-1] = %r (got %r)"
                                  % (who, e, t0, float(t[-1]), time))
-            if isinstance(species, bool) or not isinstance(species, (int, np.integer)) or not 0 <= species < S:
+            if not _is_int(species, 0, S - 1):
                 raise ValueError("MassActionODELogLike: %sevent %d names species %r (an int in 0..%d)" % (who, e, species, S - 1))
             if isinstance(factor, Monomial) or isinstance(amount, Monomial):
                 raise ValueError("MassActionODELogLike: %sevent %d: factor and amount are numbers; a Monomial (a sampled dose) is not supported" % (who, e))
-            if not real(factor) or factor < 0 or not real(amount) or amount < 0:
+            if not _is_real(factor) or factor < 0 or not _is_real(amount) or amount < 0:
                 raise ValueError("MassActionODELogLike: %sevent %d: factor and amount must be finite and >= 0 (got %r, %r)" % (who, e, factor, amount))
             out.append((float(time), int(species), float(factor), float(amount)))
         return tuple(sorted(out, key=lambda ev: ev[0]))
 
-    @staticmethod
-    def _checked_data(data, sd, O, T, who):
+    def _checked_data(self, data, sd, who):
+        O, T = len(self.observables), len(self.t)
         data, sd = np.asarray(data, dtype=float), np.asarray(sd, dtype=float)
         try:
             sd = np.broadcast_to(sd, data.shape) if data.shape == (O, T) else sd
@@ -1245,21 +617,26 @@ class MassActionODELogLike:
         return data, np.array(sd)
 
     # ---- the data block (csrc/dz_ode.h) and the generated source
+    def _experiments(self):
+        """The object's experiments as a list of dict(y0, data, sd, events, equilibrate): the conditions, or the single experiment of the
+        constructor's own values.  events () and equilibrate None where there are none (so for an object from before the keywords
+        existed).  What tells the two kinds of object apart is `self.conditions is not None`: only then the data block has its
+        [C, stride] header, the kernels are the item kernels and the host build's results have an axis of conditions."""
+        own = [dict(y0=self.y0, data=self.data, sd=self.sd, events=self.events, equilibrate=self.equilibrate)]
+        return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None)
+                for e in (own if self.conditions is None else self.conditions)]
+
     def _event_lists(self):
-        """Every experiment's events (a condition made before the keyword existed has none)."""
-        if self.conditions is None:
-            return [self.events or ()]
-        return [cond.get("events") or () for cond in self.conditions]
+        """Every experiment's events."""
+        return [e["events"] for e in self._experiments()]
 
     def _max_events(self):
         """Emax, the generated network's EVENTS: the largest event count over the object's experiments (0: a network without events)."""
         return max(len(ev) for ev in self._event_lists())
 
     def _equilibrate_list(self):
-        """Every experiment's equilibration settings, None where it has none (so for an object from before the keyword existed)."""
-        if self.conditions is None:
-            return [self.equilibrate or None]
-        return [cond.get("equilibrate") or None for cond in self.conditions]
+        """Every experiment's equilibration settings, None where it has none."""
+        return [e["equilibrate"] for e in self._experiments()]
 
     def _equilibrates(self):
         """Some experiment of the object equilibrates: the generated network's EQUILIBRATE and the six doubles at each block's end."""
@@ -1283,17 +660,16 @@ class MassActionODELogLike:
 
     def condition_block(self, c=0):
         """One experiment's block: condition c's, or (without conditions) the constructor's own."""
-        if self.conditions is None:
-            return self._experiment_block(self.y0, self.data, self.sd, self.events or (), self.equilibrate)
-        cond = self.conditions[c]
-        return self._experiment_block(cond["y0"], cond["data"], cond["sd"], cond.get("events") or (), cond.get("equilibrate"))
+        return self._experiment_block(**self._experiments()[c if self.conditions is not None else 0])
 
     def data_block(self):
         """The block the kernels read (csrc/dz_ode.h): one experiment's, or with conditions [C, stride] and the C experiments' blocks."""
-        if self.conditions is None:
-            return self.condition_block()
-        blocks = [self.condition_block(c) for c in range(len(self.conditions))]
-        return np.concatenate([[float(len(blocks)), float(len(blocks[0]))]] + blocks)
+        blocks = [self._experiment_block(**e) for e in self._experiments()]
+        return np.concatenate(([[float(len(blocks)), float(len(blocks[0]))]] if self.conditions is not None else []) + blocks)
+
+    def _per_point(self, results):
+        """[n, C, ...] from the host build as the caller sees it: the axis of conditions only for an object made with conditions"""
+        return results if self.conditions is not None else results[:, 0]
 
     def _monomials(self):
         """What the generated network needs beyond rate constants of one parameter each, or None: then the source is what it always was
@@ -1304,12 +680,7 @@ class MassActionODELogLike:
         return None
 
     def source(self):
-        items = self.conditions is not None
-        if self.lanes_per_point == 1:
-            return _ode_source(self.n_species, self.reactions, self.observables, self.log10, items, self._monomials(), self._max_events(),
-                               self._equilibrates())
-        return _ode_group_source(self.n_species, self.reactions, self.observables, self.log10, self.lanes_per_point, items, self._monomials(),
-                                 self._max_events(), self._equilibrates())
+        return _ode_source.generate(self)
 
     @staticmethod
     def _header_hash(name="dz_ode.h"):
@@ -1333,12 +704,8 @@ class MassActionODELogLike:
         return self.path
 
     def _dz_apply(self, engine):
-        if self.conditions is None:
-            kernel = "dz_ode_batch" if self.lanes_per_point == 1 else "dz_ode_group_batch"
-            engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False)
-        else:
-            kernel = "dz_ode_item_batch" if self.lanes_per_point == 1 else "dz_ode_group_item_batch"
-            engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False, items_per_point=len(self.conditions))
+        kernel = "dz_ode%s%s_batch" % ("" if self.lanes_per_point == 1 else "_group", "" if self.conditions is None else "_item")
+        engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False, items_per_point=len(self._experiments()))
 
     # ---- the host build
     def host_library(self):
@@ -1390,11 +757,11 @@ class MassActionODELogLike:
         """The observables at the output times, [n, T, O] -- with conditions [n, C, T, O] -- (NaN where the integration failed), from the
         host build."""
         X = self._rows(X)
-        lead = (len(X),) if self.conditions is None else (len(X), len(self.conditions))
+        lead = (len(X), len(self._experiments()))
         sim, like = np.full(lead + (len(self.t), len(self.observables)), np.nan), np.zeros(lead)
         self._host_call("dzode_simulate", X, len(X), X.shape[1], self.data_block(), sim, like)
         sim[like == -np.inf] = np.nan
-        return sim
+        return self._per_point(sim)
 
     def batch_conditions(self, X):
         """The per-condition log-likelihoods of the rows of X, [n, C], from the host build: column c is what an object made of condition c
@@ -1412,10 +779,10 @@ class MassActionODELogLike:
         not live), one that does not gives its y0.  return_steps: also the ATTEMPTED steps of the phase, [n] or [n, C] -- what the
         phase's max_steps counts."""
         X = self._rows(X)
-        lead = (len(X),) if self.conditions is None else (len(X), len(self.conditions))
+        lead = (len(X), len(self._experiments()))
         y, st = np.full(lead + (self.n_species,), np.nan), np.zeros(lead, dtype=np.int32)
         self._host_call("dzode_equilibrate", X, len(X), X.shape[1], self.data_block(), y, st)
-        return (y, st) if return_steps else y
+        return (self._per_point(y), self._per_point(st)) if return_steps else self._per_point(y)
 
     def constraint_terms(self, X):
         """g(x) = sum over the constraints of norm(loc, sd).logpdf(monomial) for the rows of X, from the host build: what the single

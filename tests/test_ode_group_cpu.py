@@ -49,7 +49,7 @@ def test_networks_at_the_reaction_limit_compile_without_scratch(S, R, lanes, tmp
 def test_one_lane_networks_at_the_reaction_limit_compile_without_scratch(S, R, lanes, tmp_path, monkeypatch):
     """The one-lane build at its limits, 8 species and up to 64 reactions, on the same recipe (20 parameters): scratch 0.  Above 16
     reactions its generated source builds every sum up reaction by reaction behind fences and keeps one rate constant per parameter
-    (likelihoods._ode_long_source); written like the short form these two took 512 registers and 796 / 84 bytes of scratch."""
+    (_ode_source._ode_long_source); written like the short form these two took 512 registers and 796 / 84 bytes of scratch."""
     monkeypatch.setenv("DREAMZS_KERNEL_CACHE", str(tmp_path))
     like = W.dense_network(S, R, lanes)
     assert "DZODE_FENCE" in like.source() and "dz_ode_group" not in like.source()

@@ -144,13 +144,13 @@ def test_kernel_cache_refuses_a_fallback_directory_others_can_write(tmp_path, mo
     (tmp_path / "file").write_text("")
     monkeypatch.setenv("HOME", str(tmp_path / "file" / "home"))             # ~/.cache cannot be created
     monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
-    monkeypatch.setattr(LK, "_FALLBACK_DIR", [])
+    monkeypatch.setattr(LK._kernel_cache, "_FALLBACK_DIR", [])
     fallback = tmp_path / ("dreamzs_kernels_%d" % os.getuid())
     d = LK.kernel_cache_dir()
     assert d == str(fallback) and stat.S_IMODE(os.stat(d).st_mode) == 0o700
     os.chmod(d, 0o777)                                                      # world-writable: refused
     d2 = LK.kernel_cache_dir()
-    assert d2 != str(fallback) and LK._private_dir(d2) and os.path.dirname(d2) == str(tmp_path)
+    assert d2 != str(fallback) and LK._kernel_cache._private_dir(d2) and os.path.dirname(d2) == str(tmp_path)
     os.chmod(d, 0o700)
     real = os.getuid()
     monkeypatch.setattr(os, "getuid", lambda: real + 1)                     # a directory of another user: refused

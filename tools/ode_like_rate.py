@@ -9,7 +9,7 @@
   * run_dream generations/s with the likelihood on the device against the host path with 16 worker processes
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
-    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle]
+    python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
                                   [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
@@ -41,7 +41,10 @@ mm: tests/ode_networks' Michaelis-Menten network (4 species), imported from the 
 scipy's Radau before anything is timed); chain8 runs with 1 lane per point and with 16, on the same points;
 enzyme13: pydream_amd/examples/enzyme; binding_cycle: pydream_amd/examples/binding_cycle (monomials; 9 conditions per point, so a
 launch covers points x 9 items and steps are counted over a point's nine integrations).  --lanes defaults to the fewest lanes the network fits in.
+Any other name is an example of the package, pydream_amd/examples/<name>/<name>_device.py: its make_likelihood(), the box NOMINAL (or
+TRUE, where the module has no NOMINAL) +- WIDTH (1.0 where it has none); --lanes goes to make_likelihood as lanes_per_point.
 """
+import importlib
 import json
 import os
 import sys
@@ -100,6 +103,10 @@ def network(name, lanes):
         assert lanes in (None, 64), "cascade is a wave-per-point example"
         from pydream_amd.examples.cascade import cascade_device as CAS
         return CAS.make_likelihood(), CAS.NOMINAL, CAS.WIDTH
+    if name not in ("chain8", "chain32", "chain64"):
+        mod = importlib.import_module("pydream_amd.examples.%s.%s_device" % (name, name))
+        like = mod.make_likelihood(**({} if lanes is None else dict(lanes_per_point=lanes)))
+        return like, mod.NOMINAL if hasattr(mod, "NOMINAL") else mod.TRUE, getattr(mod, "WIDTH", 1.0)
     from tests import ode_wide_networks as W
     S = dict(chain8=8, chain32=32, chain64=64)[name]
     if S == 64:
@@ -128,34 +135,48 @@ def with_conditions(like, C):
     return multi, [MassActionODELogLike(*args, s * like.y0, like.t, like.observables, like.data, like.sd, **shared) for s in scales]
 
 
-def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
+def box_points(nominal, width, n):
+    return nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, len(nominal)))
+
+
+def engine_for(like, N, k, nominal, width):
+    """An engine of N chains x k tries with the box prior nominal +- width and the likelihood applied"""
     from pydream_amd import _capi
+    d = len(nominal)
+    eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
+    eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
+    like._dz_apply(eng)
+    return eng
+
+
+def timed(calls, rounds=7, reps=10):
+    """calls: {key: function}.  Three warm-up calls of each, then `rounds` rounds of `reps` timed calls of each, alternately (a drift of
+    the machine hits all alike) -> ({key: the last warm-up's result}, {key: the rounds' microseconds per call})"""
+    last, us = {}, {key: [] for key in calls}
+    for _ in range(3):
+        for key, f in calls.items():
+            last[key] = f()
+    for _ in range(rounds):
+        for key, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            us[key].append((time.perf_counter() - t0) / reps * 1e6)
+    return last, us
+
+
+def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
     like, nominal, width = network(name, lanes)
     multi, singles = with_conditions(like, C)
-    n, d = N * k, len(nominal)
-    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
-
-    def engine(obj):
-        eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
-        eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
-        obj._dz_apply(eng)
-        return eng
-    one, many = engine(multi), [engine(s) for s in singles]
-    combined = lambda: one.eval_logp(X)[1]                              # noqa: E731
-    separate = lambda: [e.eval_logp(X)[1] for e in many]                # noqa: E731
-    for _ in range(3):
-        lk, parts = combined(), separate()
+    n = N * k
+    X = box_points(nominal, width, n)
+    one, many = engine_for(multi, N, k, nominal, width), [engine_for(s, N, k, nominal, width) for s in singles]
+    last, t = timed(dict(combined=lambda: one.eval_logp(X)[1], separate=lambda: [e.eval_logp(X)[1] for e in many]), rounds, reps)
+    lk, parts = last["combined"], last["separate"]
     total = parts[0]
     for p in parts[1:]:
         total = total + p
     assert lk.tobytes() == total.tobytes() == multi.batch(X).tobytes(), "the combined launch, the separate launches and the host build differ"
-    t = {"combined": [], "separate": []}
-    for _ in range(rounds):                                             # alternately: a drift of the machine hits both alike
-        for key, f in (("combined", combined), ("separate", separate)):
-            t0 = time.perf_counter()
-            for _ in range(reps):
-                f()
-            t[key].append((time.perf_counter() - t0) / reps * 1e6)
     steps = np.stack([s.batch(X, return_steps=True)[1] for s in singles], axis=1).reshape(-1)       # item order: the condition fastest
     per_wave = 64 // like.lanes_per_point
     w = steps[: len(steps) // per_wave * per_wave].reshape(-1, per_wave)
@@ -172,7 +193,6 @@ def conditions_rate(N, k, name, lanes, C, rounds=7, reps=10):
 
 def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10, equilibrate=False):
     """E events per condition against none or (equilibrate) the phase on in every condition against off: see the head"""
-    from pydream_amd import _capi
     from pydream_amd.likelihoods import MassActionODELogLike
     like, nominal, width = network(name, lanes)
     plain, _ = with_conditions(like, C)
@@ -188,32 +208,19 @@ def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10, equilibrate=False):
         events = [(like.t0 + (e + 1) * span / (E + 1), s, 0.5, 0.0) if e % 2 == 0 else (like.t0 + (e + 1) * span / (E + 1), s, 1.0, 0.5 * like.y0[s])
                   for e in range(E)]
         objs[second] = MassActionODELogLike(like.n_species, like.reactions, None, like.t, like.observables, like.data, like.sd, events=events, **shared)
-    n, d = N * k, len(nominal)
-    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
-    engines = {}
-    for key, obj in objs.items():
-        eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
-        eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
-        obj._dz_apply(eng)
-        engines[key] = eng
+    n = N * k
+    X = box_points(nominal, width, n)
+    engines = {key: engine_for(obj, N, k, nominal, width) for key, obj in objs.items()}
+    last, t = timed({key: (lambda eng=eng: eng.eval_logp(X)[1]) for key, eng in engines.items()}, rounds, reps)
     out = dict(network=name, lanes=like.lanes_per_point, conditions=C, chains=N, tries=k, points=n, items=n * C,
                **(dict(equilibrate=True) if equilibrate else dict(events_per_condition=E)))
-    for key, eng in engines.items():
-        for _ in range(3):
-            lk = eng.eval_logp(X)[1]
+    for key, lk in last.items():
         host, steps = objs[key].batch(X, return_steps=True)
         assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
         out[key] = dict(steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)))
         if equilibrate and key == second:
             attempts = objs[key].steady_state(X, return_steps=True)[1]
             out[key].update(phase_attempts_median=float(np.median(attempts)), phase_attempts_max=int(attempts.max()))
-    t = {key: [] for key in engines}
-    for _ in range(rounds):                                             # alternately: a drift of the machine hits both alike
-        for key, eng in engines.items():
-            t0 = time.perf_counter()
-            for _ in range(reps):
-                eng.eval_logp(X)
-            t[key].append((time.perf_counter() - t0) / reps * 1e6)
     for key in engines:
         us = float(np.median(t[key]))
         out[key].update(us_per_launch=round(us, 1), us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6))
@@ -230,10 +237,9 @@ def _host_part(args):
 
 def host_twin_rate(N, k, name, lanes, rounds=7, reps=10):
     import multiprocessing
-    from pydream_amd import _capi
     like, nominal, width = network(name, lanes)
-    n, d = N * k, len(nominal)
-    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
+    n = N * k
+    X = box_points(nominal, width, n)
     like.host_library()                                                 # (compiled before anything is timed or forked)
     workers = int(os.environ.get("DREAMZS_HOST_WORKERS", "16"))
     # (the host pass first: its workers are forked before this process opens the device)
@@ -243,18 +249,10 @@ def host_twin_rate(N, k, name, lanes, rounds=7, reps=10):
         parts = pool.map(_host_part, [(like, part) for part in np.array_split(X, workers)])
         host_s = time.perf_counter() - t0
     host, steps = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
-    eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
-    eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
-    like._dz_apply(eng)
-    for _ in range(3):
-        lk = eng.eval_logp(X)[1]
+    eng = engine_for(like, N, k, nominal, width)
+    last, us = timed(dict(device=lambda: eng.eval_logp(X)[1]), rounds, reps)
+    lk, t = last["device"], us["device"]
     assert lk.tobytes() == host.tobytes(), "device and host builds differ"
-    t = []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            eng.eval_logp(X)
-        t.append((time.perf_counter() - t0) / reps * 1e6)
     us = float(np.median(t))
     per_wave = 64 // like.lanes_per_point
     w = steps[: n // per_wave * per_wave].reshape(-1, per_wave)
@@ -290,19 +288,12 @@ def gens_per_s(like, N, k, G, host_workers=None, nominal=ROB.NOMINAL, width=3.0)
 
 
 def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
-    from pydream_amd import _capi
     like, nominal, width = network(name, lanes)
-    n, d = N * k, len(nominal)
-    X = nominal - width + 2 * width * np.random.default_rng(11).uniform(size=(n, d))
-    eng = _capi.Engine(nchains=N, ndim=d, multitry=k, history_capacity=8)
-    eng.set_prior(np.full(d, 2, dtype=np.int32), nominal - width, np.full(d, 2 * width))
-    like._dz_apply(eng)
-    for _ in range(3):
-        eng.eval_logp(X)
-    reps, t0 = 20, time.perf_counter()
-    for _ in range(reps):
-        pr, lk = eng.eval_logp(X)
-    us = (time.perf_counter() - t0) / reps * 1e6
+    n = N * k
+    X = box_points(nominal, width, n)
+    eng = engine_for(like, N, k, nominal, width)
+    last, us = timed(dict(device=lambda: eng.eval_logp(X)[1]), rounds=1, reps=20)
+    lk, us = last["device"], us["device"][0]
     host, steps = like.batch(X, return_steps=True)
     assert lk.tobytes() == host.tobytes(), "device and host builds differ"
     per_wave = 64 // like.lanes_per_point
@@ -333,26 +324,18 @@ if __name__ == "__main__":
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
+    name, lanes = opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None
+    nums = [int(a) for a in argv[:2] if not a.startswith("--")]
+    nums += [4096, 5][len(nums):]
     if "--host-twin" in argv:
-        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
-        host_twin_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None)
-        sys.exit(0)
-    if "--equilibrate" in argv:
+        host_twin_rate(*nums, name, lanes)
+    elif "--equilibrate" in argv:
         assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
-        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
-        events_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
-                    int(opt["--conditions"]), 0, equilibrate=True)
-        sys.exit(0)
-    if "--events" in opt:
+        events_rate(*nums, name, lanes, int(opt["--conditions"]), 0, equilibrate=True)
+    elif "--events" in opt:
         assert "--conditions" in opt, "--events goes with --conditions C"
-        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
-        events_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
-                    int(opt["--conditions"]), int(opt["--events"]))
-        sys.exit(0)
-    if "--conditions" in opt:
-        nums = [int(a) for a in argv[:2] if not a.startswith("--")]
-        conditions_rate(*(nums + [4096, 5][len(nums):]), opt.get("--network", "robertson"), int(opt["--lanes"]) if "--lanes" in opt else None,
-                        int(opt["--conditions"]))
-        sys.exit(0)
-    main(*(int(a) for a in argv[:3] if not a.startswith("--")), kernel_only="--kernel-only" in argv, name=opt.get("--network", "robertson"),
-         lanes=int(opt["--lanes"]) if "--lanes" in opt else None)
+        events_rate(*nums, name, lanes, int(opt["--conditions"]), int(opt["--events"]))
+    elif "--conditions" in opt:
+        conditions_rate(*nums, name, lanes, int(opt["--conditions"]))
+    else:
+        main(*(int(a) for a in argv[:3] if not a.startswith("--")), kernel_only="--kernel-only" in argv, name=name, lanes=lanes)
