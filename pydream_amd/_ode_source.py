@@ -83,7 +83,7 @@ class _Network:
     def __init__(self, like):
         self.S, self.reactions, self.observables, self.log10 = like.n_species, like.reactions, like.observables, like.log10
         self.mono, self.events, self.equilibrate = like._monomials(), like._max_events(), like._equilibrates()
-        self.items, self.lanes = like.conditions is not None, like.lanes_per_point
+        self.items, self.lanes, self.noise = like.conditions is not None, like.lanes_per_point, like.noise
         self.R = len(self.reactions)
         self.N = np.zeros((self.S, self.R), dtype=np.int64)
         for r, (reac, prod, _) in enumerate(self.reactions):
@@ -188,6 +188,38 @@ def _monomial_members(mono):
     return L
 
 
+def _noise_members(net):
+    """The members of a generated network with sampled noise (csrc/dz_ode.h's head, NOISE), for the three emitters alike: the per-point
+    values a_q, b_q with their liveness, and one output time's terms with q a constant.  net.noise: O entries, None or a Noise."""
+    L = ["    static constexpr bool NOISE = true;", "    DZO_HD static double noise_value(int m, const double* x, bool& good)", "    {", "        switch (m) {"]
+    for q, z in enumerate(net.noise):
+        for m, c, bound in ((2 * q, z and z.sigma, "v > 0.0"), (2 * q + 1, z and z.rel, "v >= 0.0")):
+            if c is not None:
+                value, idx = net.constant(c)
+                L.append("        case %d: { const double v = %s; good = %s; return v; }" % (m, value, " && ".join(_finite(idx, ["v"]) + [bound])))
+            elif z is not None:             # (a Noise without rel: b = 0; an observable without a Noise: NaN, below)
+                L.append("        case %d: good = true; return 0.0;" % m)
+    L += ['        default: good = true; return __builtin_nan("");', "        }", "    }",
+          "    DZO_HD static bool noise_terms(const double* nz, const double* o, const double* dat, const double* sd, double& acc)", "    {",
+          "        bool good = true;"]
+    for q, z in enumerate(net.noise):
+        if z is None:                       # (the two statements this observable always ran)
+            L.append("        { const double r = (o[%d] - dat[%d]) / sd[%d]; acc = acc - 0.5 * r * r; }" % (q, q, q))
+            continue
+        log = z.scale == "log"
+        L += ["        {", "            const double m = o[%d], w = sd[%d];" % (q, q),
+              "            double s = nz[%d]%s;" % (2 * q, " + nz[%d] * dzode::dabs(m)" % (2 * q + 1) if z.rel is not None else ""),
+              "            s = s * w;",
+              "            const double r = (%s - dat[%d]) / s;" % ("dzode::dlog(m)" if log else "m", q),
+              "            double a = acc - %s;" % ("0.5 * r * r" if z.dist == "normal" else "dzode::dabs(r)"),
+              "            a = a - dzode::dlog(s);",
+              "            const bool seen = w < __builtin_huge_val();",
+              "            acc = seen ? a : acc;",
+              "            good = good && (!seen || (dzode::finite(m) && %sdzode::finite(s) && s > 0.0));" % ("m > 0.0 && " if log else ""),
+              "        }"]
+    return L + ["        return good;", "    }"]
+
+
 def _product(factors):
     return " * ".join(factors) if factors else "1.0"
 
@@ -227,7 +259,7 @@ def _net_source(net, body):
     L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (net.S, net.R, len(net.observables))]
     L += ["    static constexpr int EVENTS = %d;" % net.events] if net.events else []
     L += ["    static constexpr bool EQUILIBRATE = true;"] if net.equilibrate else []
-    L += body + (_monomial_members(net.mono) if net.mono else [])
+    L += body + (_monomial_members(net.mono) if net.mono else []) + (_noise_members(net) if net.noise else [])
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(net.S, net.observables) + ["    }", "};", entries, ""]
     return '#include "%s"\n' % header + "\n".join(L)
 

@@ -1,5 +1,5 @@
 """The limits of pydream_amd.likelihoods.MassActionODELogLike, the predicates its checks are made of, and the immutable values a network
-is written with: Monomial, Hill, RateLaw."""
+is written with: Monomial, Hill, RateLaw, Noise."""
 import numpy as np
 
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
@@ -191,3 +191,51 @@ class RateLaw:
 
     def __repr__(self):
         return "RateLaw(%r, %r, %r)" % (self.rate, list(self.factors), None if self.order is None else dict(self.order))
+
+
+class Noise:
+    """An observable's measurement noise as a sampled quantity, for MassActionODELogLike(noise=[...]): the residual of observable q at an
+    output time is scaled by s = sigma (with rel: sigma + rel * |m|, m the simulated observable) times the entry's fixed weight, and
+    the term -log s is part of the likelihood.  sigma, rel: a parameter index (10**x[i] under rate_scale "log10", x[i] under "linear"),
+    a finite float (sigma > 0, rel >= 0) or a Monomial; rel None: no proportional part.  dist: "normal" or "laplace" residuals; scale:
+    "lin", or "log" -- the residual is ln m - ln data (rel is then refused: a proportional part on the log scale is the log scale
+    itself).  An immutable value."""
+    __slots__ = ("sigma", "rel", "dist", "scale")
+
+    def __init__(self, sigma, rel=None, dist="normal", scale="lin"):
+        sigma = _checked_constant(sigma, "a Noise's sigma")
+        if isinstance(sigma, float) and not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError("MassActionODELogLike: a Noise's fixed sigma must be finite and > 0 (got %r)" % (sigma,))
+        if rel is not None:
+            rel = _checked_constant(rel, "a Noise's rel")
+            if isinstance(rel, float) and not (np.isfinite(rel) and rel >= 0):
+                raise ValueError("MassActionODELogLike: a Noise's fixed rel must be finite and >= 0 (got %r)" % (rel,))
+        if dist not in ("normal", "laplace"):
+            raise ValueError('MassActionODELogLike: a Noise\'s dist must be "normal" or "laplace" (got %r)' % (dist,))
+        if scale not in ("lin", "log"):
+            raise ValueError('MassActionODELogLike: a Noise\'s scale must be "lin" or "log" (got %r)' % (scale,))
+        if rel is not None and scale == "log":
+            raise ValueError('MassActionODELogLike: a Noise with scale "log" takes no rel: a proportional part on the log scale is the log scale itself')
+        for name, v in zip(self.__slots__, (sigma, rel, dist, scale)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Noise is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a Noise is immutable")
+
+    def _key(self):
+        return (type(self.sigma).__name__, self.sigma, type(self.rel).__name__, self.rel, self.dist, self.scale)
+
+    def __eq__(self, other):
+        return isinstance(other, Noise) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return Noise, (self.sigma, self.rel, self.dist, self.scale)
+
+    def __repr__(self):
+        return "Noise(%r, %r, %r, %r)" % (self.sigma, self.rel, self.dist, self.scale)

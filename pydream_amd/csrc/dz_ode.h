@@ -111,6 +111,38 @@
 // The Jacobian stays analytic, straight-line code with every entry written.  A network without a RateLaw generates the source it always
 // did, and compiles to what it compiled to before the member existed.
 //
+// NOISE (likelihoods.Noise, MassActionODELogLike(noise=...)): the spread of an observable's measurement as a sampled quantity.  For an
+// observable q with a Noise(sigma, rel, dist, scale) the residual's scale is no number of the data block but a function of the point:
+//   * PER-POINT VALUES: a_q = sigma_q and b_q = rel_q (0 without rel) are evaluated once per point, when its rate constants are, with
+//     the arithmetic of a rate constant (a parameter: dexp(x[i] * 2.302585092994046) under "log10", x[i] under "linear"; a monomial: its
+//     sum and one dexp; a fixed number: itself), and never again per output time.  Value 2q of the network is a_q, value 2q + 1 is b_q:
+//     the one-lane shape keeps the 2 O of them in registers beside the rate constants; the lane group and the wave keep them in the
+//     point's LDS row behind everything else (group_lds_row counts them), value m evaluated by lane m % L.
+//   * LIVENESS: a point is not live (-inf) if a coordinate that a Noise reads is not finite, an a_q is not finite or not > 0, or a b_q
+//     is not finite or < 0.  Under "linear" a sampled sigma <= 0 rejects the point.
+//   * THE ENTRY'S TERM at an output time j, with m = o[q] after scale, and d = data, w = sd from the block (for such an observable sd
+//     is a fixed WEIGHT, the replicate's relative precision):
+//         scale "lin":   s = a_q   (with rel: s = a_q + b_q * dabs(m));   s = s * w;   r = (m - d) / s
+//         scale "log":   the block's data slot holds ln d, computed on the host;   s = a_q * w;   r = (dlog(m) - lnd) / s
+//         dist "normal":    acc = acc - 0.5 * r * r;   acc = acc - dlog(s);
+//         dist "laplace":   acc = acc - dabs(r);       acc = acc - dlog(s);
+//   * AN UNOBSERVED ENTRY has w = +inf in the block, as always, and contributes exactly 0 by a select on w, whatever m is -- also
+//     m <= 0 on the log scale.
+//   * A FAILED INTEGRATION (-inf): an observed entry at which m is not finite, the scale is "log" and m is not > 0, or s is not
+//     finite or not > 0.
+//   * THE CONSTANT C (blk[0]) is the sum over the observed entries of: -log sd - log(2 pi) / 2 for an observable without a Noise, as
+//     always; -log(2 pi) / 2 for "normal"; -log 2 for "laplace"; on the "log" scale additionally -ln d.  w is inside s and not in C.
+//   * Entries are visited in the loop's order, j and then q; an observable without a Noise runs the two statements it always ran; sim
+//     holds the scaled observables on the natural scale.
+// A network with at least one Noise carries
+//     static constexpr bool NOISE = true;
+//     static double noise_value(int m, const double* x, bool& good);   value m of the point and its liveness (no Noise: NaN; no rel: 0)
+//     static bool noise_terms(const double* nz, const double* o, const double* dat, const double* sd, double& acc);
+//                                                                      one output time's O entries, q ascending, straight-line code with q
+//                                                                      a constant (nz: the 2 O values; dat, sd: the time's rows of the block);
+//                                                                      false: a failed integration
+// and a network without one generates the source, and the data block, it always did.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -237,6 +269,28 @@ template <class Net> struct has_slots<Net, decltype((void)Net::SLOTS)> {
 };
 // the doubles of a point's rate constants and slots (an array of at least one)
 template <class Net> constexpr int rate_doubles() { return Net::R + has_slots<Net>::count > 0 ? Net::R + has_slots<Net>::count : 1; }
+
+// ... and sampled noise (the head of the file, NOISE): 2 O per-point values, a_q and b_q
+template <class Net, class = void> struct has_noise { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_noise<Net, decltype((void)Net::NOISE)> { static constexpr bool value = true; static constexpr int count = 2 * Net::O; };
+// the doubles of a point's noise values (an array of at least one)
+template <class Net> constexpr int noise_doubles() { return has_noise<Net>::count > 0 ? has_noise<Net>::count : 1; }
+
+// The point's noise values nz[2 O] in the order of the contract; false if one of them says that the point is not live.
+template <class Net>
+DZO_HD bool noise_point(const double* x, double* nz)
+{
+    bool good = true;
+    if constexpr (has_noise<Net>::value) {
+#pragma unroll
+        for (int m = 0; m < has_noise<Net>::count; ++m) {
+            bool g;
+            nz[m] = Net::noise_value(m, x, g);
+            good = good && g;
+        }
+    }
+    return good;
+}
 
 template <class Net>
 DZO_HD bool monomials_live(const double* x)
@@ -460,6 +514,7 @@ DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h
 //     sh.observe(y, o)                                 o[O]
 //     Shape::EVENTS, sh.apply(y, species, factor, amount)   (a network with events: Emax, and y[species] = factor * y[species] + amount)
 //     Shape::EQUILIBRATE, sh.drift2(y, rtol, atol)     (a network that equilibrates: the steady-state test's wnorm2(f(y), y, rtol, atol))
+//     Shape::Net, sh.noise()                           (a network with sampled noise: where the point's 2 O noise values are)
 // and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
 // Group<Net, L> (dz_ode_group.h: a group of L lanes per point, and its host twin).  A point that is not live keeps h = 0, ok = false and
 // takes no step, but does not return ahead of the loop: the lanes of a group stay with their wave.
@@ -583,11 +638,19 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             if (tend < tout) continue;                                       // landed on an event, not on the output time
         }
         sh.observe(y, o);
+        if constexpr (has_noise<typename Shape::Net>::value) {               // (the head of the file, NOISE: the network's own terms)
+            const bool fine = Shape::Net::noise_terms(sh.noise(), o, dat + (long long)j * O, sd + (long long)j * O, acc);
 #pragma unroll
-        for (int q = 0; q < O; ++q) {
-            const double r = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
-            acc = acc - 0.5 * r * r;
-            if (sim) sim[(long long)j * O + q] = o[q];
+            for (int q = 0; q < O; ++q)
+                if (sim) sim[(long long)j * O + q] = o[q];
+            if (!fine) { ok = false; break; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < O; ++q) {
+                const double r = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
+                acc = acc - 0.5 * r * r;
+                if (sim) sim[(long long)j * O + q] = o[q];
+            }
         }
         ++j;
     }
@@ -632,9 +695,12 @@ template <class Alg>
 struct Array {
     static constexpr int S = Alg::Net::S, O = Alg::Net::O, EVENTS = has_events<typename Alg::Net>::count;
     static constexpr bool EQUILIBRATE = has_equilibrate<typename Alg::Net>::value;
+    typedef typename Alg::Net Net;
     struct State { double v[S]; };
     const double* k;                                   // the rate constants
     const double* x;                                   // the point's row (read only by a network with monomials)
+    const double* nz = nullptr;                        // the point's noise values (read only by a network with sampled noise)
+    DZO_HD const double* noise() const { return nz; }
     DZO_HD void init(const double* blk, State& y) const
     {
 #pragma unroll
@@ -679,9 +745,15 @@ template <class Alg>
 DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out, bool first = true)
 {
     double k[rate_doubles<typename Alg::Net>()];
+    [[maybe_unused]] double nz[noise_doubles<typename Alg::Net>()];
     if (nsteps_out) *nsteps_out = 0;
     if (!Alg::rates(x, k)) return -__builtin_huge_val();
-    return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
+    if constexpr (has_noise<typename Alg::Net>::value) {
+        if (!noise_point<typename Alg::Net>(x, nz)) return -__builtin_huge_val();
+        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x, nz}, blk, true, sim, nsteps_out), x, first);
+    } else {
+        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
+    }
 }
 
 // The host build's resting state of one point's experiment (blk: one experiment's block): the state handed to the experiment, before
@@ -714,6 +786,16 @@ DZO_HD double constraint_term(const double* x)
     return Alg::rates(x, k) ? add_constraints<typename Alg::Net>(0.0, x, true) : -__builtin_huge_val();
 }
 
+// The host build's noise values of one point alone, ab[O][2] = (a_q, b_q) whether or not the point is live (a network without sampled
+// noise: NaN throughout).
+template <class Net>
+DZO_HD void noise_values(const double* x, double* ab)
+{
+    if constexpr (has_noise<Net>::value) noise_point<Net>(x, ab);
+    else
+        for (int m = 0; m < 2 * Net::O; ++m) ab[m] = __builtin_nan("");
+}
+
 // The host build's point under C conditions (the data block with the [C, stride] header): the rate constants once, then condition by
 // condition in ascending order through the same integrate as a device item, the terms added as k_sum_items adds the items:
 // ((l_0 + l_1) + l_2) + ... (l_0 with the constraints' g, if the network has any).  terms[C] (optional): the l_c; sim (optional): [C][T][O]; nsteps_out: the steps of all conditions.
@@ -723,12 +805,14 @@ DZO_HD double integrate_conditions(const double* x, const double* hdr, double* t
     const int C = (int)hdr[0];
     const long long stride = (long long)hdr[1], per = (long long)(int)hdr[2 + 5] * Alg::Net::O;
     double k[rate_doubles<typename Alg::Net>()];
-    const bool live = Alg::rates(x, k);
+    double nz[noise_doubles<typename Alg::Net>()];
+    const bool rated = Alg::rates(x, k);
+    const bool live = noise_point<typename Alg::Net>(x, nz) && rated;
     double total = 0.0;
     int steps = 0;
     for (int c = 0; c < C; ++c) {
         int st = 0;
-        double v = live ? integrate(Array<Alg>{k, x}, hdr + 2 + c * stride, true, sim ? sim + c * per : nullptr, &st) : -__builtin_huge_val();
+        double v = live ? integrate(Array<Alg>{k, x, nz}, hdr + 2 + c * stride, true, sim ? sim + c * per : nullptr, &st) : -__builtin_huge_val();
         if (live) v = add_constraints<typename Alg::Net>(v, x, c == 0);
         if (terms) terms[c] = v;
         total = c == 0 ? v : total + v;
@@ -771,6 +855,10 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     extern "C" void dzode_constraints(const double* X, long long n, int ld, double* g)                                                  \
     {                                                                                                                                    \
         for (long long i = 0; i < n; ++i) g[i] = dzode::constraint_term<ALG>(X + i * ld);                                                \
+    }                                                                                                                                    \
+    extern "C" void dzode_noise(const double* X, long long n, int ld, double* ab)                                                       \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) dzode::noise_values<ALG::Net>(X + i * ld, ab + i * 2 * ALG::Net::O);                           \
     }                                                                                                                                    \
     extern "C" double dzode_exp(double x) { return dzode::dexp(x); }                                                                     \
     extern "C" double dzode_log(double x) { return dzode::dlog(x); }

@@ -41,6 +41,9 @@
 //     static double rate_mono(int j, const double* x, bool& good);    the rate constant of a reaction whose rate_index is -2
 // and, for a network with rate laws (dz_ode.h's head, RATE LAWS: Hill factors and kinetic orders inside rhs_row / jac_entry),
 //     static constexpr int SLOTS;  static double slot(int m, const double* x, bool& good);    Kn of the distinct (K, n) pair m: entry R + m of k
+// and, for a network with sampled noise (dz_ode.h's head, NOISE: the members NOISE, noise_value and noise_terms), the point's 2 O noise
+// values at the very end of its LDS row (noise_row), value m evaluated by lane m % L when the rate constants are; the host twin takes
+// them from dz_ode.h's noise_point, the same generated function value by value.
 // Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd; with the
 // equilibration phase: its six doubles at the end.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
 // the group's norm, a group-wide value).
@@ -221,6 +224,10 @@ struct Replica<Net, 64> {                     // a wave: its S doubles of LDS; a
     __device__ __forceinline__ void fill(int r, double own) { wave_publish<Net::S>(y, r, own); }
 };
 
+// The point's noise values in its row of LDS: behind the rate constants, the slots and (64 lanes) the wave's state.
+template <class Net, int L>
+__device__ __forceinline__ double* noise_row(double* ks) { return ks + Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0); }
+
 template <class Net, int L>
 __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
 {
@@ -229,6 +236,13 @@ __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
         bool g;
         ks[j] = rate_constant<Net>(j, x, g);
         good = good && g;
+    }
+    if constexpr (has_noise<Net>::value) {      // (the point's noise values, behind everything else in its row: dz_ode.h's NOISE)
+        for (int m = r; m < has_noise<Net>::count; m += L) {
+            bool g;
+            noise_row<Net, L>(ks)[m] = Net::noise_value(m, x, g);
+            good = good && g;
+        }
     }
     return !Lanes<L>::any(!(good && monomials_live<Net>(x)));
 }
@@ -376,14 +390,16 @@ __device__ __forceinline__ double group_start_step(double* ks, double y, double 
 
 // The group's shape for dz_ode.h's integrate: lane r's entry of the state.  Every lane of the group returns the same value.  The caller's
 // live = false (a point past the batch's end, or a rate constant that is not finite): no step is taken, -inf.
-template <class Net, int L>
+template <class NET, int L>
 struct Group {
+    typedef NET Net;
     static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
     static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
     typedef double State;
     double* ks;                                        // the point's row of LDS: its rate constants (64 lanes: and its state behind them)
     int r;
     const double* x;                                   // the point's row (read only by a network with monomials)
+    __device__ __forceinline__ const double* noise() const { return noise_row<Net, L>(ks); }      // (a network with sampled noise)
     __device__ __forceinline__ void init(const double* blk, double& y) const { y = r < S ? start_amount<Net>(r, x, blk[6 + r]) : 0.0; }
     __device__ __forceinline__ double start_step(double y, double rtol, double atol, double span) const
     {
@@ -417,9 +433,9 @@ struct Group {
 };
 
 // The doubles of static LDS a point's lanes share: R + 1 rate constants (with rate laws: R + SLOTS + 1, the Hill slots behind the rate
-// constants), and for a wave per point the S doubles of its state behind them.
+// constants), for a wave per point the S doubles of its state behind them, and for a network with sampled noise its 2 O values last.
 template <class Net, int L>
-constexpr int group_lds_row() { return Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0); }
+constexpr int group_lds_row() { return Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0) + has_noise<Net>::count; }
 #endif
 
 #if !defined(__HIP__)

@@ -10,7 +10,7 @@ from . import _kernel_cache, _ode_source      # noqa: F401
 from ._kernel_cache import _build_cached, _compiler_version, compile_device_kernel, csrc_dir, kernel_cache_dir      # noqa: F401
 from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate_indices, _slot_indices
 from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
-                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS, Hill, Monomial, RateLaw,
+                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS, Hill, Monomial, Noise, RateLaw,
                           _checked_constant, _is_int, _is_real)
 
 
@@ -368,17 +368,45 @@ class MassActionODELogLike:
     the indices every K reads.  A RateLaw with no factors and order=None is the plain reaction, source and bits; a model without a
     RateLaw generates the source and the data block it always did.  Conditions, Monomials, events, equilibration, fixed_steps,
     simulate and steady_state work with it unchanged.  Not supported: a non-integer or sampled Hill exponent, arbitrary rate
-    expressions, time-dependent inputs, rate laws in event amounts."""
+    expressions, time-dependent inputs, rate laws in event amounts.
+
+    Sampled noise: noise=[...], None or O entries, each None or a Noise(sigma, rel=None, dist="normal", scale="lin"), shared by all
+    conditions like `scale`.  An observable whose entry is None keeps the fixed-sd term above exactly; for one with a Noise the spread
+    of the readout is part of the point, and its sd (still O x T, the constructor's or a condition's; sd=None means 1 when every
+    observable has a Noise) is a fixed WEIGHT w, the replicate's relative precision.  sigma and rel are a parameter index (10**x[i]
+    under "log10", x[i] under "linear"), a finite float (sigma > 0, rel >= 0) or a Monomial; dist is "normal" or "laplace"; scale is
+    "lin" or "log" (rel with "log" is refused: a proportional part on the log scale is the log scale itself; data of a "log" observable
+    must be > 0 where observed).  The contract (csrc/dz_ode.h's head, NOISE), the same in both builds and every shape:
+      * a_q = sigma_q and b_q = rel_q are evaluated once per point, when the rate constants are and with their arithmetic (one dexp,
+        or the Monomial's sum), never per output time; noise_values(X) returns them, [n, O, 2] (NaN for an observable without a Noise,
+        b = 0 without rel);
+      * a point is -inf if a coordinate that a Noise reads is not finite, a_q is not finite or not > 0, or b_q is not finite or < 0:
+        under "linear" a sampled sigma <= 0 rejects the point;
+      * at an output time, with m the observable after `scale`, d the data and w the weight: "lin": s = a_q (with rel: a_q + b_q |m|),
+        s = s * w, r = (m - d) / s; "log": s = a_q * w, r = (dlog(m) - ln d) / s with ln d computed on the host; "normal" adds
+        -r r / 2 - dlog(s), "laplace" -|r| - dlog(s): the log-likelihood is sum norm(m, s).logpdf(d), or laplace(m, s), and on the log
+        scale the same density at ln d around ln m, minus ln d;
+      * an entry that is not observed (NaN data) adds exactly 0 whatever m is, also m <= 0 on the log scale; an observed entry at
+        which m is not finite, m is not > 0 on the log scale, or s is not finite or not > 0 is a failed integration (-inf);
+      * the block's constant holds, per observed entry, -log sd - log(2 pi) / 2 (no Noise), -log(2 pi) / 2 ("normal"), -log 2
+        ("laplace") and on the log scale additionally -ln d; w is inside s.
+    simulate still returns the scaled observables on the natural scale; ndim covers every index a Noise reads; noise=None and a list
+    of Nones generate the source and the data block the object always had.  Not supported: Student-t residuals, a per-condition
+    noise, a sampled offset on the log scale; fixed_steps has no likelihood and ignores noise."""
 
     conditions = None       # (an object pickled before the keyword existed)
     events = None           # (likewise)
     equilibrate = None      # (likewise)
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
+    noise = None            # (likewise: before Noise existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
-                 equilibrate=None):
+                 equilibrate=None, noise=None):
         self.n_species, self.lanes_per_point, lim = self._checked_shape(n_species, lanes_per_point, len(reactions))
+        noise = self._checked_noise(noise)      # None, or the entries (None | Noise); their number is tested below, once O is known
+        if sd is None and noise is not None and all(z is not None for z in noise):
+            sd = 1.0                            # (every observable has a Noise: sd is a weight, 1 unless the user says otherwise)
         if rate_scale not in ("log10", "linear"):
             raise ValueError('MassActionODELogLike: rate_scale must be "log10" or "linear"')
         self.rate_scale, self.log10 = rate_scale, rate_scale == "log10"
@@ -387,6 +415,9 @@ class MassActionODELogLike:
         self.y0_monomials = {}                  # species -> the Monomial its start amount is, wherever a y0 says so (the same in all)
         self.y0 = y0 if y0 is None else self._checked_y0(y0, "")
         self.t, self.t0, self.observables = self._checked_times(t, t0, observables, self.n_species, lim)
+        if noise is not None and len(noise) != len(self.observables):
+            raise ValueError("MassActionODELogLike: noise must be None or hold O = %d entries, each None or a Noise (got %d)" % (len(self.observables), len(noise)))
+        self.noise = noise if noise is not None and any(z is not None for z in noise) else None
         self.data, self.sd = self._checked_data(data, sd, "") if data is not None and sd is not None else (data, sd)
         events = self._checked_events(events, "")
         if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
@@ -521,9 +552,23 @@ class MassActionODELogLike:
             raise ValueError("MassActionODELogLike: at most %d constraints are supported (got %d)" % (ODE_MAX_CONSTRAINTS, len(cons)))
         return tuple(cons)
 
+    @staticmethod
+    def _checked_noise(noise):
+        """None, or the noise models as a list of None | Noise"""
+        if noise is None:
+            return None
+        try:
+            entries = list(noise)
+        except TypeError:
+            entries = [noise]
+        if isinstance(noise, Noise) or not all(z is None or isinstance(z, Noise) for z in entries):
+            raise ValueError("MassActionODELogLike: noise must be None or a sequence of O entries, each None or a Noise (got %r)" % (noise,))
+        return entries
+
     def _checked_ndim(self, ndim):
-        """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K or a Monomial reads."""
+        """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K, a Monomial or a Noise reads."""
         outside = list(self.y0_monomials.values()) + [f for f in self.scale or [] if isinstance(f, Monomial)] + [c[0] for c in self.constraints]
+        outside += [c for z in self.noise or [] if z is not None for c in (z.sigma, z.rel) if c is not None and not isinstance(c, float)]
         idx = _rate_indices(self.reactions) + _slot_indices(_hill_slots(self.reactions)) + _indices_read(outside)
         d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
         if idx and max(idx) >= d:
@@ -614,6 +659,9 @@ class MassActionODELogLike:
         seen = np.isfinite(data)
         if np.any(np.isinf(data)) or not np.all(np.isfinite(sd[seen]) & (sd[seen] > 0)):
             raise ValueError("MassActionODELogLike: %sdata must be finite or NaN (not observed), and sd finite and > 0 where data is observed" % who)
+        for q, z in enumerate(self.noise or []):
+            if z is not None and z.scale == "log" and np.any(data[q][seen[q]] <= 0):
+                raise ValueError('MassActionODELogLike: %sdata of observable %d must be > 0 where observed: its Noise has scale "log"' % (who, q))
         return data, np.array(sd)
 
     # ---- the data block (csrc/dz_ode.h) and the generated source
@@ -644,7 +692,20 @@ class MassActionODELogLike:
 
     def _experiment_block(self, y0, data, sd, events=(), equilibrate=None):
         seen = np.isfinite(data)
-        C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
+        if self.noise is None:
+            C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
+        else:                                   # (csrc/dz_ode.h, NOISE: an entry's constant by its observable's model; "log": ln d in the data slot)
+            const, data = np.zeros(data.shape), np.array(data)
+            for q, z in enumerate(self.noise):
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    if z is None:
+                        const[q] = -np.log(sd[q]) - _LOG_2PI_HALF
+                        continue
+                    const[q] = -_LOG_2PI_HALF if z.dist == "normal" else -np.log(2.0)
+                    if z.scale == "log":
+                        data[q] = np.log(data[q])
+                        const[q] = const[q] - data[q]
+            C = float(np.sum(const[seen]))
         dat = np.where(seen, data, 0.0).T.reshape(-1)               # (time-major; unobserved: data 0, sd inf -> adds exactly 0)
         sd = np.where(seen, sd, np.inf).T.reshape(-1)
         blk = [[C, self.rtol, self.atol, float(self.max_steps), self.t0, float(len(self.t))], y0, self.t, dat, sd]
@@ -725,6 +786,7 @@ class MassActionODELogLike:
             L.dzode_fixed.restype = I
             L.dzode_constraints.argtypes = [P, I64, I, P]
             L.dzode_equilibrate.argtypes = [P, I64, I, P, P, C.POINTER(C.c_int)]
+            L.dzode_noise.argtypes = [P, I64, I, P]
             L.dzode_exp.argtypes = L.dzode_log.argtypes = [D]
             L.dzode_exp.restype = L.dzode_log.restype = D
             self._host = L
@@ -792,6 +854,14 @@ class MassActionODELogLike:
         g = np.zeros(len(X))
         self._host_call("dzode_constraints", X, len(X), X.shape[1], g)
         return g
+
+    def noise_values(self, X):
+        """The per-point noise values of the rows of X, [n, O, 2], from the host build: (a_q, b_q) = (sigma_q, rel_q) as the kernels hold
+        them (csrc/dz_ode.h, NOISE), whether or not the point is live.  NaN for an observable without a Noise; b is 0 without rel."""
+        X = self._rows(X)
+        ab = np.full((len(X), len(self.observables), 2), np.nan)
+        self._host_call("dzode_noise", X, len(X), X.shape[1], ab)
+        return ab
 
     def fixed_steps(self, x, t1, nsteps, embedded=False, condition=0):
         """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test).

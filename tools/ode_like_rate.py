@@ -10,7 +10,7 @@
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
-                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin]
+                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -27,6 +27,12 @@ alone and never names the keyword (so the same script runs on a checkout from be
 True)) -- the network under C conditions with the phase on in every condition against the same C conditions without it, alternately,
 the median of 7 rounds of 10 calls each and the rounds' spread; proposals/s, the host build's steps per point for both and the phase's
 attempted steps per item.  Kernel only.
+
+--noise: what a sampled noise model costs (MassActionODELogLike(noise=...)) -- the network with a Noise(sigma, rel) on every observable,
+sigma and rel two further coordinates (10**x, x in 0 +- 0.5 and -1 +- 0.5; the network's sd stays as the entries' weight), against the
+same network without the keyword on the same rate constants, alternately, the median of 7 rounds of 10 calls each and the rounds'
+spread; proposals/s and the host build's steps per point for both.  The per-entry cost is one dlog and a division at each of the T x O
+entries of an integration.  Kernel only.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -230,6 +236,33 @@ def events_rate(N, k, name, lanes, C, E, rounds=7, reps=10, equilibrate=False):
     return out
 
 
+def noise_rate(N, k, name, lanes, rounds=7, reps=10):
+    """A Noise(sigma, rel) on every observable against the network as it is: see the head"""
+    from pydream_amd.likelihoods import MassActionODELogLike, Noise
+    like, nominal, width = network(name, lanes)
+    assert like.conditions is None and like.events is None and like.equilibrate is None and not like.y0_monomials and not like.constraints and like.scale is None
+    d, n = like.d, N * k
+    noisy = MassActionODELogLike(like.n_species, like.reactions, like.y0, like.t, like.observables, like.data, like.sd, rate_scale=like.rate_scale, t0=like.t0,
+                                 rtol=like.rtol, atol=like.atol, max_steps=like.max_steps, lanes_per_point=like.lanes_per_point,
+                                 noise=[Noise(d, rel=d + 1)] * len(like.observables))
+    X = np.concatenate([box_points(nominal, width, n), box_points(np.array([0.0, -1.0]), 0.5, n)], axis=1)
+    objs = dict(without_noise=(like, X[:, :d].copy()), with_noise=(noisy, X))
+    engines = {}
+    for key, (obj, pts) in objs.items():
+        engines[key] = engine_for(obj, N, k, pts.mean(axis=0), 4.0)              # (a box that holds every point: the prior is not what is timed)
+    last, t = timed({key: (lambda key=key: engines[key].eval_logp(objs[key][1])[1]) for key in objs}, rounds, reps)
+    out = dict(network=name, lanes=like.lanes_per_point, species=like.n_species, observables=len(like.observables), times=len(like.t), chains=N, tries=k, points=n)
+    for key, lk in last.items():
+        host, steps = objs[key][0].batch(objs[key][1], return_steps=True)
+        assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
+        us = float(np.median(t[key]))
+        out[key] = dict(steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)), us_per_launch=round(us, 1),
+                        us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6))
+    out["with_over_without"] = round(out["with_noise"]["us_per_launch"] / out["without_noise"]["us_per_launch"], 3)
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def _host_part(args):
     like, part = args
     return like.batch(part, return_steps=True)
@@ -329,6 +362,8 @@ if __name__ == "__main__":
     nums += [4096, 5][len(nums):]
     if "--host-twin" in argv:
         host_twin_rate(*nums, name, lanes)
+    elif "--noise" in argv:
+        noise_rate(*nums, name, lanes)
     elif "--equilibrate" in argv:
         assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
         events_rate(*nums, name, lanes, int(opt["--conditions"]), 0, equilibrate=True)
