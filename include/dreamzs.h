@@ -142,6 +142,26 @@ int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const c
  * dz_set_likelihood_module, which resets it to 1; 1..DZ_MAX_LIKELIHOOD_ITEMS.  With C > 1 the generations run the multi-kernel path. */
 #define DZ_MAX_LIKELIHOOD_ITEMS 64
 int dz_set_likelihood_items(dz_engine* e, int32_t items_per_point);
+/* A device kernel that returns ARRAYS per item beside its term -- posterior-predictive trajectories, per-datum residuals, anything a model
+ * computes on the way to its log likelihood.  The code object exports
+ *     extern "C" __global__ __launch_bounds__(256)
+ *     void NAME(const double* X, long long n, int d, int ld, double* like, const void* data, double* out, long long out_ld);
+ * X, d, ld, data and the grid rules are those of dz_set_likelihood_module with `items_per_point` items per point: the kernel's n is the
+ * ITEM count, item w belongs to point w / C and is that point's term w % C (C = 1: item w is point w); lanes_per_point (1, 16, 32 or 64)
+ * counts the lanes of an item.  The kernel writes the item's term to like[w] and its `doubles_per_item` values to out[w * out_ld + m],
+ * m < doubles_per_item (out_ld = doubles_per_item: an item's values are contiguous); it must write every one of them, the buffer is
+ * reused and never cleared.  The output module is independent of the likelihood: its own code object, its own device copy of `data`;
+ * neither call replaces the other's module, and the generations never launch this kernel.  Any user kernel with this signature may use
+ * the two functions, not only the ODE models of pydream_amd.likelihoods (MassActionODELogLike.device(): the kernels dz_ode_predict,
+ * dz_ode_item_predict, dz_ode_group_predict and dz_ode_group_item_predict of csrc/dz_ode.h and csrc/dz_ode_group.h). */
+int dz_set_output_module(dz_engine* e, const char* code_object_path, const char* kernel_name, int32_t lanes_per_point, int32_t items_per_point,
+                         int64_t doubles_per_item, const void* data, int64_t data_bytes);
+/* Evaluate the output module on n arbitrary points X [n, d]: the rows are uploaded as dz_eval_logp uploads them, the kernel is launched
+ * once over n * items_per_point items, and after a synchronisation the terms and the outputs come back exactly as the kernel wrote them:
+ * no prior is added, the terms are not summed over a point's items and nan is not mapped to -inf.  The device buffers grow on demand and
+ * are reused by later calls.  n: 1..2^22, and n * items_per_point within one launch's grid. */
+int dz_eval_outputs(dz_engine* e, const double* X, int64_t n, double* like_items /* [n * items_per_point] */,
+                    double* out /* [n * items_per_point][doubles_per_item] */);
 
 /* Multi-GPU: chains are sharded, Z / positions are replicated by an all-gather at the
  * end of appending generations (replaces the multiprocessing shared arrays,

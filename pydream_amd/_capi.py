@@ -36,7 +36,7 @@ XCHG_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 SYMBOLS = [
     "dz_version", "dz_last_error", "dz_device_count", "dz_create", "dz_destroy", "dz_set_bounds", "dz_set_gamma_table",
     "dz_set_history", "dz_set_state", "dz_set_cr_probs", "dz_set_gamma_probs", "dz_set_prior", "dz_set_likelihood_mvn",
-    "dz_set_likelihood_mixture", "dz_set_likelihood_host", "dz_set_likelihood_module", "dz_set_likelihood_items", "dz_hip_library", "dz_comm_library", "dz_comm_unique_id", "dz_comm_init_rccl", "dz_comm_count", "dz_comm_barrier", "dz_set_exchange", "dz_peer_export", "dz_peer_attach", "dz_peer_detach", "dz_exchange_stats", "dz_exchange_bytes", "dz_set_temperatures", "dz_get_swaps",
+    "dz_set_likelihood_mixture", "dz_set_likelihood_host", "dz_set_likelihood_module", "dz_set_likelihood_items", "dz_set_output_module", "dz_eval_outputs", "dz_hip_library", "dz_comm_library", "dz_comm_unique_id", "dz_comm_init_rccl", "dz_comm_count", "dz_comm_barrier", "dz_set_exchange", "dz_peer_export", "dz_peer_attach", "dz_peer_detach", "dz_exchange_stats", "dz_exchange_bytes", "dz_set_temperatures", "dz_get_swaps",
     "dz_step", "dz_continue_run", "dz_step_range", "dz_set_chain_state", "dz_get_chain_state", "dz_get_chain_probs", "dz_sync", "dz_trace_reset", "dz_generation", "dz_redraw_rounds", "dz_last_kernel_variant", "dz_last_kernel_tries", "dz_get_state", "dz_get_trace", "dz_get_trace_chains", "dz_trace_download_begin", "dz_trace_download_wait", "dz_host_register", "dz_host_unregister", "dz_get_history", "dz_get_history_range", "dz_history_checksum",
     "dz_get_cr_state", "dz_get_gamma_state", "dz_get_rhat", "dz_get_chain_moments", "dz_eval_logp", "dz_debug_propose",
     "dz_profile_enable", "dz_profile_get", "dz_profile_reset", "dz_profile_get_list",
@@ -86,6 +86,8 @@ def load_library():
     L.dz_set_likelihood_host.argtypes = [V, LOGP_CB, V]
     L.dz_set_likelihood_module.argtypes = [V, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, V, C.c_int64]
     L.dz_set_likelihood_items.argtypes = [V, C.c_int32]
+    L.dz_set_output_module.argtypes = [V, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, V, C.c_int64]
+    L.dz_eval_outputs.argtypes = [V, V, C.c_int64, V, V]
     L.dz_comm_unique_id.argtypes = [V]
     L.dz_comm_library.restype = C.c_char_p
     L.dz_hip_library.restype = C.c_char_p
@@ -283,6 +285,24 @@ class Engine:
                                                    1 if always_finite else 0, buf, len(blob)))
         if int(items_per_point) != 1:           # (dz_set_likelihood_module itself has gone back to one item per point)
             self._chk(self.L.dz_set_likelihood_items(self.h, int(items_per_point)))
+
+    def set_output_module(self, code_object_path, kernel_name, lanes_per_point=1, items_per_point=1, doubles_per_item=1, data=None):
+        """A gfx950 code object's kernel that returns doubles_per_item values per item beside its term (include/dreamzs.h
+        dz_set_output_module): independent of the likelihood, evaluated by eval_outputs."""
+        blob = b"" if data is None else (data if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).tobytes())
+        buf = C.create_string_buffer(bytes(blob), len(blob)) if blob else None
+        self._chk(self.L.dz_set_output_module(self.h, os.fsencode(code_object_path), kernel_name.encode(), int(lanes_per_point),
+                                               int(items_per_point), int(doubles_per_item), buf, len(blob)))
+        self._out_shape = (int(items_per_point), int(doubles_per_item))
+
+    def eval_outputs(self, X):
+        """(terms [n, items_per_point], outputs [n, items_per_point, doubles_per_item]) of the rows of X from the output module's kernel,
+        as it wrote them (dz_eval_outputs: no prior, no sum over the items, no nan mapping)."""
+        X = _f64(X).reshape(-1, self.d)
+        items, per = getattr(self, "_out_shape", (1, 1))
+        terms, out = np.zeros((len(X), items)), np.zeros((len(X), items, per))
+        self._chk(self.L.dz_eval_outputs(self.h, _p(X), len(X), _p(terms), _p(out)))
+        return terms, out
 
     def set_exchange(self, fn):
         """fn(send_bytes, nbytes) -> bytes of all ranks' blocks in rank order (host-staged all-gather)."""

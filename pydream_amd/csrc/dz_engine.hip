@@ -138,6 +138,10 @@ struct dz_engine {
     int lk_items = 1; double* d_items = nullptr; size_t items_len = 0;
     // ... and, when the code object has them, the persistent kernels with that density inlined (generations_wave_body<.., UserLike>): [0] lean, [1] full proposal code
     hipFunction_t lk_gen_fn[4] = {nullptr, nullptr, nullptr, nullptr};      // ([2], [3]: 128 < d <= 256)
+    // an OUTPUT kernel beside the likelihood (dz_set_output_module / dz_eval_outputs): its own module, data block and device buffers
+    // (d_out: items x out_doubles, d_out_like: items; both grown on demand and reused)
+    hipModule_t out_module = nullptr; hipFunction_t out_fn = nullptr; void* d_out_data = nullptr; int out_lanes = 1, out_items = 1;
+    int64_t out_doubles = 0; double* d_out = nullptr; double* d_out_like = nullptr; size_t out_len = 0, out_like_len = 0;
     dz_exchange_cb xcb = nullptr; void* xcb_user = nullptr;
     ncclComm_t comm = nullptr; int rank = 0, world = 1;
     // peer transport (dz_peer_export / dz_peer_attach): the other ranks' archives, position buffers and flag words mapped into this
@@ -1568,6 +1572,10 @@ int dz_destroy(dz_engine* e)
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     if (e->lk_module) (void)hipModuleUnload(e->lk_module);
     if (e->d_lk_data) (void)hipFree(e->d_lk_data);
+    if (e->out_module) (void)hipModuleUnload(e->out_module);
+    if (e->d_out_data) (void)hipFree(e->d_out_data);
+    if (e->d_out) (void)hipFree(e->d_out);
+    if (e->d_out_like) (void)hipFree(e->d_out_like);
     for (auto& pr : e->peers) {
         if (pr.st) { (void)hipStreamSynchronize(pr.st); (void)hipStreamDestroy(pr.st); }
         if (pr.Z) (void)hipIpcCloseMemHandle(pr.Z);
@@ -1793,6 +1801,41 @@ int dz_set_likelihood_items(dz_engine* e, int32_t items_per_point)
     if (items_per_point < 1 || items_per_point > DZ_MAX_LIKELIHOOD_ITEMS)
         return fail("dz_set_likelihood_items: items_per_point must be 1.." DZ_USER_STR(DZ_MAX_LIKELIHOOD_ITEMS) " (got " + std::to_string(items_per_point) + ")");
     e->lk_items = items_per_point; e->have_logp = false;
+    return 0;
+}
+
+int dz_set_output_module(dz_engine* e, const char* code_object_path, const char* kernel_name, int32_t lanes_per_point, int32_t items_per_point,
+                         int64_t doubles_per_item, const void* data, int64_t data_bytes)
+{
+    if (!e || !code_object_path || !kernel_name) return fail("null argument");
+    if (lanes_per_point != 1 && lanes_per_point != 16 && lanes_per_point != 32 && lanes_per_point != 64)
+        return fail("dz_set_output_module: lanes_per_point must be 1 (a thread per item), 16 or 32 (a lane group per item) or 64 (a wave per item) (got " + std::to_string(lanes_per_point) + ")");
+    if (items_per_point < 1 || items_per_point > DZ_MAX_LIKELIHOOD_ITEMS)
+        return fail("dz_set_output_module: items_per_point must be 1.." DZ_USER_STR(DZ_MAX_LIKELIHOOD_ITEMS) " (got " + std::to_string(items_per_point) + ")");
+    if (doubles_per_item < 1) return fail("dz_set_output_module: doubles_per_item must be >= 1 (got " + std::to_string(doubles_per_item) + ")");
+    if (data_bytes < 0 || (data_bytes > 0 && !data)) return fail("dz_set_output_module: bad data block");
+    HIPCK(hipSetDevice(e->c.device));
+    DZCK(sync_all(e));
+    hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
+    hipError_t err = hipModuleLoad(&mod, code_object_path);
+    if (err != hipSuccess) { (void)hipGetLastError(); return fail(std::string("hipModuleLoad(") + code_object_path + "): " + hipGetErrorString(err) + " (a gfx950 code object is expected: hipcc --offload-arch=gfx950 --genco)"); }
+    err = hipModuleGetFunction(&fn, mod, kernel_name);
+    if (err != hipSuccess) { (void)hipGetLastError(); (void)hipModuleUnload(mod); return fail(std::string("hipModuleGetFunction(") + kernel_name + "): " + hipGetErrorString(err) + " (the kernel must be extern \"C\")"); }
+    void* d_new = nullptr;      // (as dz_set_likelihood_module: module, function and data change together, once every step has succeeded)
+    if (data_bytes > 0) {
+        hipError_t me = hipMalloc(&d_new, (size_t)data_bytes);
+        if (me == hipSuccess) me = hipMemcpy(d_new, data, (size_t)data_bytes, hipMemcpyHostToDevice);
+        if (me != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_new) (void)hipFree(d_new);
+            (void)hipModuleUnload(mod);
+            return fail(std::string("dz_set_output_module: data block: ") + hipGetErrorString(me));
+        }
+    }
+    if (e->out_module) (void)hipModuleUnload(e->out_module);
+    if (e->d_out_data) (void)hipFree(e->d_out_data);
+    e->d_out_data = d_new;
+    e->out_module = mod; e->out_fn = fn; e->out_lanes = lanes_per_point; e->out_items = items_per_point; e->out_doubles = doubles_per_item;
     return 0;
 }
 
@@ -2449,6 +2492,44 @@ int dz_eval_logp(dz_engine* e, const double* X, int64_t n, double* prior, double
     DZCK(sync_all(e));
     HIPCK(hipMemcpy(prior, dp, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIPCK(hipMemcpy(like, dl, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int need_doubles(double** buf, size_t* have, size_t want, const char* what)
+{
+    if (*have >= want) return 0;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    hipError_t err = hipMalloc((void**)buf, sizeof(double) * want);
+    if (err != hipSuccess) { (void)hipGetLastError(); *buf = nullptr; return fail(std::string("dz_eval_outputs: cannot allocate ") + std::to_string(want) + " doubles for " + what + ": " + hipGetErrorString(err)); }
+    *have = want;
+    return 0;
+}
+
+int dz_eval_outputs(dz_engine* e, const double* X, int64_t n, double* like_items, double* out)
+{
+    if (!e || !X || !like_items || !out) return fail("null argument");
+    if (!e->out_fn) return fail("dz_eval_outputs: call dz_set_output_module first");
+    if (n < 1) return fail("dz_eval_outputs: n must be >= 1");
+    if (n > (1 << 22)) return fail("too many points in one call");
+    HIPCK(hipSetDevice(e->c.device));
+    const unsigned per_block = 256u / (unsigned)e->out_lanes;      // the grid rules of dz_set_likelihood_module, over items
+    const long long items = (long long)n * e->out_items, blocks = (items + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffll) return fail("dz_eval_outputs: " + std::to_string(items) + " items are more than one launch's grid holds");
+    DZCK(need_scratch(e, (size_t)n));
+    DZCK(sync_all(e));
+    DZCK(need_doubles(&e->d_out, &e->out_len, (size_t)items * (size_t)e->out_doubles, "the outputs"));
+    DZCK(need_doubles(&e->d_out_like, &e->out_like_len, (size_t)items, "the terms"));
+    double* pts = e->d_scratch;
+    DZCK(upload_padded(e, pts, X, (int)n, 0.0));
+    struct { const double* X; long long n; int d; int ld; double* like; const void* data; double* out; long long out_ld; } a =
+        {pts, items, e->p.d, e->p.ld, e->d_out_like, e->d_out_data, e->d_out, (long long)e->out_doubles};
+    size_t asz = sizeof(a);
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
+    HIPCK(hipModuleLaunchKernel(e->out_fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, e->stream, nullptr, extra));
+    DZCK(sync_all(e));
+    HIPCK(hipMemcpy(like_items, e->d_out_like, sizeof(double) * (size_t)items, hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(out, e->d_out, sizeof(double) * (size_t)items * (size_t)e->out_doubles, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -903,7 +903,7 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
 
 // The entry points around a generated network struct NET: the batch kernel the engine's multi-kernel path launches (one thread per
 // point, 256 threads per block: dz_set_likelihood_module with lanes_per_point 1) and the host build's C functions.
-#if defined(__HIP__)
+#if defined(__HIP__) && !defined(DZODE_PREDICT)
 #define DZODE_ENTRIES(NET)                                                                                                              \
     extern "C" __global__ __launch_bounds__(256) void dz_ode_batch(const double* X, long long n, int d, int ld, double* like,           \
                                                                   const void* data)                                                    \
@@ -929,6 +929,46 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
         DZODE_FENCE(blk);          /* (one opaque pointer per lane: see below) */                                                        \
         like[w] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, nullptr, nullptr, w == i * C);                           \
+    }
+#elif defined(__HIP__)
+// PREDICTION (MassActionODELogLike.device().simulate): the same generated source behind a leading `#define DZODE_PREDICT 1` is a
+// translation unit of its own whose entry macros make the PREDICTION kernels instead (dz_set_output_module / dz_eval_outputs): the launch,
+// the item arithmetic and the integration of the kernels above -- the same integrate on the same shape from the same block -- with sim
+// given: item w's T * O scaled observables go to out[w * out_ld + j * O + q], what the host build's dzode_simulate writes, and its
+// term to like[w].  An item whose term is -inf leaves NaN in its whole slice (integrate breaks off in the middle of a failed run: the
+// lane that wrote the slice overwrites all of it, entries never reached included; nothing relies on the buffer having been cleared).
+namespace dzode {
+__device__ __forceinline__ void predict_finish(double term, const double* blk, int O, double* sim)
+{
+    if (term == -__builtin_huge_val()) {
+        const long long per = (long long)(int)blk[5] * O;
+        for (long long m = 0; m < per; ++m) sim[m] = __builtin_nan("");
+    }
+}
+}  // namespace dzode
+#define DZODE_ENTRIES(NET)                                                                                                              \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_predict(const double* X, long long n, int d, int ld, double* like,         \
+                                                                    const void* data, double* out, long long out_ld)                   \
+    {                                                                                                                                    \
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
+        if (i >= n) return;                                                                                                              \
+        const double v = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, (const double*)data, out + i * out_ld, nullptr);       \
+        like[i] = v;                                                                                                                     \
+        dzode::predict_finish(v, (const double*)data, NET::O, out + i * out_ld);                                                         \
+    }
+#define DZODE_ITEM_ENTRIES(NET)                                                                                                         \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_item_predict(const double* X, long long n, int d, int ld, double* like,    \
+                                                                         const void* data, double* out, long long out_ld)              \
+    {                                                                                                                                    \
+        const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
+        if (w >= n) return;                                                                                                              \
+        const double* hdr = (const double*)data;                                                                                         \
+        const long long C = (long long)hdr[0], stride = (long long)hdr[1], i = w / C;                                                    \
+        const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
+        DZODE_FENCE(blk);                                                                                                                \
+        const double v = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, out + w * out_ld, nullptr, w == i * C);           \
+        like[w] = v;                                                                                                                     \
+        dzode::predict_finish(v, blk, NET::O, out + w * out_ld);                                                                         \
     }
 #else
 #define DZODE_ENTRIES(NET)                                                                                                              \

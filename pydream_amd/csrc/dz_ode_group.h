@@ -569,7 +569,7 @@ struct HostGroup {
 // launches (dz_set_likelihood_module with lanes_per_point LANES: 256 threads per block, point i on lanes [i * LANES, (i + 1) * LANES) of
 // the grid; with 64 lanes: 4 points per block, one per wave) and the host build's C functions under dz_ode.h's names.  A group whose point index is >= n reads the last point's row,
 // takes no step and stores nothing: it stays with its wave through every cross-lane operation.
-#if defined(__HIP__)
+#if defined(__HIP__) && !defined(DZODE_PREDICT)
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
     extern "C" __global__ __launch_bounds__(256) void dz_ode_group_batch(const double* X, long long n, int d, int ld, double* like,     \
                                                                         const void* data)                                              \
@@ -605,6 +605,54 @@ struct HostGroup {
         const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, hdr + 2 + (wv - i * C) * stride, valid && good,        \
                                           nullptr, nullptr);                                                                             \
         if (valid && r == 0) like[w] = good ? dzode::add_constraints<NET>(v, x, wv == i * C) : v;                                        \
+    }
+#elif defined(__HIP__)
+// The prediction kernels (dz_ode.h, PREDICTION) of the lane group: every lane of a group holds the same o[], so lane 0 alone is given the
+// item's slice and stores each value once -- the other lanes, and the padding groups of the last block, pass sim = nullptr and store
+// nothing --, and lane 0 overwrites the slice of a failed item with NaN.  No LDS beyond the likelihood kernel's.
+#define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_group_predict(const double* X, long long n, int d, int ld, double* like,   \
+                                                                          const void* data, double* out, long long out_ld)             \
+    {                                                                                                                                    \
+        static_assert(NET::S <= LANES, "a lane per species");                                                                            \
+        __shared__ double ks[256 / LANES][dzode::group_lds_row<NET, LANES>()];                                                           \
+        const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
+        const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
+        const bool valid = i < n;                                                                                                        \
+        const double* x = X + (valid ? i : n - 1) * ld;                                                                                  \
+        const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
+        __syncthreads();                                                                                                                 \
+        double* sim = valid && r == 0 ? out + i * out_ld : nullptr;                                                                      \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, (const double*)data, valid && good, sim, nullptr);     \
+        const double term = good ? dzode::add_constraints<NET>(v, x, true) : v;                                                          \
+        if (sim) {                                                                                                                       \
+            like[i] = term;                                                                                                              \
+            dzode::predict_finish(term, (const double*)data, NET::O, sim);                                                               \
+        }                                                                                                                                \
+    }
+#define DZODE_GROUP_ITEM_ENTRIES(NET, LANES)                                                                                            \
+    extern "C" __global__ __launch_bounds__(256) void dz_ode_group_item_predict(const double* X, long long n, int d, int ld,            \
+                                                                               double* like, const void* data, double* out,            \
+                                                                               long long out_ld)                                       \
+    {                                                                                                                                    \
+        static_assert(NET::S <= LANES, "a lane per species");                                                                            \
+        __shared__ double ks[256 / LANES][dzode::group_lds_row<NET, LANES>()];                                                           \
+        const long long w = ((long long)blockIdx.x * 256 + threadIdx.x) / LANES;                                                         \
+        const int r = threadIdx.x % LANES, g = threadIdx.x / LANES;                                                                      \
+        const bool valid = w < n;                                                                                                        \
+        const double* hdr = (const double*)data;                                                                                         \
+        const long long C = (long long)hdr[0], stride = (long long)hdr[1], wv = valid ? w : n - 1, i = wv / C;                           \
+        const double* x = X + i * ld;                                                                                                    \
+        const double* blk = hdr + 2 + (wv - i * C) * stride;                                                                             \
+        const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
+        __syncthreads();                                                                                                                 \
+        double* sim = valid && r == 0 ? out + w * out_ld : nullptr;                                                                      \
+        const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, blk, valid && good, sim, nullptr);                     \
+        const double term = good ? dzode::add_constraints<NET>(v, x, wv == i * C) : v;                                                   \
+        if (sim) {                                                                                                                       \
+            like[w] = term;                                                                                                              \
+            dzode::predict_finish(term, blk, NET::O, sim);                                                                               \
+        }                                                                                                                                \
     }
 #else
 #define DZODE_GROUP_ENTRIES(NET, LANES)                                                                                                 \

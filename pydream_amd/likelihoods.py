@@ -392,7 +392,27 @@ class MassActionODELogLike:
         ("laplace") and on the log scale additionally -ln d; w is inside s.
     simulate still returns the scaled observables on the natural scale; ndim covers every index a Noise reads; noise=None and a list
     of Nones generate the source and the data block the object always had.  Not supported: Student-t residuals, a per-condition
-    noise, a sampled offset on the log scale; fixed_steps has no likelihood and ignores noise."""
+    noise, a sampled offset on the log scale; fixed_steps has no likelihood and ignores noise.
+
+    Prediction: what follows a fit -- the trajectories of the posterior's rows against the data -- runs on the device too.
+    device(device=0, max_bytes=256 << 20, chunk_items=None) returns an ODEDeviceEvaluator (a context manager; close() frees its small
+    engine) with batch(X), batch_conditions(X) and simulate(X, return_terms=False): the host methods of the same names evaluated by the
+    kernels, no prior added.  batch goes through the likelihood kernel the sampler runs (dz_eval_logp); simulate and batch_conditions
+    through the PREDICTION kernels (csrc/dz_ode.h, PREDICTION: dz_ode_predict, dz_ode_item_predict, dz_ode_group_predict,
+    dz_ode_group_item_predict), the same integration with the observables kept: predict_source() is source() behind the line
+    "#define DZODE_PREDICT 1", a translation unit of its own that is compiled on first use and cached under its own key -- a model that
+    never predicts never compiles it, and the likelihood's code object is what it was.  Results are the bits of the host methods in
+    every shape and with every feature above: simulate gives the scaled observables on the natural scale, [n, T, O] or
+    [n, C, T, O], and NaN throughout the slice of an item whose term is -inf; the terms are those of batch_conditions.  Rows are
+    processed in chunks of whole points (at least one) so that the device's output buffer stays within max_bytes, or within
+    chunk_items items.  Without a GPU device() raises DreamZSError: there is no fallback to the host build.
+    with_outputs(t, t0=None) returns a sibling object for smooth curves between the measurement times: the same network, conditions,
+    y0, events, equilibration, scale and noise, new output times, and every data entry NaN (not observed), so its batch is the
+    block's constant (0, plus the constraints' term) wherever the integration succeeds; events must lie within the new [t0, t[-1]];
+    with the object's own t it simulates to the same bits.  posterior_predictive(sampled_params, like, burnin, thin, device, t) in this
+    module selects the rows of run_dream's chains and simulates them.  Noise replicates are drawn on the host from simulate's result
+    and noise_values(rows).  Not supported on the device: trajectories of species that are not observables (declare an observable
+    with NaN data), steady_state and fixed_steps; these remain host-only."""
 
     conditions = None       # (an object pickled before the keyword existed)
     events = None           # (likewise)
@@ -764,6 +784,41 @@ class MassActionODELogLike:
             self.path = compile_device_kernel(self._unit(), extra_flags=("-I" + csrc_dir(),))
         return self.path
 
+    def predict_source(self):
+        """The prediction kernels' translation unit: source() behind the one line that switches the entry macros (csrc/dz_ode.h, PREDICTION)."""
+        return "#define DZODE_PREDICT 1\n" + self.source()
+
+    def predict_kernel(self):
+        """The name of the one kernel predict_code_object() exports."""
+        return "dz_ode%s%s_predict" % ("" if self.lanes_per_point == 1 else "_group", "" if self.conditions is None else "_item")
+
+    def predict_code_object(self):
+        """The gfx950 code object of the prediction kernel (predict_kernel()), compiled with hipcc on first use and cached under a key of
+        its own (the unit's first line differs); always from the source, also for an object made with path=."""
+        if getattr(self, "_predict_path", None) is None:
+            self._predict_path = compile_device_kernel("#define DZODE_PREDICT 1\n" + self._unit(), extra_flags=("-I" + csrc_dir(),))
+        return self._predict_path
+
+    def device(self, device=0, max_bytes=256 << 20, chunk_items=None):
+        """An ODEDeviceEvaluator of this object on GPU `device` (the class docstring, Prediction); DreamZSError without a GPU."""
+        return ODEDeviceEvaluator(self, device=device, max_bytes=max_bytes, chunk_items=chunk_items)
+
+    def with_outputs(self, t, t0=None):
+        """A sibling object with the output times t (and start time t0, default: this object's) and every data entry NaN: the same
+        network, conditions, y0, events, equilibration, scale and noise (the class docstring, Prediction)."""
+        import copy
+        new = copy.copy(self)
+        lim = self._checked_shape(self.n_species, self.lanes_per_point, len(self.reactions))[2]
+        new.t, new.t0, _ = self._checked_times(t, self.t0 if t0 is None else t0, self.observables, self.n_species, lim)
+        shape = (len(self.observables), len(new.t))
+        new.data, new.sd = np.full(shape, np.nan), np.ones(shape)
+        new.events = new._checked_events(self.events, "") or None
+        if self.conditions is not None:
+            new.conditions = [dict(cond, data=new.data, sd=new.sd, events=new._checked_events(cond["events"], "condition %d: " % c))
+                              for c, cond in enumerate(self.conditions)]
+        new.path, new._host, new._predict_path = None, None, None
+        return new
+
     def _dz_apply(self, engine):
         kernel = "dz_ode%s%s_batch" % ("" if self.lanes_per_point == 1 else "_group", "" if self.conditions is None else "_item")
         engine.set_likelihood_module(self.code_object(), kernel, self.lanes_per_point, self.data_block(), False, items_per_point=len(self._experiments()))
@@ -874,3 +929,122 @@ class MassActionODELogLike:
     def __getstate__(self):                      # (the host library is a handle of this process: loaded again on first use)
         st = dict(self.__dict__); st["_host"] = None
         return st
+
+
+class ODEDeviceEvaluator:
+    """MassActionODELogLike.device(): the object's batch, batch_conditions and simulate evaluated by the device kernels, on an arbitrary
+    batch outside the sampler (the class docstring of MassActionODELogLike, Prediction).  It owns a small engine (three chains, no prior)
+    that is made on first use and freed by close() or on leaving the `with` block; the likelihood module is set on the first batch(), the
+    output module -- and the prediction code object compiled -- on the first simulate() or batch_conditions().
+
+    Chunks: a call processes its rows in chunks of WHOLE points, so no chunk ends in the middle of a point's conditions: points per
+    chunk = max(1, chunk_items // C) when chunk_items is given, else as many as keep the output buffer (C * T * O doubles per point)
+    within max_bytes, at least one."""
+
+    def __init__(self, like, device=0, max_bytes=256 << 20, chunk_items=None):
+        if chunk_items is not None and int(chunk_items) < 1:
+            raise ValueError("ODEDeviceEvaluator: chunk_items must be >= 1")
+        if int(max_bytes) < 1:
+            raise ValueError("ODEDeviceEvaluator: max_bytes must be >= 1")
+        self.like, self.device_index, self.max_bytes = like, int(device), int(max_bytes)
+        self.chunk_items = None if chunk_items is None else int(chunk_items)
+        self._engine, self._have_like, self._have_out = None, False, False
+        self._open()                            # (no GPU, no library: DreamZSError here, not at the first call)
+
+    def _open(self):
+        if self._engine is None:
+            from . import _capi
+            self._engine = _capi.Engine(nchains=3, ndim=max(self.like.d, 1), history_capacity=8, device=self.device_index)
+            self._have_like = self._have_out = False
+        return self._engine
+
+    def close(self):
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __getstate__(self):                      # (the engine is a device handle: made again on first use)
+        st = dict(self.__dict__); st["_engine"] = None; st["_have_like"] = st["_have_out"] = False
+        return st
+
+    def _shape(self):
+        like = self.like
+        return len(like._experiments()), len(like.t) * len(like.observables)
+
+    def points_per_chunk(self):
+        """The points of one launch (whole points: see the class docstring)."""
+        C, per = self._shape()
+        items = self.chunk_items if self.chunk_items is not None else self.max_bytes // (8 * per)
+        return int(min(max(1, items // C), 1 << 22))
+
+    def _chunks(self, X):
+        """The rows as the engine takes them ([n, max(d, 1)]: the kernels read the first d coordinates), in chunks of whole points."""
+        X = self.like._rows(X)
+        d = self.like.d
+        X = np.ascontiguousarray(X[:, :d]) if d else np.zeros((len(X), 1))
+        step = self.points_per_chunk()
+        return len(X), [X[i:i + step] for i in range(0, len(X), step)]
+
+    def batch(self, X):
+        """The log-likelihoods of the rows of X by the likelihood kernel (dz_eval_logp, no prior): the bits of the host batch(X)."""
+        eng = self._open()
+        if not self._have_like:
+            self.like._dz_apply(eng)
+            self._have_like = True
+        n, chunks = self._chunks(X)
+        return np.concatenate([eng.eval_logp(c)[1] for c in chunks]) if n else np.zeros(0)
+
+    def _outputs(self, X):
+        like = self.like
+        C, per = self._shape()
+        eng = self._open()
+        if not self._have_out:
+            eng.set_output_module(like.predict_code_object(), like.predict_kernel(), like.lanes_per_point, C, per, like.data_block())
+            self._have_out = True
+        n, chunks = self._chunks(X)
+        terms, sim = np.zeros((n, C)), np.zeros((n, C, len(like.t), len(like.observables)))
+        i = 0
+        for c in chunks:
+            tc, oc = eng.eval_outputs(c)
+            terms[i:i + len(c)], sim[i:i + len(c)] = tc, oc.reshape((len(c),) + sim.shape[1:])
+            i += len(c)
+        return terms, sim
+
+    def batch_conditions(self, X):
+        """The per-condition terms of the rows of X, [n, C], by the prediction kernel: the bits of the host batch_conditions(X)."""
+        if self.like.conditions is None:
+            raise ValueError("MassActionODELogLike: batch_conditions needs an object made with conditions=[...]")
+        return self._outputs(X)[0]
+
+    def simulate(self, X, return_terms=False):
+        """The scaled observables at the output times, [n, T, O] or [n, C, T, O], NaN where the item failed, by the prediction kernel: the
+        bits of the host simulate(X).  return_terms: also the items' terms, [n] or [n, C]."""
+        terms, sim = self._outputs(X)
+        terms, sim = self.like._per_point(terms), self.like._per_point(sim)
+        return (sim, terms) if return_terms else sim
+
+
+def posterior_predictive(sampled_params, like, burnin=0, thin=1, device=True, t=None):
+    """The trajectories of a posterior sample: (rows, sim).  sampled_params: the chains run_dream returned (a sequence of [niterations, d]
+    arrays); rows: from each chain in turn the iterations burnin, burnin + thin, burnin + 2 thin, ..., stacked chain after chain;
+    sim = simulate(rows) of `like`, or with t of like.with_outputs(t) (a denser grid for smooth curves) -- on the device (device=True:
+    like.device(), or an int: that GPU) or by the host build (device=False), the same bits either way.  Noise replicates are the caller's:
+    numpy draws around sim with like.noise_values(rows)."""
+    if not _is_int(burnin, 0) or not _is_int(thin, 1):
+        raise ValueError("posterior_predictive: burnin must be an integer >= 0 and thin an integer >= 1")
+    chains = [np.asarray(c, dtype=float) for c in sampled_params]
+    if not chains or any(c.ndim != 2 or c.shape[1] != chains[0].shape[1] for c in chains):
+        raise ValueError("posterior_predictive: sampled_params must be a sequence of [niterations, d] arrays of one d")
+    rows = np.concatenate([c[int(burnin)::int(thin)] for c in chains])
+    model = like if t is None else like.with_outputs(t)
+    if device is False:
+        return rows, model.simulate(rows)
+    with model.device(device=0 if device is True else int(device)) as ev:
+        return rows, ev.simulate(rows)
