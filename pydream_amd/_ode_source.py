@@ -84,6 +84,7 @@ class _Network:
         self.S, self.reactions, self.observables, self.log10 = like.n_species, like.reactions, like.observables, like.log10
         self.mono, self.events, self.equilibrate = like._monomials(), like._max_events(), like._equilibrates()
         self.items, self.lanes, self.noise = like.conditions is not None, like.lanes_per_point, like.noise
+        self.inputs = [(u.species, u.gain) for u in like.inputs or ()]      # (species, gain): the tables are the data block's
         self.R = len(self.reactions)
         self.N = np.zeros((self.S, self.R), dtype=np.int64)
         for r, (reac, prod, _) in enumerate(self.reactions):
@@ -103,6 +104,10 @@ class _Network:
         if isinstance(c, _INT):
             return _dexp10("x[%d]" % c) if self.log10 else "x[%d]" % c, (c,)
         return _hexlit(c), ()
+
+    def input_of(self, s):
+        """the number of the input that species s carries, or None"""
+        return next((i for i, (species, _) in enumerate(self.inputs) if species == s), None)
 
     def slot_of(self, f):
         return self.slots[type(f.K), f.K, f.n]
@@ -158,6 +163,39 @@ def _slot_lines(net, first):
         L.append("        k[%d] = %s;" % (first + m, " * ".join(["K%d" % m] * n)))
         tests += _finite((), ["K%d" % m, "k[%d]" % (first + m)]) + ["k[%d] > 0.0" % (first + m)]
     return L, tests
+
+
+def _input_lines(net, first):
+    """The one-lane rates()' statements for the inputs' gains, k[first + i] = g_i (1 without a gain), and their liveness tests
+    (csrc/dz_ode.h, INPUTS)."""
+    L, tests = [], _finite(_indices_read([g for _, g in net.inputs if g is not None]))
+    for i, (_, gain) in enumerate(net.inputs):
+        L.append("        k[%d] = %s;" % (first + i, "1.0" if gain is None else net.constant(gain)[0]))
+        if gain is not None:
+            tests += _finite((), ["k[%d]" % (first + i)]) + ["k[%d] > 0.0" % (first + i)]
+    return L, tests
+
+
+def _input_members(net, drive):
+    """The members of a generated network with inputs (csrc/dz_ode.h's head, INPUTS), for the three emitters alike.  drive: the entry of
+    the point's values at which the drives begin; the gains stand in front of them."""
+    I = len(net.inputs)
+    species, scaled = "-1", "v"
+    for i in reversed(range(I)):
+        species = "i == %d ? %d : %s" % (i, net.inputs[i][0], species)
+        if net.inputs[i][1] is not None:
+            scaled = "i == %d ? k[%d] * v : %s" % (i, drive - I + i, scaled)
+    L = ["    static constexpr int INPUTS = %d, DRIVE = %d;" % (I, drive),
+         "    DZO_HD static int input_species(int i) { return %s; }" % species,
+         "    DZO_HD static double input_scaled(int i, const double* k, double v) { return %s; }" % scaled]
+    if net.lanes != 1:                      # (the group form: gain i by lane (R + SLOTS + i) % L once per point)
+        L += ["    DZO_HD static double gain(int i, const double* x, bool& good)", "    {", "        switch (i) {"]
+        for i, (_, gain) in enumerate(net.inputs):
+            if gain is not None:
+                value, idx = net.constant(gain)
+                L.append("        case %d: { const double v = %s; good = %s; return v; }" % (i, value, " && ".join(_finite(idx, ["v"]) + ["v > 0.0"])))
+        L += ["        default: good = true; return 1.0;", "        }", "    }"]
+    return L
 
 
 def _monomial_members(mono):
@@ -249,7 +287,7 @@ def _obs_lines(S, observables):
 
 def _net_source(net, body):
     """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
-    closing brace of the last one), the members of a network with monomials, the observables and the entry macro.  net.events: the
+    closing brace of the last one), the members of a network with inputs (net.drive: where the emitter put their drives), of one with monomials, the observables and the entry macro.  net.events: the
     largest event count over the object's experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  net.equilibrate: some
     experiment equilibrates first; the member EQUILIBRATE only then."""
     if net.lanes == 1:
@@ -259,6 +297,7 @@ def _net_source(net, body):
     L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (net.S, net.R, len(net.observables))]
     L += ["    static constexpr int EVENTS = %d;" % net.events] if net.events else []
     L += ["    static constexpr bool EQUILIBRATE = true;"] if net.equilibrate else []
+    L += _input_members(net, net.drive) if net.inputs else []
     L += body + (_monomial_members(net.mono) if net.mono else []) + (_noise_members(net) if net.noise else [])
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(net.S, net.observables) + ["    }", "};", entries, ""]
     return '#include "%s"\n' % header + "\n".join(L)
@@ -281,6 +320,8 @@ def _ode_long_source(net):
     kname = ["k[%d]" % used.index(rate) if isinstance(rate, _INT + (Monomial,)) else _hexlit(rate) for rate in net.rates]
     v, dv = net.rate_code(kname, len(used))
     slot_lines, slot_tests = _slot_lines(net, len(used))    # (then the Hill slots: k[len(used) + m] = Kn)
+    gain_lines, gain_tests = _input_lines(net, len(used) + len(net.slots))     # (then the inputs' gains and, behind them, their drives)
+    net.drive = len(used) + len(net.slots) + len(net.inputs)
     started = set()
 
     def add(target, c, e):
@@ -293,8 +334,8 @@ def _ode_long_source(net):
     L = ["    static constexpr int SLOTS = %d;" % len(net.slots)] if net.slots else []
     L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     L += ["        k[%d] = %s;" % (i, net.constant(p)[0]) for i, p in enumerate(used)]
-    L += slot_lines
-    L.append("        return %s;" % (" && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % i for i in range(len(used))]) + slot_tests) or "true"))
+    L += slot_lines + gain_lines
+    L.append("        return %s;" % (" && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % i for i in range(len(used))]) + slot_tests + gain_tests) or "true"))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     for r in range(net.R):
         rows = [s for s in range(S) if N[s, r] != 0]
@@ -303,7 +344,8 @@ def _ode_long_source(net):
         L.append("        const double v%d = %s;" % (r, v(r)))
         L += [add("f[%d]" % s, int(N[s, r]), "v%d" % r) for s in rows]
         L.append("        " + " ".join("DZODE_FENCE(f[%d]);" % s for s in rows))
-    L += ["        f[%d] = 0.0;" % s for s in range(S) if "f[%d]" % s not in started]
+    # (a species no reaction changes: 0, or for an input species its drive)
+    L += ["        f[%d] = %s;" % (s, "0.0" if net.input_of(s) is None else "k[%d]" % (net.drive + net.input_of(s))) for s in range(S) if "f[%d]" % s not in started]
     L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
     for r in range(net.R):                              # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: rate_code's dv)
         rows = [s for s in range(S) if N[s, r] != 0]
@@ -325,14 +367,19 @@ def _ode_source(net):
         return _ode_long_source(net)
     v, dv = net.rate_code(["k[%d]" % r for r in range(R)], R)
     slot_lines, slot_tests = _slot_lines(net, R)        # (the Hill slots behind the rate constants: k[R + m] = Kn)
+    gain_lines, gain_tests = _input_lines(net, R + len(net.slots))      # (then the inputs' gains and, behind them, their drives)
+    net.drive = R + len(net.slots) + len(net.inputs)
     L = ["    static constexpr int SLOTS = %d;" % len(net.slots)] if net.slots else []
     L += ["    DZO_HD static bool rates(const double* x, double* k)", "    {"]
     L += ["        k[%d] = %s;" % (r, net.constant(rate)[0]) for r, rate in enumerate(net.rates)]
-    L += slot_lines                             # (10**-inf is a finite 0: test x itself)
-    L.append("        return %s;" % " && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % r for r in range(R)]) + slot_tests))
+    L += slot_lines + gain_lines                # (10**-inf is a finite 0: test x itself)
+    L.append("        return %s;" % " && ".join(_finite(_rate_indices(net.reactions), ["k[%d]" % r for r in range(R)]) + slot_tests + gain_tests))
     L += ["    }", "    DZO_HD static void rhs(const double* k, const double* y, double* f)", "    {"]
     L += ["        const double v%d = %s;" % (r, v(r)) for r in range(R)]
     for s in range(S):
+        if net.input_of(s) is not None:                 # (an input species: its drive; nothing produces or consumes it)
+            L.append("        f[%d] = k[%d];" % (s, net.drive + net.input_of(s)))
+            continue
         L.append("        f[%d] = %s;" % (s, _combine([(int(N[s, r]), "v%d" % r) for r in range(R) if N[s, r] != 0])))
     L += ["    }", "    DZO_HD static void jac(const double* k, const double* y, double* J)", "    {"]
     for r in range(R):                                  # dv_r / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu (a RateLaw: rate_code's dv)
@@ -370,6 +417,7 @@ def _ode_group_source(net):
 
     # (the Hill slots behind the rate constants: k[R + m] = Kn, by lane (R + m) % L once per point)
     v, dv = net.rate_code(["k[z + %d]" % j for j in range(R)], R)
+    net.drive = R + len(net.slots) + len(net.inputs)    # (behind the slots the inputs' gains, then their drives: csrc/dz_ode_group.h)
     sampled = _INT + (Monomial,)
     L = ["    static constexpr bool LOG10 = %s;" % ("true" if net.log10 else "false"),
          "    DZO_HD static int rate_index(int j)", "    {", "        switch (j) {"]
@@ -392,7 +440,13 @@ def _ode_group_source(net):
                 L.append("        case %d: { const double v = %s; good = %s; return v; }" % (j, kv, " && ".join(_finite(idx, ["v"]))))
         L += ["        default: good = false; return 0.0;", "        }", "    }"]
     L += ["    DZO_HD static double rhs_row(int r, const double* k, const double* y)", "    {"]
-    L += weighted_sum([(j, v(j)) for j in range(R) if np.any(N[:, j] != 0)], "        ")
+    row = weighted_sum([(j, v(j)) for j in range(R) if np.any(N[:, j] != 0)], "        ")
+    if net.inputs:                                       # (an input's row: a select onto its drive, branch-free on the row)
+        value = row.pop().strip()[len("return "):-1]
+        for i, (s, _) in enumerate(net.inputs):
+            value = "r == %d ? k[%d] : %s" % (s, net.drive + i, value)
+        row.append("        return %s;" % value)
+    L += row
     L += ["    }", "    DZO_HD static double jac_entry(int r, int q, const double* k, const double* y)", "    {", "        switch (q) {"]
     for q in range(S):                                   # dv_j / dy_q = k nu_q y_q^(nu_q - 1) prod_others y^nu
         terms = [(j, dv(j, q)) for j in range(R) if q in net.kinetic[j] and np.any(N[:, j] != 0)]

@@ -1,5 +1,5 @@
 """The limits of pydream_amd.likelihoods.MassActionODELogLike, the predicates its checks are made of, and the immutable values a network
-is written with: Monomial, Hill, RateLaw, Noise."""
+is written with: Monomial, Hill, RateLaw, Noise, Input."""
 import numpy as np
 
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
@@ -11,6 +11,8 @@ ODE_EQUILIBRATE_MAX_STEPS = 2000    # equilibrate=...: the attempted steps of th
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated products
 ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction
+ODE_MAX_INPUTS = 4          # inputs=[Input, ...]: piecewise-linear time courses, each on a species of its own
+ODE_MAX_INPUT_KNOTS = 128   # the working knots of one experiment, over all its inputs together (csrc/dz_ode.h: MAX_INPUT_KNOTS)
 _INT = (int, np.integer)
 _REAL = (int, np.integer, float, np.floating)
 
@@ -239,3 +241,67 @@ class Noise:
 
     def __repr__(self):
         return "Noise(%r, %r, %r, %r)" % (self.sigma, self.rel, self.dist, self.scale)
+
+
+class Input:
+    """A measured or prescribed time course that drives the network, for MassActionODELogLike(inputs=[...]): the amount of `species` is
+    gain * u(t), u the piecewise-linear curve through (times[k], values[k]).  species: the species' index -- nothing may produce or
+    consume it; times: at least 2, finite and strictly increasing; values: one per time, finite and >= 0; gain: None, a finite float
+    > 0, a parameter index (10**x[i] under rate_scale "log10", x[i] under "linear") or a Monomial: a sampled amplitude.  An immutable
+    value: `times` and `values` are tuples of floats."""
+    __slots__ = ("species", "times", "values", "gain")
+
+    def __init__(self, species, times, values, gain=None):
+        if not _is_int(species, 0):
+            raise ValueError("MassActionODELogLike: an Input's species must be a non-negative integer (got %r)" % (species,))
+        try:
+            times, values = [float(v) for v in np.asarray(times, dtype=float).reshape(-1)], [float(v) for v in np.asarray(values, dtype=float).reshape(-1)]
+        except (TypeError, ValueError):
+            raise ValueError("MassActionODELogLike: an Input's times and values must be sequences of numbers")
+        if len(times) < 2 or not np.all(np.isfinite(times)) or np.any(np.diff(times) <= 0):
+            raise ValueError("MassActionODELogLike: an Input's times must be at least 2 finite, strictly increasing numbers (got %r)" % (times,))
+        if len(values) != len(times) or not np.all(np.isfinite(values)) or np.any(np.asarray(values) < 0):
+            raise ValueError("MassActionODELogLike: an Input's values must be finite and >= 0, one per time (got %r for %d times)" % (values, len(times)))
+        if gain is not None:
+            gain = _checked_constant(gain, "an Input's gain")
+            if isinstance(gain, float) and not (np.isfinite(gain) and gain > 0):
+                raise ValueError("MassActionODELogLike: an Input's fixed gain must be finite and > 0 (got %r)" % (gain,))
+        for name, v in zip(self.__slots__, (int(species), tuple(times), tuple(values), gain)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("an Input is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("an Input is immutable")
+
+    def interp(self, t):
+        """u(t) in numpy, without the gain (a time outside the table: the nearest end's value)"""
+        return np.interp(t, self.times, self.values)
+
+    def working_knots(self, t0, t_end):
+        """The knots the solver applies between t0 and t_end (csrc/dz_ode.h, INPUTS), as (time, value, slope) in ascending time: one at
+        t0 -- the table's value there, v_k + (t0 - tau_k) * s_k in the segment that holds t0, or the table value itself where t0 is a
+        table time -- with that segment's slope, then the table's knots strictly inside (t0, t_end), each with its value and the slope
+        of the segment that follows.  The table must cover [t0, t_end]."""
+        tau, v = self.times, self.values
+        slope = [(v[k + 1] - v[k]) / (tau[k + 1] - tau[k]) for k in range(len(tau) - 1)]
+        k = max(j for j in range(len(tau) - 1) if tau[j] <= t0) if t0 < tau[-1] else len(tau) - 2
+        first = v[k] if t0 == tau[k] else v[k + 1] if t0 == tau[k + 1] else v[k] + (t0 - tau[k]) * slope[k]
+        out = [(float(t0), first, slope[k] if t0 < tau[-1] else 0.0)]
+        return out + [(tau[j], v[j], slope[j]) for j in range(1, len(tau) - 1) if t0 < tau[j] < t_end]
+
+    def _key(self):
+        return (self.species, self.times, self.values, type(self.gain).__name__, self.gain)
+
+    def __eq__(self, other):
+        return isinstance(other, Input) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return Input, (self.species, self.times, self.values, self.gain)
+
+    def __repr__(self):
+        return "Input(%r, %r, %r, %r)" % (self.species, list(self.times), list(self.values), self.gain)

@@ -143,6 +143,48 @@
 //                                                                      false: a failed integration
 // and a network without one generates the source, and the data block, it always did.
 //
+// INPUTS (likelihoods.Input, MassActionODELogLike(inputs=...)): a measured or prescribed time course u_i(t), piecewise linear, that drives
+// the network as one more species.  Nothing produces or consumes an input species; reactions may read it as a catalyst, a kinetic order
+// or the species of a Hill factor.  Its right-hand side is the current segment's slope, its Jacobian row is zero, and its value is set
+// exactly at every knot, so the system stays autonomous: Rodas4's coefficients and the clock-free equilibration phase remain correct.
+// A network with I = 1..4 inputs carries
+//     static constexpr int INPUTS = I;
+//     static constexpr int DRIVE = D;                                  entry D + i of the point's values k is input i's DRIVE, entry
+//                                                                      D - I + i its GAIN g_i (1 without one); D: behind rates and slots
+//     static int input_species(int i);                                 the species input i is carried by (a select, no branch on i)
+//     static double input_scaled(int i, const double* k, double v);    g_i * v, one product; v itself for an input without a gain
+//     static double gain(int i, const double* x, bool& good);          (the group form; the one-lane rates() fills the gains itself)
+// and each experiment's block (each sub-block, with conditions) grows at its very end -- after the equilibration's six doubles, the
+// event records, or sd, whichever is last -- by
+//     K_c, this experiment's count of working knots (I..Kmax),   then Kmax records (time, input, value, slope), sorted by time and at
+//     one time by input, padded with zeros
+// so that the conditions' stride stays uniform; Kmax <= 128 over all inputs of an experiment together.  The working knots are made in
+// Python, once: for every input one knot at t0 (the table's value there and the slope of the segment that holds t0), then the table's
+// knots strictly inside (t0, t[T-1]), each with its value and the slope of the segment that follows.  The block of a network without
+// inputs is what it always was.  The semantics, the same in both builds and every shape:
+//   * THE GAIN g_i (a parameter under rate_scale, a fixed number or a monomial) is evaluated once per point, when the rate constants
+//     are, with a rate constant's arithmetic.  A point is not live (-inf) if a coordinate that a gain reads is not finite, or g_i is not
+//     finite or not > 0.
+//   * A DUE KNOT (time, i, v, s) sets y[species_i] = g_i * v -- one product; without a gain v itself, so a gain that is exactly 1 gives
+//     the bits of no gain -- which removes accumulated rounding, and sets the drive to g_i * s, one product, computed when the knot is
+//     applied and not per stage.  The input's right-hand side is exactly that drive.  Inputs at one time apply in ascending index.
+//   * KNOTS ARE BREAKPOINTS beside t0, the event times and the output times: a step is clipped to land exactly on a knot.  The
+//     controller is NOT restarted there: a clipped step leaves its size alone, exactly as at an output time.  max_steps counts per
+//     segment.
+//   * AT A TIME tau the order is: an output at tau first (measure, then intervene), then the knots due at tau, then the events due at
+//     tau in the order given.  The knots at t0 are part of the start, like the events at t0: applied before the start step and before an
+//     output at t0.
+//   * THE START: the block's y0 entry of an input species is 0.  Ahead of an equilibration phase every input is HELD at its value at
+//     t0 with drive 0 -- the knots at t0 applied with slope 0 --, and the phase runs in that state: the resting state under the basal
+//     input.  Then, with or without the phase, the knots at t0 are applied as they are, which installs the first slopes before the
+//     events at t0 and the start step.
+//   * The drive is per-experiment state, not a rate constant: with conditions on the host the point's rate constants and gains are
+//     computed once and every condition starts by holding its inputs.  The one-lane shape keeps the drives in registers beside k; the
+//     lane group and the wave keep gains and drives in 2 I more doubles of the point's LDS row (dz_ode_group.h).
+//   * Knot times come from the block, so control flow stays uniform within a lane group.  integrate_fixed ignores inputs (every drive
+//     0, the input species at the block's 0), as it ignores events.
+// Every loop stays bounded: at most T + Emax + Kmax segments.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -267,8 +309,21 @@ template <class Net> struct has_slots<Net, decltype((void)Net::SLOTS)> {
     static constexpr int count = Net::SLOTS;
     static_assert(Net::SLOTS >= 1 && Net::R + Net::SLOTS <= 256, "reactions plus slots within the shape's reaction limit");
 };
-// the doubles of a point's rate constants and slots (an array of at least one)
-template <class Net> constexpr int rate_doubles() { return Net::R + has_slots<Net>::count > 0 ? Net::R + has_slots<Net>::count : 1; }
+// ... and inputs (the head of the file, INPUTS): I piecewise-linear time courses, each a species of its own; their gains and drives
+// are 2 I doubles behind the rate constants and slots
+constexpr int MAX_INPUT_KNOTS = 128;
+template <class Net, class = void> struct has_inputs { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_inputs<Net, decltype((void)Net::INPUTS)> {
+    static constexpr bool value = true;
+    static constexpr int count = Net::INPUTS;
+    static_assert(Net::INPUTS >= 1 && Net::INPUTS <= 4 && Net::DRIVE >= Net::INPUTS, "1..4 inputs, their gains in front of their drives");
+};
+// the doubles of a point's rate constants and slots (an array of at least one; with inputs: and their gains and drives)
+template <class Net> constexpr int rate_doubles()
+{
+    if constexpr (has_inputs<Net>::value) return Net::DRIVE + Net::INPUTS;
+    else return Net::R + has_slots<Net>::count > 0 ? Net::R + has_slots<Net>::count : 1;
+}
 
 // ... and sampled noise (the head of the file, NOISE): 2 O per-point values, a_q and b_q
 template <class Net, class = void> struct has_noise { static constexpr bool value = false; static constexpr int count = 0; };
@@ -290,6 +345,17 @@ DZO_HD bool noise_point(const double* x, double* nz)
         }
     }
     return good;
+}
+
+// The drives of a point's inputs set to 0: the array shapes' knot reads the entries it does not write (a select over the unrolled
+// index), so they hold a number before the first knot.
+template <class Net>
+DZO_HD void clear_drives(double* k)
+{
+    if constexpr (has_inputs<Net>::value) {
+#pragma unroll
+        for (int m = 0; m < Net::INPUTS; ++m) k[Net::DRIVE + m] = 0.0;
+    }
 }
 
 template <class Net>
@@ -515,17 +581,62 @@ DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h
 //     Shape::EVENTS, sh.apply(y, species, factor, amount)   (a network with events: Emax, and y[species] = factor * y[species] + amount)
 //     Shape::EQUILIBRATE, sh.drift2(y, rtol, atol)     (a network that equilibrates: the steady-state test's wnorm2(f(y), y, rtol, atol))
 //     Shape::Net, sh.noise()                           (a network with sampled noise: where the point's 2 O noise values are)
+//     Shape::INPUTS, sh.knot(y, i, value, slope)       (a network with inputs: I, and y[species_i] = g_i * value, drive_i = g_i * slope)
 // and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
 // Group<Net, L> (dz_ode_group.h: a group of L lanes per point, and its host twin).  A point that is not live keeps h = 0, ok = false and
 // takes no step, but does not return ahead of the loop: the lanes of a group stay with their wave.
 // With events (the head of the file) every pass of the outer loop is one SEGMENT: the events that are due and the controller's (re)start
 // -- the start at t0 is the first of them, so the start step exists once in the code --, the steps up to the next breakpoint, and the
-// output if the breakpoint is one.  Without events a pass is an output interval, as it always was.
+// output if the breakpoint is one.  A network with inputs (the head of the file, INPUTS) runs in segments too, whether or not it has
+// events: the knots at t0 are applied ahead of the loop -- and, without events, the start step computed there as it always was: a
+// start step inside the loop is a second copy of the right-hand side in it; with it, and with the records' address and count carried
+// through the loop, enzyme13 + input @ 16 took 268 registers and, past 256, ran with half its waves: 1.9 times the time --, and a pass first applies the knots that are due, which does not restart the controller.  Without events
+// and inputs a pass is an output interval, as it always was.
 // The equilibration phase (the head of the file) of one experiment: y from the experiment's start amounts to the resting state, by the
 // steps and the controller of integrate without a clock and without an end time.  ok in: the point is live; out: the state is steady
 // (or the experiment does not equilibrate).  nsteps grows by the accepted steps; attempts (optional): the attempted ones.  The loop is
 // bounded by the block's max_steps_ss; `on`, the tolerances and the limits come from the block and the test's result is one value per
 // lane group, so control flow stays uniform within a group.
+// The knot count of one experiment's block (blk: the experiment's block); behind it the records (time, input, value, slope).
+template <class Shape>
+DZO_HD const double* input_knots(const double* blk)
+{
+    const long long per = (long long)(int)blk[5] * Shape::O;
+    return blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0) + (Shape::EQUILIBRATE ? 6 : 0);
+}
+
+// The start of an experiment of a network with inputs: every input held at its value at t0 with drive 0 (the knots at t0 with slope 0).
+template <class Shape>
+DZO_HD void hold_inputs(const Shape& sh, const double* blk, typename Shape::State& y)
+{
+    if constexpr (Shape::INPUTS > 0) {
+        const double* inp = input_knots<Shape>(blk);
+        const int K = (int)dmin(inp[0], (double)MAX_INPUT_KNOTS);
+#pragma unroll 1
+        for (int kn = 0; kn < K && inp[1 + 4 * kn] <= blk[4]; ++kn) sh.knot(y, (int)inp[2 + 4 * kn], inp[3 + 4 * kn], 0.0);
+    }
+}
+
+// The knots from the cursor kn on that are due at time t, applied in the block's order; the new cursor.  (The records' address and
+// the count are formed from the block where they are needed and not carried through the step loop: registers.)
+template <class Shape>
+DZO_HD int due_knots(const Shape& sh, const double* blk, typename Shape::State& y, int kn, double t)
+{
+    const double* inp = input_knots<Shape>(blk);
+    const int K = (int)dmin(inp[0], (double)MAX_INPUT_KNOTS);
+#pragma unroll 1
+    for (; kn < K && inp[1 + 4 * kn] <= t; ++kn) sh.knot(y, (int)inp[2 + 4 * kn], inp[3 + 4 * kn], inp[4 + 4 * kn]);
+    return kn;
+}
+
+// The time of the knot at the cursor, +inf past the last.
+template <class Shape>
+DZO_HD double next_knot(const double* blk, int kn)
+{
+    const double* inp = input_knots<Shape>(blk);
+    return kn < (int)dmin(inp[0], (double)MAX_INPUT_KNOTS) ? inp[1 + 4 * kn] : __builtin_huge_val();
+}
+
 template <class Shape>
 DZO_HD bool equilibrate(const Shape& sh, const double* blk, typename Shape::State& y, bool ok, int& nsteps, int* attempts)
 {
@@ -577,12 +688,16 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     typename Shape::State y, yn;
     double o[O];
     sh.init(blk, y);
+    if constexpr (Shape::EQUILIBRATE) hold_inputs(sh, blk, y);              // (a network with inputs: the phase sees them held at u(t0), every drive 0)
     double t = t0, acc = 0.0;
-    constexpr int EV = Shape::EVENTS;
+    constexpr int EV = Shape::EVENTS, IN = Shape::INPUTS;
+    constexpr bool SEG = EV > 0 || IN > 0;                                   // the loop's passes are segments between breakpoints
     double h = 0.0;
     bool ok = live, rejected = false;
     int nsteps = 0;
     if constexpr (Shape::EQUILIBRATE) ok = equilibrate(sh, blk, y, ok, nsteps, nullptr);      // y: the resting state, the experiment's start
+    [[maybe_unused]] int kn = 0;                                             // the knot cursor
+    if constexpr (IN > 0) kn = due_knots(sh, blk, y, kn, t0);               // the knots at t0 are part of the start: the first slopes
     if constexpr (EV == 0) {
         h = ok ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
         ok = ok && finite(h) && h > 0.0;
@@ -595,6 +710,7 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     for (int j = 0; ok && j < T;) {
         const double tout = tt[j];
         double tend = tout;                                                  // the segment's end
+        if constexpr (IN > 0) kn = due_knots(sh, blk, y, kn, t);             // the knots that are due: the value exactly, the next slope
         if constexpr (EV > 0) {
 #pragma unroll 1
             for (; ev < E && evt[4 * ev] <= t; ++ev) {                       // the events that are due, in the order given
@@ -609,6 +725,7 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             }
             if (ev < E && evt[4 * ev] < tout) tend = evt[4 * ev];            // (an event at tout: after the output, in the next pass)
         }
+        if constexpr (IN > 0) tend = dmin(tend, next_knot<Shape>(blk, kn));  // (a knot at tout: after the output; the controller is not restarted)
         for (int n = 0; t < tend; ++n) {
             const bool clip = t + h >= tend;
             const double hs = clip ? tend - t : h;
@@ -634,8 +751,8 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             }
         }
         if (!ok) break;
-        if constexpr (EV > 0) {
-            if (tend < tout) continue;                                       // landed on an event, not on the output time
+        if constexpr (SEG) {
+            if (tend < tout) continue;                                       // landed on an event or a knot, not on the output time
         }
         sh.observe(y, o);
         if constexpr (has_noise<typename Shape::Net>::value) {               // (the head of the file, NOISE: the network's own terms)
@@ -694,6 +811,7 @@ DZO_HD double start_step(const double* k, const double* y, double rtol, double a
 template <class Alg>
 struct Array {
     static constexpr int S = Alg::Net::S, O = Alg::Net::O, EVENTS = has_events<typename Alg::Net>::count;
+    static constexpr int INPUTS = has_inputs<typename Alg::Net>::count;
     static constexpr bool EQUILIBRATE = has_equilibrate<typename Alg::Net>::value;
     typedef typename Alg::Net Net;
     struct State { double v[S]; };
@@ -737,6 +855,20 @@ struct Array {
 #pragma unroll
         for (int s = 0; s < S; ++s) y.v[s] = s == species ? factor * y.v[s] + amount : y.v[s];
     }
+    // A knot of input i: the value into its species, the slope into its drive -- entry DRIVE + i of the caller's own array k, which is
+    // per-experiment state and not constant (selects over the unrolled s and m: y and k stay in registers)
+    DZO_HD void knot(State& y, int i, double value, double slope) const
+    {
+        if constexpr (INPUTS > 0) {
+            double* drive = const_cast<double*>(k) + Net::DRIVE;
+            const int species = Net::input_species(i);
+            const double gv = Net::input_scaled(i, k, value), gs = Net::input_scaled(i, k, slope);
+#pragma unroll
+            for (int s = 0; s < S; ++s) y.v[s] = s == species ? gv : y.v[s];
+#pragma unroll
+            for (int m = 0; m < INPUTS; ++m) drive[m] = m == i ? gs : drive[m];
+        }
+    }
 };
 
 // One point through an array shape.  The rate constants are tested here, ahead of the loop, and the loop runs with live a constant.
@@ -748,6 +880,7 @@ DZO_HD double integrate_point(const double* x, const double* blk, double* sim, i
     [[maybe_unused]] double nz[noise_doubles<typename Alg::Net>()];
     if (nsteps_out) *nsteps_out = 0;
     if (!Alg::rates(x, k)) return -__builtin_huge_val();
+    clear_drives<typename Alg::Net>(k);
     if constexpr (has_noise<typename Alg::Net>::value) {
         if (!noise_point<typename Alg::Net>(x, nz)) return -__builtin_huge_val();
         return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x, nz}, blk, true, sim, nsteps_out), x, first);
@@ -767,9 +900,11 @@ DZO_HD void equilibrate_point(const double* x, const double* blk, double* yss, i
     const Array<Alg> sh{k, x};
     typename Array<Alg>::State y;
     bool ok = Alg::rates(x, k);
+    clear_drives<typename Alg::Net>(k);
     *attempts = 0;
     if (ok) {
         sh.init(blk, y);
+        hold_inputs(sh, blk, y);
         if constexpr (Array<Alg>::EQUILIBRATE) {
             int steps = 0;
             ok = equilibrate(sh, blk, y, ok, steps, attempts);
@@ -807,6 +942,7 @@ DZO_HD double integrate_conditions(const double* x, const double* hdr, double* t
     double k[rate_doubles<typename Alg::Net>()];
     double nz[noise_doubles<typename Alg::Net>()];
     const bool rated = Alg::rates(x, k);
+    clear_drives<typename Alg::Net>(k);
     const bool live = noise_point<typename Alg::Net>(x, nz) && rated;
     double total = 0.0;
     int steps = 0;
@@ -830,6 +966,7 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     constexpr int S = Alg::Net::S;
     double k[rate_doubles<typename Alg::Net>()], yn[S], ye[S];
     if (!Alg::rates(x, k)) return false;
+    clear_drives<typename Alg::Net>(k);                                      // (inputs are ignored: every drive 0)
 #pragma unroll
     for (int s = 0; s < S; ++s) y[s] = start_amount<typename Alg::Net>(s, x, blk[6 + s]);
     const double h = (t1 - blk[4]) / nsteps;

@@ -44,8 +44,13 @@
 // and, for a network with sampled noise (dz_ode.h's head, NOISE: the members NOISE, noise_value and noise_terms), the point's 2 O noise
 // values at the very end of its LDS row (noise_row), value m evaluated by lane m % L when the rate constants are; the host twin takes
 // them from dz_ode.h's noise_point, the same generated function value by value.
+// and, for a network with inputs (dz_ode.h's head, INPUTS: the members INPUTS, DRIVE = R + SLOTS + I, input_species, input_scaled and
+//     static double gain(int i, const double* x, bool& good);         g_i and its liveness (an input without a gain: 1)
+// ), 2 I more doubles of the point's LDS row right behind the rate constants and slots: entry R + SLOTS + i is the gain g_i, evaluated by
+// lane (R + SLOTS + i) % L when the rate constants are, entry DRIVE + i the drive, which one lane of the group writes when a knot is
+// applied (Group::knot) and the generated rhs_row of the input's row selects; the host twin keeps the same 2 I entries in its array k.
 // Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd; with the
-// equilibration phase: its six doubles at the end.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
+// equilibration phase: its six doubles at the end; with inputs: the knot records behind those.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
 // the group's norm, a group-wide value).
 #pragma once
 #include "dz_ode.h"
@@ -89,6 +94,11 @@ DZO_HD double stage_add(int st, double ih, double k1, double k2, double k3, doub
     }
 }
 
+// The doubles at the head of a point's row of values: rate constants, Hill slots and, with inputs, their gains and drives.
+template <class Net> constexpr int ROW_VALUES = Net::R + has_slots<Net>::count + 2 * has_inputs<Net>::count;
+// ... of which the first are evaluated once per point (the drives are per-experiment state, written when a knot is applied)
+template <class Net> constexpr int ROW_CONSTANTS = Net::R + has_slots<Net>::count + has_inputs<Net>::count;
+
 DZO_HD double pivot_key(double a)          // |a|, a NaN as +inf: the arg-max is then over a total order
 {
     const double v = dabs(a);
@@ -98,6 +108,9 @@ DZO_HD double pivot_key(double a)          // |a|, a NaN as +inf: the arg-max is
 template <class Net>
 DZO_HD double rate_constant(int j, const double* x, bool& good)
 {
+    if constexpr (has_inputs<Net>::value) {     // (entry R + SLOTS + i of the row: the gain of input i, dz_ode.h's INPUTS)
+        if (j >= Net::R + has_slots<Net>::count) return Net::gain(j - Net::R - has_slots<Net>::count, x, good);
+    }
     if constexpr (has_slots<Net>::value) {      // (entry R + m of the row: the Hill slot m, dz_ode.h's RATE LAWS)
         if (j >= Net::R) return Net::slot(j - Net::R, x, good);
     }
@@ -185,9 +198,9 @@ __device__ __forceinline__ int uniform_index(int v)
     return v;
 }
 
-// The wave's copy of the state in LDS, behind its R + 1 rate constants (a network with rate laws: R + SLOTS + 1).
+// The wave's copy of the state in LDS, behind its R + 1 rate constants (a network with rate laws: R + SLOTS + 1; with inputs: + 2 I).
 template <class Net>
-__device__ __forceinline__ double* wave_state(double* ks) { return ks + Net::R + has_slots<Net>::count + 1; }
+__device__ __forceinline__ double* wave_state(double* ks) { return ks + ROW_VALUES<Net> + 1; }
 
 // Lane r's entry into the wave's copy.  The fences keep the compiler from moving the reads of the previous copy below the write and the
 // reads of this copy above it; the hardware executes one wave's LDS operations in order.
@@ -226,13 +239,13 @@ struct Replica<Net, 64> {                     // a wave: its S doubles of LDS; a
 
 // The point's noise values in its row of LDS: behind the rate constants, the slots and (64 lanes) the wave's state.
 template <class Net, int L>
-__device__ __forceinline__ double* noise_row(double* ks) { return ks + Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0); }
+__device__ __forceinline__ double* noise_row(double* ks) { return ks + ROW_VALUES<Net> + 1 + (L == 64 ? Net::S : 0); }
 
 template <class Net, int L>
 __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
 {
     bool good = true;
-    for (int j = r; j < Net::R + has_slots<Net>::count; j += L) {
+    for (int j = r; j < ROW_CONSTANTS<Net>; j += L) {
         bool g;
         ks[j] = rate_constant<Net>(j, x, g);
         good = good && g;
@@ -393,7 +406,7 @@ __device__ __forceinline__ double group_start_step(double* ks, double y, double 
 template <class NET, int L>
 struct Group {
     typedef NET Net;
-    static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count;
+    static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count, INPUTS = has_inputs<Net>::count;
     static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
     typedef double State;
     double* ks;                                        // the point's row of LDS: its rate constants (64 lanes: and its state behind them)
@@ -430,12 +443,28 @@ struct Group {
     {
         y = r == species ? factor * y + amount : y;
     }
+    // A knot of input i (dz_ode.h's INPUTS): the value into the lane that holds its species, the slope into its drive in the point's
+    // row of LDS.  One lane of the group writes the drive, between the fence and wave_barrier that wave_publish uses: only the point's
+    // own wave reads it, in the right-hand sides that follow, and the hardware executes one wave's LDS operations in order.  No block
+    // barrier: the groups of a block take their knots at different times.
+    __device__ __forceinline__ void knot(double& y, int i, double value, double slope) const
+    {
+        if constexpr (INPUTS > 0) {
+            const double gv = Net::input_scaled(i, ks, value), gs = Net::input_scaled(i, ks, slope);
+            y = r == Net::input_species(i) ? gv : y;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (r == 0) ks[Net::DRIVE + i] = gs;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
 };
 
 // The doubles of static LDS a point's lanes share: R + 1 rate constants (with rate laws: R + SLOTS + 1, the Hill slots behind the rate
-// constants), for a wave per point the S doubles of its state behind them, and for a network with sampled noise its 2 O values last.
+// constants; with inputs: 2 I more, their gains and drives behind those), for a wave per point the S doubles of its state behind them, and for a network with sampled noise its 2 O values last.
 template <class Net, int L>
-constexpr int group_lds_row() { return Net::R + has_slots<Net>::count + 1 + (L == 64 ? Net::S : 0) + has_noise<Net>::count; }
+constexpr int group_lds_row() { return ROW_VALUES<Net> + 1 + (L == 64 ? Net::S : 0) + has_noise<Net>::count; }
 #endif
 
 #if !defined(__HIP__)
@@ -456,7 +485,7 @@ struct HostGroup {
     static bool rates(const double* x, double* k)
     {
         bool good = true;
-        for (int j = 0; j < R + has_slots<Net>::count; ++j) {
+        for (int j = 0; j < ROW_CONSTANTS<Net>; ++j) {
             bool g;
             k[j] = rate_constant<Net>(j, x, g);
             good = good && g;

@@ -10,8 +10,8 @@ from . import _kernel_cache, _ode_source      # noqa: F401
 from ._kernel_cache import _build_cached, _compiler_version, compile_device_kernel, csrc_dir, kernel_cache_dir      # noqa: F401
 from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate_indices, _slot_indices
 from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
-                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS, Hill, Monomial, Noise, RateLaw,
-                          _checked_constant, _is_int, _is_real)
+                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_INPUT_KNOTS, ODE_MAX_INPUTS, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS,
+                          Hill, Input, Monomial, Noise, RateLaw, _checked_constant, _is_int, _is_real)
 
 
 class MVNormalLogLike:
@@ -283,7 +283,7 @@ class MassActionODELogLike:
     Monomials and events work as below.
 
     conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
-    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events", "equilibrate"; a missing key is the constructor's own argument,
+    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events", "equilibrate", "inputs"; a missing key is the constructor's own argument,
     which (y0, data, sd) may be None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
     point is ((l_0 + l_1) + l_2) + ..., l_c exactly what this class gives for condition c alone (-inf if any integration fails).  On the
     device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
@@ -368,7 +368,41 @@ class MassActionODELogLike:
     the indices every K reads.  A RateLaw with no factors and order=None is the plain reaction, source and bits; a model without a
     RateLaw generates the source and the data block it always did.  Conditions, Monomials, events, equilibration, fixed_steps,
     simulate and steady_state work with it unchanged.  Not supported: a non-integer or sampled Hill exponent, arbitrary rate
-    expressions, time-dependent inputs, rate laws in event amounts.
+    expressions, rate laws in event amounts.
+
+    Inputs: inputs=[Input(species, times, values, gain=None), ...], at most 4 (ODE_MAX_INPUTS), each on a species of its own: a
+    measured or prescribed TIME COURSE that drives the network -- an upstream activity read off a blot, a perfusion protocol, a PK
+    curve, a light schedule.  The amount of `species` is gain * u(t), u the piecewise-linear curve through (times[k], values[k])
+    (times strictly increasing, at least 2; values finite and >= 0); gain is None, a finite float > 0, a parameter index (10**x[i]
+    or x[i], by rate_scale) or a Monomial: a sampled amplitude.  Nothing produces or consumes an input species -- every reaction has
+    net stoichiometry 0 on it; it may be a catalyst, a kinetic order or the species of a Hill factor --, no event targets it, its y0
+    entry is 0 and not a Monomial (the value comes from the table), it counts towards the shape's species limit, and each table
+    covers [t0, t[-1]].  A condition may carry its own "inputs": a missing key or None inherits the constructor's; its list names the
+    same species in the same order with the same gains, only the tables differ.  The contract (csrc/dz_ode.h's head, INPUTS), the
+    same in both builds and every shape:
+      * the input is carried as one more species: its right-hand side is the current segment's slope, its Jacobian row is zero, its
+        value is set exactly at every knot.  The system stays autonomous, and a Rosenbrock method integrates u' = const exactly up
+        to rounding;
+      * the WORKING KNOTS are made here, once (Input.working_knots): one at t0 -- the table's value there and the slope of the
+        segment that holds t0 --, then the table's knots strictly inside (t0, t[-1]), each with its value and the slope that follows;
+        at most 128 per experiment over all its inputs together (ODE_MAX_INPUT_KNOTS).  Each experiment's block grows at its end by
+        their count and Kmax records (time, input, value, slope);
+      * the gain g_i is evaluated once per point, when the rate constants are and with their arithmetic; a point is -inf if a
+        coordinate that a gain reads is not finite or g_i is not finite or not > 0;
+      * a due knot sets y[species] = g_i * v (one product; without a gain v itself, so Monomial({i: 1}) at x[i] = 0 gives the bits
+        of no gain) and the drive to g_i * s; inputs at one time apply in ascending index;
+      * knots are breakpoints beside t0, the event times and the output times: a step is clipped to land exactly on a knot, and the
+        controller is NOT restarted there -- a clipped step leaves its size alone, as at an output time; max_steps counts per
+        segment;
+      * at one time: an output first (measure, then intervene), then the knots, then the events in the order given;
+      * equilibrate runs with the input held at g_i * u(t0) and every drive 0, the resting state under the basal input; the knot at
+        t0 then installs the first slope before the start step.
+    ndim covers the indices a gain reads.  with_outputs(t, t0) carries the inputs over, recomputes the working knots and refuses a
+    span the tables do not cover; simulate, batch, batch_conditions, steady_state, device(), posterior_predictive and the host path of
+    run_dream work with inputs; fixed_steps ignores them, as it ignores events (every drive 0, the input species at 0).  inputs=None
+    and inputs=[] are the object it always was: the same source, data block and cache key.  To see an input's own trajectory declare
+    it as an observable with NaN data.  Not supported: inputs that are not piecewise linear, an input that reactions also consume,
+    sampled knot times.
 
     Sampled noise: noise=[...], None or O entries, each None or a Noise(sigma, rel=None, dist="normal", scale="lin"), shared by all
     conditions like `scale`.  An observable whose entry is None keeps the fixed-sd term above exactly; for one with a Noise the spread
@@ -419,10 +453,11 @@ class MassActionODELogLike:
     equilibrate = None      # (likewise)
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
     noise = None            # (likewise: before Noise existed)
+    inputs = None           # (likewise: before Input existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
-                 equilibrate=None, noise=None):
+                 equilibrate=None, noise=None, inputs=None):
         self.n_species, self.lanes_per_point, lim = self._checked_shape(n_species, lanes_per_point, len(reactions))
         noise = self._checked_noise(noise)      # None, or the entries (None | Noise); their number is tested below, once O is known
         if sd is None and noise is not None and all(z is not None for z in noise):
@@ -449,6 +484,13 @@ class MassActionODELogLike:
         # experiment: its own values, else the constructor's (checked above)
         self.conditions = conditions and [self._checked_condition(cond, "condition %d: " % c, events) for c, cond in enumerate(conditions)]
         self.scale, self.constraints = self._checked_scale(scale, len(self.observables)), self._checked_constraints(constraints)
+        self.inputs = self._checked_inputs(inputs, "") or None      # None, or the checked Input objects
+        self._check_input_species()
+        if self.conditions is not None:         # (a condition's own tables: the same species, order and gains as the constructor's)
+            for c, cond in enumerate(self.conditions):
+                own = conditions[c].get("inputs")
+                if own is not None:
+                    cond["inputs"] = self._checked_inputs(own, "condition %d: " % c, like=self.inputs or ())
         self.d = self._checked_ndim(ndim)
         self.path, self._host = path, None
 
@@ -513,8 +555,9 @@ class MassActionODELogLike:
         if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
             raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
         for c, cond in enumerate(conditions):
-            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate"}:
-                raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate" (each optional)' % c)
+            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate", "inputs"}:
+                raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate", "inputs" '
+                                 '(each optional)' % c)
             for key, top in own.items():
                 if cond.get(key) is None and top is None:
                     raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
@@ -589,6 +632,7 @@ class MassActionODELogLike:
         """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K, a Monomial or a Noise reads."""
         outside = list(self.y0_monomials.values()) + [f for f in self.scale or [] if isinstance(f, Monomial)] + [c[0] for c in self.constraints]
         outside += [c for z in self.noise or [] if z is not None for c in (z.sigma, z.rel) if c is not None and not isinstance(c, float)]
+        outside += [u.gain for u in self.inputs or () if u.gain is not None and not isinstance(u.gain, float)]
         idx = _rate_indices(self.reactions) + _slot_indices(_hill_slots(self.reactions)) + _indices_read(outside)
         d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
         if idx and max(idx) >= d:
@@ -615,6 +659,55 @@ class MassActionODELogLike:
                                  % (who, s, m, monomials[s]))
             y0[s] = np.nan
         return y0
+
+    def _checked_inputs(self, inputs, who, like=None):
+        """The inputs as a tuple of Input whose tables cover [t0, t[-1]] and whose working knots fit the experiment's limit.  like: the
+        constructor's inputs, for a condition's own: the same species in the same order with the same gains, only the tables differ."""
+        if inputs is None:
+            return ()
+        try:
+            inputs = list(inputs)
+        except TypeError:
+            inputs = [inputs]
+        if not all(isinstance(u, Input) for u in inputs):
+            raise ValueError("MassActionODELogLike: %sinputs must be a sequence of Input objects (got %r)" % (who, inputs))
+        if len(inputs) > ODE_MAX_INPUTS:
+            raise ValueError("MassActionODELogLike: %sat most %d inputs are supported (got %d)" % (who, ODE_MAX_INPUTS, len(inputs)))
+        t0, t_end = self.t0, float(self.t[-1])
+        for i, u in enumerate(inputs):
+            if not u.species < self.n_species:
+                raise ValueError("MassActionODELogLike: %sinput %d names species %r (an int in 0..%d)" % (who, i, u.species, self.n_species - 1))
+            if u.species in [v.species for v in inputs[:i]]:
+                raise ValueError("MassActionODELogLike: %sinput %d: species %d already carries an input: one input per species" % (who, i, u.species))
+            if not (u.times[0] <= t0 and u.times[-1] >= t_end):
+                raise ValueError("MassActionODELogLike: %sinput %d: its table must cover t0 = %r .. t[-1] = %r (it covers %r .. %r)"
+                                 % (who, i, t0, t_end, u.times[0], u.times[-1]))
+        if like is not None and [(u.species, type(u.gain), u.gain) for u in inputs] != [(u.species, type(u.gain), u.gain) for u in like]:
+            raise ValueError("MassActionODELogLike: %sinputs must name the constructor's input species in the same order with the same gains; "
+                             "only the tables may differ" % who)
+        knots = sum(len(u.working_knots(t0, t_end)) for u in inputs)
+        if knots > ODE_MAX_INPUT_KNOTS:
+            raise ValueError("MassActionODELogLike: %sat most %d working knots per experiment are supported, over all its inputs together (got %d)"
+                             % (who, ODE_MAX_INPUT_KNOTS, knots))
+        return tuple(inputs)
+
+    def _check_input_species(self):
+        """What an input species may not be: produced or consumed by a reaction, the target of an event, started from anything but 0."""
+        for i, u in enumerate(self.inputs or ()):
+            for r, (reac, prod, _) in enumerate(self.reactions):
+                if reac.get(u.species, 0) != prod.get(u.species, 0):
+                    raise ValueError("MassActionODELogLike: input %d: reaction %d produces or consumes species %d; an input species has net "
+                                     "stoichiometry 0 in every reaction (a catalyst, a kinetic order, a Hill factor's species)" % (i, r, u.species))
+            if u.species in self.y0_monomials:
+                raise ValueError("MassActionODELogLike: input %d: y0[%d] is a Monomial; an input species starts from its table (y0 entry 0)" % (i, u.species))
+            for c, e in enumerate(self._experiments()):
+                who = "condition %d: " % c if self.conditions is not None else ""
+                if e["y0"][u.species] != 0:
+                    raise ValueError("MassActionODELogLike: %sinput %d: y0[%d] must be 0, the value comes from the table (got %r)"
+                                     % (who, i, u.species, float(e["y0"][u.species])))
+                for n, ev in enumerate(e["events"]):
+                    if ev[1] == u.species:
+                        raise ValueError("MassActionODELogLike: %sinput %d: event %d targets the input species %d" % (who, i, n, u.species))
 
     def _checked_equilibrate(self, eq, who):
         """None (no phase) or the phase's settings, every default filled in: dict(rtol, atol, horizon, max_step, max_steps)."""
@@ -691,8 +784,19 @@ class MassActionODELogLike:
         existed).  What tells the two kinds of object apart is `self.conditions is not None`: only then the data block has its
         [C, stride] header, the kernels are the item kernels and the host build's results have an axis of conditions."""
         own = [dict(y0=self.y0, data=self.data, sd=self.sd, events=self.events, equilibrate=self.equilibrate)]
-        return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None)
+        with_inputs = lambda e: dict(inputs=e.get("inputs") or self.inputs) if self.inputs else {}      # noqa: E731
+        return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None, **with_inputs(e))
                 for e in (own if self.conditions is None else self.conditions)]
+
+    def _input_knots(self, inputs):
+        """One experiment's working knots as records (time, input, value, slope), sorted by time and at one time by input
+        (csrc/dz_ode.h, INPUTS)."""
+        t0, t_end = self.t0, float(self.t[-1])
+        return sorted((tau, float(i), v, s) for i, u in enumerate(inputs) for tau, v, s in u.working_knots(t0, t_end))
+
+    def _max_input_knots(self):
+        """Kmax: the largest count of working knots over the object's experiments (0: a network without inputs)."""
+        return max(len(self._input_knots(e["inputs"])) for e in self._experiments()) if self.inputs else 0
 
     def _event_lists(self):
         """Every experiment's events."""
@@ -710,7 +814,7 @@ class MassActionODELogLike:
         """Some experiment of the object equilibrates: the generated network's EQUILIBRATE and the six doubles at each block's end."""
         return any(eq is not None for eq in self._equilibrate_list())
 
-    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None):
+    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=()):
         seen = np.isfinite(data)
         if self.noise is None:
             C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
@@ -737,6 +841,11 @@ class MassActionODELogLike:
         if self._equilibrates():                # (csrc/dz_ode.h: on, rtol_ss, atol_ss, horizon, max_step, max_steps_ss at the very end)
             eq = equilibrate
             blk += [[1.0, eq["rtol"], eq["atol"], eq["horizon"], eq["max_step"], float(eq["max_steps"])] if eq else [0.0] * 6]
+        if self.inputs:                         # (csrc/dz_ode.h: K_c, then Kmax records padded with zeros, behind everything else)
+            knots = self._input_knots(inputs)
+            rec = np.zeros((self._max_input_knots(), 4))
+            rec[:len(knots)] = np.asarray(knots, dtype=float).reshape(-1, 4)
+            blk += [[float(len(knots))], rec.reshape(-1)]
         return np.concatenate(blk)
 
     def condition_block(self, c=0):
@@ -813,8 +922,10 @@ class MassActionODELogLike:
         shape = (len(self.observables), len(new.t))
         new.data, new.sd = np.full(shape, np.nan), np.ones(shape)
         new.events = new._checked_events(self.events, "") or None
+        new.inputs = new._checked_inputs(self.inputs, "") or None       # (the tables must cover the new span; the working knots follow it)
         if self.conditions is not None:
-            new.conditions = [dict(cond, data=new.data, sd=new.sd, events=new._checked_events(cond["events"], "condition %d: " % c))
+            new.conditions = [dict(cond, data=new.data, sd=new.sd, events=new._checked_events(cond["events"], "condition %d: " % c),
+                                   **({"inputs": new._checked_inputs(cond["inputs"], "condition %d: " % c)} if cond.get("inputs") else {}))
                               for c, cond in enumerate(self.conditions)]
         new.path, new._host, new._predict_path = None, None, None
         return new
@@ -920,7 +1031,8 @@ class MassActionODELogLike:
 
     def fixed_steps(self, x, t1, nsteps, embedded=False, condition=0):
         """The state at t1 after nsteps equal steps from (t0, y0): the order-4 solution, or the embedded order-3 one (order test).
-        condition: whose y0, for an object made with conditions."""
+        condition: whose y0, for an object made with conditions.  Inputs are ignored, as events are: every drive is 0 and an input
+        species stays at its y0 entry, 0."""
         x = np.ascontiguousarray(np.asarray(x, dtype=float).reshape(-1))
         y = np.zeros(self.n_species)
         ok = self._host_call("dzode_fixed", x, self.condition_block(condition), float(t1), int(nsteps), int(bool(embedded)), y)

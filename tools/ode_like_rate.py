@@ -10,7 +10,7 @@
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
-                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise]
+                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise] [--input]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -33,6 +33,12 @@ sigma and rel two further coordinates (10**x, x in 0 +- 0.5 and -1 +- 0.5; the n
 same network without the keyword on the same rate constants, alternately, the median of 7 rounds of 10 calls each and the rounds'
 spread; proposals/s and the host build's steps per point for both.  The per-entry cost is one dlog and a division at each of the T x O
 entries of an integration.  Kernel only.
+
+--input: what a piecewise-linear input time course costs (MassActionODELogLike(inputs=...)) -- --network drive2 | mm | enzyme13 | chain17 |
+chain40 of tests/ode_input_networks.py, a network with an input species driven by its table (a pulse of six knots), against what could
+be built before inputs existed: the same species and reactions with the input species a plain species fed by a fixed zero-order source,
+a single ramp, on the same points; alternately, the median of 7 rounds of 10 calls each and the rounds' spread; proposals/s and the host
+build's steps per point for both.  The work per step is the same; knots only add clipped steps.  Kernel only.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -263,6 +269,38 @@ def noise_rate(N, k, name, lanes, rounds=7, reps=10):
     return out
 
 
+def input_rate(N, k, name, rounds=7, reps=10):
+    """A network with an input against its emulation by a fixed zero-order source: see the head"""
+    from tests import ode_input_networks as IN
+    nominal = IN.network(name)["nominal"]
+    objs = dict(emulated=IN.emulation(name), with_input=IN.single(name))
+    import multiprocessing
+    n = N * k
+    X = box_points(nominal, 1.0, n)
+    workers = int(os.environ.get("DREAMZS_HOST_WORKERS", "16"))
+    hosts = {}
+    for key, obj in objs.items():                                        # (the host passes first: their workers are forked before the device is opened)
+        obj.host_library()
+        with multiprocessing.get_context("fork").Pool(workers) as pool:
+            parts = pool.map(_host_part, [(obj, part) for part in np.array_split(X, workers)])
+        hosts[key] = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    engines = {key: engine_for(obj, N, k, nominal, 1.0) for key, obj in objs.items()}
+    last, t = timed({key: (lambda eng=eng: eng.eval_logp(X)[1]) for key, eng in engines.items()}, rounds, reps)
+    like = objs["with_input"]
+    out = dict(network=name + " + input", lanes=like.lanes_per_point, species=like.n_species, inputs=len(like.inputs),
+               working_knots=len(like._input_knots(like.inputs)), chains=N, tries=k, points=n)
+    for key, lk in last.items():
+        host, steps = hosts[key]
+        assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
+        us = float(np.median(t[key]))
+        out[key] = dict(steps_mean=round(float(np.mean(steps)), 1), steps_median=float(np.median(steps)), steps_max=int(steps.max()),
+                        failed_points=int(np.sum(lk == -np.inf)), us_per_launch=round(us, 1),
+                        us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6))
+    out["with_over_emulated"] = round(out["with_input"]["us_per_launch"] / out["emulated"]["us_per_launch"], 3)
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def _host_part(args):
     like, part = args
     return like.batch(part, return_steps=True)
@@ -364,6 +402,8 @@ if __name__ == "__main__":
         host_twin_rate(*nums, name, lanes)
     elif "--noise" in argv:
         noise_rate(*nums, name, lanes)
+    elif "--input" in argv:
+        input_rate(*nums, name)
     elif "--equilibrate" in argv:
         assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
         events_rate(*nums, name, lanes, int(opt["--conditions"]), 0, equilibrate=True)
