@@ -258,6 +258,10 @@ DZ_DEV void mfma_units_d2(const Params& p, const double* __restrict__ Mg, const 
 // first two tries of a phase are requested before the PREVIOUS phase's barrier and likelihood pass: row indices depend on
 // (chain, generation, phase, try) only, never on the selected point.
 struct RowPair { double2 a, b; };
+// Ends the life of a buffer's values without an instruction: whatever it held has been read, and the next reader's rows will have been requested.  To the
+// compiler the buffer is a value its loops carry from set to set; where that is not said, the registers the requests land in and the registers the try loop
+// reads are kept apart and copied into each other at every set.
+DZ_DEV void rows_done(RowPair& R) { asm volatile("" : "=v"(R.a.x), "=v"(R.a.y), "=v"(R.b.x), "=v"(R.b.y)); }
 
 // The two row numbers of a DE try, random.sample(range(M), 2) (:662), from the words of its idx-1 slot
 DZ_DEV void sample_pair(uint32_t wx, uint32_t wy, uint32_t M, uint32_t& r0, uint32_t& r1)
@@ -352,15 +356,18 @@ DZ_DEV void propose_de_pf(const Params& p, int phase, uint32_t g, uint32_t M, in
         if (lane >= i0 && lane < i1) sl[lane] = 0.0;
         return;
     }
+    // (KC: the third buffer belongs to the set -- every try that reads it has requested it -- so it is not a value the caller's loops carry from set to set)
+    RowPair Cown;
+    RowPair& Cu = KC ? Cown : C;
     for (int i = i0; i < i1; i += 3) {
-        if (i + 2 < i1) request_pair<XF>(p, ds, rs + (i + 2) * sc.npt, gc, g, M, lane, C, Zb, ldb);
+        if (i + 2 < i1) request_pair<XF>(p, ds, rs + (i + 2) * sc.npt, gc, g, M, lane, Cu, Zb, ldb);
         body(i, A);
         if (i + 1 >= i1) break;
         if (i + 3 < i1) request_pair<XF>(p, ds, rs + (i + 3) * sc.npt, gc, g, M, lane, A, Zb, ldb);
         body(i + 1, B);
         if (i + 2 >= i1) break;
         if (i + 4 < i1) request_pair<XF>(p, ds, rs + (i + 4) * sc.npt, gc, g, M, lane, B, Zb, ldb);
-        body(i + 2, C);
+        body(i + 2, Cu);
     }
     if (lane >= i0 && lane < i1) { sl[lane] = 0.0; if (LEAN && prior_out) prior_out[lane] = 0.0; }            // snooker_logp = 0 (flat priors: 0)
 }
@@ -732,6 +739,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
                 if (mine) {
                     if (((REDO && round > 0) || !PF_AHEAD) && !snk_s && !multipair) prefetch_first(dcur, phase, g, M);      // (round 0's first rows were requested a phase ahead)
                     propose_range(i0, i1, RA, RB, RC);
+                    if (CUR) { rows_done(RA); rows_done(RB); }      // (every DE set reads rows requested for it, a phase ahead: prefetch_first)
                     if (PF_AHEAD && phase == 0 && round == 0 && !snk_s && !multipair) prefetch_first(ds, 1, g, M);  // the reference set's first rows, ahead of the likelihood pass
                 }
                 if (round == 0 && phase == nph - 1 && !last) {                       // the next generation's draws and first rows
