@@ -172,7 +172,7 @@ struct dz_engine {
     // 0's published position after generation h at slot h mod 2 (L + 1); d_x0start: before generation 0.
     int ad_R1 = 1, ad_nbp = 0; bool ad_multi = false; int64_t ad_applied = -1, ad_made = -1; size_t ad_tot_stride = 0, ad_pr_stride = 0, ad_pc_stride = 0;
     double *d_DOT = nullptr, *d_x0ring = nullptr, *d_x0start = nullptr;
-    // ... and for the kernels that do not make their blocks' unit sums (burnin_multi == 2): d_posring [L + 2][N][ld] the published positions of the last
+    // ... and for the kernels that do not make their blocks' unit sums (MegaChoice::burnin == 2): d_posring [L + 2][N][ld] the published positions of the last
     // L + 2 generations (slot = generation mod (L + 2); made on first use), posring_gen the last generation in it; d_PG [L + 1][ad_nbp] the probabilities
     // the last launch's generations decided with (k_adapt_partials_ring)
     double *d_posring = nullptr, *d_PG = nullptr; int64_t posring_gen = -2;
@@ -192,7 +192,7 @@ struct dz_engine {
     int64_t stream_prop_gen = -1;   // the generation whose proposal set k_accept_propose has already made
     bool q_defer = true;            // streamed generations: no k_q_finish launches, the proposal / Metropolis kernels add the row-tile sums (DZ_QFIN=0: off)
     double* last_qpart = nullptr;   // the scratch slice the last tiled likelihood launch wrote
-    bool mega = true;               // the persistent generation kernel serves every eligible configuration (mega_eligible); DZ_MEGA=0 forces the multi-kernel path
+    bool mega = true;               // the persistent generation kernel serves every eligible configuration (mega_choose, dz_mega_select.h); DZ_MEGA=0 forces the multi-kernel path
     bool mega_redo_on = true;       // redraw rounds (Dream.py:281-289) inside the persistent kernel; DZ_MEGA_REDO=0: such configurations take the multi-kernel path
     unsigned long long* d_redraw_count = nullptr;
     int mega_d2 = 1;                // 128 < d <= 256: k_generations_d2 from 1025 chains on (DZ_MEGA_D2=0: the multi-kernel path there; 2: at any chain count)
@@ -207,6 +207,7 @@ struct dz_engine {
     int64_t redraw_rounds = 0;      // redraw launches so far (dz_redraw_rounds)
     double *d_own_cr = nullptr, *d_own_g = nullptr; std::vector<char> own_init;      // per-instance probabilities of single-chain stepping (Params::own_cr)
     std::string broken;             // non-empty: a failed dz_continue_run left the engine without some of its buffers -- dz_step refuses
+    dz::MegaShape mshape; dz::MegaChoice mchoice;      // the persistent kernels' selection, made at the start of every dz_step (mega_select)
     std::string last_variant;       // what the last dz_step launched for its generations (dz_last_kernel_variant)
     int last_kc = 0;                // ... and the try count compiled into it (MegaLaunch::kc; dz_last_kernel_tries)
     bool pending_accept = false;    // generation gen-1's Metropolis step has been deferred into the next proposal kernel
@@ -351,7 +352,7 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
     const int ks4 = 4 * ((e->p.d + 3) / 4);
     // LDS kernel: matrix (packed triangle or square) + mean + at least 4 wave tiles must fit 160 KB
     // (the dense 128-D square does not: 131 KB + 66 KB; it runs on the register-operand MFMA kernel)
-    const bool lds_fits = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld + (size_t)4 * 16 * (e->p.ld + 1)) <= (size_t)160 * 1024;
+    const bool lds_fits = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld + (size_t)4 * 16 * (e->p.ld + 1)) <= dz::LDS_LIMIT;
     const bool one_kernel = e->lk == LK_MVN && !e->p.have_prior && nrt <= 8 && lds_fits;   // the LDS kernel alone: timed by the launch's own events
     ProfScope ps(e, PR_LOGP, st, !one_kernel);
     const dim3 grid((n + 3) / 4), block(256);
@@ -363,7 +364,7 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
                 // 5-wave blocks instead of 4-wave blocks of which a quarter does a second tile
                 const size_t lds_fixed = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld), lds_wave = sizeof(double) * (size_t)16 * (e->p.ld + 1);
                 int nwv = std::max(4, std::min(8, (ntiles + e->num_cu - 1) / e->num_cu));
-                while (nwv > 4 && lds_fixed + nwv * lds_wave > (size_t)160 * 1024) --nwv;
+                while (nwv > 4 && lds_fixed + nwv * lds_wave > dz::LDS_LIMIT) --nwv;
                 const size_t lds = lds_fixed + nwv * lds_wave;
                 const dim3 gl((unsigned)std::min(e->num_cu, (ntiles + nwv - 1) / nwv)), bl(64 * nwv);
 #define DZ_LDS_CASE(NRT_)                                                                                                      \
@@ -930,139 +931,35 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
 // ---- persistent generation kernel (dz_megakernel.h) -------------------------------------------------
 // chain states, gamma table and decisions ride in LDS next to the matrix whenever that fits (the packed triangle at
 // d=100 leaves room; the dense square does not)
-// chains (= waves) per block: 16 once that still gives every CU a block, else 8 or 4 (C2: 1024 chains -> 256 blocks of 4)
-// -> chains per block of the (first) launch; split_c / ch_b: a generation as TWO launches -- whole rounds of ch-chain blocks for the local chains
-// [0, split_c), the remainder in blocks of ch_b chains (split_c == nl: one launch)
-struct MegaPlan { int ch, split_c, ch_b; };
-MegaPlan mega_plan(const dz_engine* e)
+// Which instantiation runs, with what grid, block and LDS size, is decided in dz_mega_select.h: mega_choose once per dz_step from the facts gathered
+// here -- the only selection code that reads the engine -- and mega_launch_plan once per launch.
+static_assert(LK_MVN == dz::MEGA_LK_MVN && LK_MIX == dz::MEGA_LK_MIX && LK_MODULE == dz::MEGA_LK_MODULE, "likelihood kinds");
+dz::MegaShape mega_shape(const dz_engine* e)
 {
     const dz::Params& p = e->p;
-    // One block per CU is resident (LDS), so a launch takes ceil(blocks / CUs) rounds of a block's time; measured at 100-D a block of 12
-    // chains needs 0.82 (round 6), one of 8 chains 0.67 and one of 4 chains (four waves per chain) 0.49 of the time of a block of 16.  The
-    // smallest product wins, the larger block on a tie: 4096 chains -> 16, 3072 -> 12 (round 6: 256 blocks of 12 -- 677 M proposals/s; as
-    // 192 blocks of 16, a quarter of the chip idle, 561), 2048 -> 8, 1024 -> 4 ... among the block sizes whose LDS layout fits at all (round
-    // 4): at 113..128 dimensions the point tiles of 16 chains no longer fit next to the matrix, those of 8 do.
-    // A chain count just above whole rounds -- 5000 chains: 313 blocks of 16 -- pays a whole round for its remainder; the remainder can go in
-    // a SECOND launch of smaller blocks (whole rounds of the large blocks first).  The second launch's blocks start while the first one's
-    // last blocks drain, worth about 0.12 of a 16-chain block's time (5000 chains: 16 + 8 measured 39.8 us per generation, modelled without
-    // the overlap 46.4; 12 + 8: 40.0; 417 blocks of 12 in two rounds: 43.1).
-    const int ncu = e->num_cu > 0 ? e->num_cu : 1;
-    const int cand[4] = {16, 12, 8, 4};
-    const double cost[4] = {1.0, 0.82, 0.67, 0.49};
-    const bool need_x = p.hard || p.have_prior || p.depairs > 1;          // (the full-code instantiations keep the states in LDS)
-    const bool k1 = p.k == 1;
-    bool fits[4];
-    for (int i = 0; i < 4; ++i)
-        fits[i] = !(cand[i] == 12 && k1) &&
-                  sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, p.tri != 0, need_x, cand[i], need_x && p.pb_lds != 0).total <= (size_t)160 * 1024;
-    MegaPlan best{dz::MEGA_CHAINS, p.nl, 0}; double tb = -1.0;
-    for (int i = 0; i < 4; ++i) {
-        if (!fits[i]) continue;
-        const int ch = cand[i], blocks = (p.nl + ch - 1) / ch, rounds = (blocks + ncu - 1) / ncu;
-        const double t = rounds * cost[i];
-        if (tb < 0.0 || t < tb - 1e-9) { best = MegaPlan{ch, p.nl, 0}; tb = t; }
-        if (k1 || ch < 12 || blocks <= ncu || blocks % ncu == 0) continue;
-        const int full = (blocks / ncu) * ncu * ch, r = p.nl - full;
-        for (int j = i + 1; j < 4; ++j) {
-            if (!fits[j]) continue;
-            const int rb = ((r + cand[j] - 1) / cand[j] + ncu - 1) / ncu;
-            const double t2 = (blocks / ncu) * cost[i] + rb * cost[j] - 0.12;
-            if (t2 < tb - 1e-9) { best = MegaPlan{ch, full, cand[j]}; tb = t2; }
-        }
-    }
-    return best;
+    dz::MegaShape s;
+    s.d = p.d; s.ld = p.ld; s.k = p.k; s.depairs = p.depairs; s.npt = p.npt; s.nslots = p.nslots; s.ncr = p.ncr; s.ngamma = p.ngamma; s.J = p.J;
+    s.tri = p.tri != 0; s.mtp = p.Mtp != nullptr; s.hard = p.hard != 0; s.have_prior = p.have_prior != 0;
+    s.nl = p.nl; s.N = p.N; s.ncu = e->num_cu;
+    s.lk = e->lk; s.lk_items = e->lk_items; for (int i = 0; i < 4; ++i) s.gen_fn[i] = e->lk_gen_fn[i] != nullptr;
+    s.redo_possible = redo_possible(e);
+    s.ad_multi = e->ad_multi; s.ad_R1 = e->ad_R1; s.ad_nbp = e->ad_nbp; s.adapt_lag = e->c.adapt_lag; s.adapt_fused = e->adapt_fused; s.adapt_groups = e->adapt_groups;
+    s.tempering = e->tempering; s.world = e->world;
+    s.mega = e->mega; s.mega_d2 = e->mega_d2; s.mega_kc = e->mega_kc; s.mega_redo = e->mega_redo_on;
+    return s;
 }
-int mega_chains(const dz_engine* e) { return mega_plan(e).ch; }
-size_t mega_lds_bytes(const dz_engine* e, bool xlds)
+// dz_step: the choice for its generations (nothing the selection reads changes inside a dz_step), and the two Params fields that follow from it
+bool mega_select(dz_engine* e)
 {
-    return sizeof(double) * (size_t)dz::mega_layout(e->p.d, e->p.k, e->p.ld / 16, e->p.ncr, e->p.ngamma, e->p.tri != 0, xlds, mega_chains(e), e->p.pb_lds != 0).total;
-}
-// the full-code instantiations stage the per-dimension prior / boundary constants in LDS when that still fits (Params::pb_lds)
-void mega_set_pb_lds(dz_engine* e)
-{
-    const bool pb = e->p.hard || e->p.have_prior || e->p.depairs > 1 || (redo_possible(e) && e->lk == LK_MVN && e->p.k > 1 && e->mega_redo_on);
-    e->p.pb_lds = 0;
-    {   // uniform / flat priors whose supports contain the hard boundaries' box: the log prior of every proposal is one constant
-        bool cst = e->p.have_prior && e->p.prior_nonormal && e->p.hard;
-        for (size_t j = 0; cst && j < e->h_pkind.size(); ++j)
-            if (e->h_pkind[j] == 2 && !(j < e->h_mins.size() && e->h_mins[j] >= e->h_pa[j] && e->h_maxs[j] <= e->h_pa[j] + e->h_pb[j])) cst = false;
-        e->p.prior_const = cst ? 1 : 0;
-    }
-    if (!pb) return;
-    e->p.pb_lds = 1;
-    if (mega_lds_bytes(e, true) > (size_t)160 * 1024) e->p.pb_lds = 0;
-}
-bool mega_xlds(const dz_engine* e) { return mega_lds_bytes(e, true) <= (size_t)160 * 1024; }
-// the barrier-free variant for the mixture likelihood (k_generations_mix)
-bool mega_mix_eligible(const dz_engine* e)
-{
-    const dz::Params& p = e->p;
-    const bool pbm = p.hard || p.have_prior || p.depairs > 1;
-    return e->mega && (e->lk == LK_MIX || (e->lk == LK_MODULE && e->lk_items == 1 && e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)])) && !redo_possible(e) &&
-           p.ld <= 256 && (p.k == 1 || p.k >= 3) && p.k <= dz::MAXK &&
-           p.nslots <= 64 && p.J <= 32;
-}
-// redraw rounds inside the persistent kernel: the instantiations with the full proposal code, multi-try, device MVN likelihood
-bool mega_redo(const dz_engine* e) { return redo_possible(e) && e->lk == LK_MVN && e->p.k > 1 && e->mega_redo_on; }
-// 128 < d <= 256 (the reference example's d = 200): k_generations_d2 -- configurations with the triangular factor (what
-// MVNormalLogLike builds) whose point tiles of 16 chains fit LDS without the matrix (it is read from L2): d <= ~230 at 5 tries.  Measured and
-// left on the multi-kernel path: 8 chains per block (d = 256: 131 against 123 us per generation) and the dense matrix (its 16-chain
-// instantiation spills a hundred registers; at 8 chains per block 156 against 148 us at d = 200).
-// (round 6) 16 chains per block whose k tries' point tiles do not fit but k - 1 do (229..256 dimensions at 5 tries): the proposal set in two passes
-// (k_generations_d2<.., SP>); 3..15 tries, 128 < d
-bool mega_d2_two_pass(const dz_engine* e, int ch = 16)
-{
-    const dz::Params& p = e->p;
-    if (p.ld <= 128 || p.k < 3 || p.nslots > 64) return false;
-    if (sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, ch, false, false, true).total <= (size_t)160 * 1024) return false;
-    return sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, ch, false, false, true, 0, true).total <= (size_t)160 * 1024;
-}
-int mega_d2_chains(const dz_engine* e)
-{
-    const dz::Params& p = e->p;
-    if (!e->mega || !e->mega_d2 || e->lk != LK_MVN || p.ld > 256) return 0;
-    if (p.ld < 80 && p.nslots <= 64) return 0;
-    // (round 6) more than 15 tries: a generation's draw slots exceed a wave's lanes, the classic kernels do not take them; this one keeps one phase's
-    // slots at a time (k npt <= 64: up to 32 tries with one or two DE pairs)
-    const bool bigk = p.nslots > 64;
-    if (bigk && (p.k * p.npt > 64 || p.k > dz::MAXK)) return 0;
-    if (p.ld <= 128 && !bigk) {      // d <= 128: only where the classic kernel's 16-chain layout (matrix in LDS) does not fit -- it then runs 8 chains per block (113..128
-                            // dimensions at 5 tries, 100 dimensions at 8 or more)
-        const bool pbx = p.hard || p.have_prior || p.depairs > 1;
-        const size_t classic = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, pbx, 16, pbx && p.pb_lds != 0).total;
-        if (classic <= (size_t)160 * 1024 || p.k == 1) return 0;
-    }
-    if (e->mega_d2 == 1 && p.nl <= 1024) return 0;      // (64 blocks or fewer leave three CUs in four idle: 57 against 52 us per generation at 1024 x 200-D; DZ_MEGA_D2=2 forces it)
-    if (redo_possible(e)) return 0;      // (whole proposal sets that can be impossible: the multi-kernel path's redraw rounds)
-    if (p.k != 1 && p.k < 3) return 0;
-    if (!p.tri || !p.Mtp) return 0;
-    const size_t lds = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, 16, false, false, true).total;
-    if (lds <= (size_t)160 * 1024) return 16;
-    if (mega_d2_two_pass(e)) return 16;
-    // round 6: 8 chains x 2 waves per block where the point tiles of 16 chains do not fit (128 < d: 229..256 dimensions at 5 tries) -- multi-try only
-    if (p.ld <= 128 && !bigk) {      // (13..15 tries at 100 dimensions: the classic kernel would run 4 chains x 4 waves -- 603 M proposals/s at k = 15 against 693 for 8 x 2 here at k = 16)
-        const bool pbx = p.hard || p.have_prior || p.depairs > 1;
-        if (sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, pbx, 8, pbx && p.pb_lds != 0).total <= (size_t)160 * 1024) return 0;
-    }
-    if (p.k >= 3 &&
-        sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, 8, false, false, true).total <= (size_t)160 * 1024) return 8;
-    if (p.k >= 3 && mega_d2_two_pass(e, 8)) return 8;      // 8 x 2 with the two-pass set (256 dimensions at 8 tries)
-    // ... and 4 chains x 4 waves where not even those fit (24..32 tries at 100 dimensions, 20..32 at 128, 8 at 256): four rounds of 1024 blocks at 4096
-    // chains, still ahead of the multi-kernel path
-    if (p.k >= 4 &&
-        sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, true, false, 4, false, false, true).total <= (size_t)160 * 1024) return 4;
-    return 0;
-}
-bool mega_eligible(dz_engine* e)
-{
-    mega_set_pb_lds(e);
-    const dz::Params& p = e->p;
-    if (mega_d2_chains(e) > 0) return true;
-    if (redo_possible(e) && !mega_redo(e)) return false;
-    if (mega_mix_eligible(e)) return true;
-    if ((p.hard || p.have_prior || p.depairs > 1 || mega_redo(e)) && !mega_xlds(e)) return false;      // (the full-code instantiations keep the states in LDS)
-    return e->mega && e->lk == LK_MVN && p.ld <= 128 && (p.k == 1 || p.k >= 3) && p.k <= dz::MAXK &&
-           p.nslots <= 64 && (!p.tri || p.Mtp) && mega_lds_bytes(e, false) <= (size_t)160 * 1024;
+    e->mshape = mega_shape(e);
+    e->mchoice = dz::mega_choose(e->mshape);
+    e->p.pb_lds = e->mchoice.pb_lds ? 1 : 0;
+    // uniform / flat priors whose supports contain the hard boundaries' box: the log prior of every proposal is one constant
+    bool cst = e->p.have_prior && e->p.prior_nonormal && e->p.hard;
+    for (size_t j = 0; cst && j < e->h_pkind.size(); ++j)
+        if (e->h_pkind[j] == 2 && !(j < e->h_mins.size() && e->h_mins[j] >= e->h_pa[j] && e->h_maxs[j] <= e->h_pa[j] + e->h_pb[j])) cst = false;
+    e->p.prior_const = cst ? 1 : 0;
+    return e->mchoice.family != dz::MEGA_NONE;
 }
 // number of generations, starting at g, that one launch may cover: none of them publishes positions
 // (crossover burn-in), and only the last one may append to the history
@@ -1093,59 +990,13 @@ int mega_appends_per_launch(const dz_engine* e)
     const int a = (e->world > 1 && e->peer_on) ? (lag + 1) / 2 : lag + 1;
     return std::max(1, std::min(a, e->mega_segs));
 }
-// adapt_lag >= 1: can a launch hold several burn-in generations?  One GPU, and a kernel instantiation that makes its block's unit sums
-// generation by generation (blocks of 16 chains = one unit): the mixture kernel's MG instantiations
-size_t mix_multi_lds(const dz_engine* e)
-{
-    const dz::Params& p = e->p;
-    const size_t LDP = (size_t)4 * ((p.d + 3) / 4) + 1;
-    return sizeof(double) * ((size_t)16 * dz::mega_mix_wave_doubles(p.d, p.k, p.J) + (size_t)e->ad_R1 * e->ad_nbp + 64 * LDP + 32);
-}
-size_t mvn_multi_lds(const dz_engine* e)
-{
-    const dz::Params& p = e->p;
-    return sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, p.ld / 16, p.ncr, p.ngamma, p.tri != 0, true, 16, p.pb_lds != 0, true, false, e->ad_R1).total;
-}
-// -> 1: the kernel makes its blocks' unit sums generation by generation (the MG instantiations: blocks of 16 chains = one unit);  2: any other persistent
-// kernel (blocks of 12 / 8 / 4 chains, split generations, 128 < d <= 256, multitry off, redraw rounds) -- every generation's positions go to a ring of
-// published positions and ONE k_adapt_partials_ring launch behind it makes the sums of all its generations;  0: one burn-in generation per launch
-int burnin_multi(const dz_engine* e)
-{
-    if (!e->ad_multi || e->tempering) return 0;
-    const dz::Params& p = e->p;
-    const size_t tab = sizeof(double) * (size_t)e->ad_R1 * e->ad_nbp, cap = (size_t)160 * 1024;
-    const bool ring_ok = sizeof(double) * (size_t)(e->c.adapt_lag + 2) * p.N * p.ld <= ((size_t)8 << 30);
-    if (e->lk == LK_MIX || e->lk == LK_MODULE) {
-        if (!mega_mix_eligible(e)) return 0;
-        if (e->lk == LK_MIX && e->adapt_fused && p.k >= 3 && p.ld <= 128 && mix_multi_lds(e) <= cap) return 1;
-        return (ring_ok && sizeof(double) * (size_t)dz::MIXW * dz::mega_mix_wave_doubles(p.d, p.k, p.J) + tab <= cap) ? 2 : 0;
-    }
-    if (e->lk != LK_MVN || !e->mega) return 0;
-    const int nrt = p.ld / 16;
-    if (const int chd = mega_d2_chains(e)) {
-        const bool sp = (chd == 16 && mega_d2_two_pass(e)) || (chd == 8 && mega_d2_two_pass(e, 8));
-        return (ring_ok && sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, false, chd, false, false, true, e->ad_R1, sp).total <= cap) ? 2 : 0;
-    }
-    if (p.ld > 128 || (p.k != 1 && p.k < 3) || p.k > dz::MAXK || p.nslots > 64 || (p.tri && !p.Mtp)) return 0;
-    const MegaPlan plan = mega_plan(e);
-    const bool pb = p.hard || p.have_prior || p.depairs > 1 || mega_redo(e);
-    if (e->adapt_fused && p.k >= 3 && !redo_possible(e) && plan.ch == 16 && plan.split_c == p.nl && (pb || mega_xlds(e)) && mvn_multi_lds(e) <= cap) return 1;
-    if (!ring_ok || (redo_possible(e) && !mega_redo(e))) return 0;
-    const bool xl = pb ? true : mega_xlds(e);
-    for (int part = 0; part < 2; ++part) {
-        const int chp = part ? plan.ch_b : plan.ch;
-        if (part && plan.split_c == p.nl) break;
-        if (sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, xl, chp, p.pb_lds != 0, false, false, e->ad_R1).total > cap) return 0;
-    }
-    return 2;
-}
 int mega_segment(const dz_engine* e, uint32_t g, int64_t remaining)
 {
     // crossover burn-in: the positions are published and the probabilities adapted after every generation -- one generation per launch, or
-    // (adapt_lag = L >= 1, one GPU, a kernel that makes its units' sums generation by generation: burnin_multi) up to L + 1 of them
+    // (adapt_lag = L >= 1, one GPU, a kernel that makes its units' sums generation by generation: MegaChoice::burnin) up to L + 1 of them
     const bool pub0 = publishing(e, g);
     if (e->tempering) return remaining > 0 ? 1 : 0;       // parallel tempering: a temperature swap follows every generation (core.py:185-221)
-    if (pub0 && !burnin_multi(e)) return remaining > 0 ? 1 : 0;
+    if (pub0 && !e->mchoice.burnin) return remaining > 0 ? 1 : 0;
     const int maxg = pub0 ? e->c.adapt_lag + 1 : MEGA_MAX_GEN;      // (adapt_lag <= 1023: dz_create)
     // A launch ends with a history append -- unless the rows it writes are not sampleable yet anyway (history_lag >= 1, every lagged append
     // already made): the kernel then makes the append itself and runs on, up to mega_appends_per_launch of them (the generations behind the
@@ -1161,6 +1012,10 @@ int mega_segment(const dz_engine* e, uint32_t g, int64_t remaining)
     }
     return n;
 }
+// the translation units' launchers by row-tile count nrt = ld / 16 (dz_mega_tu.hip; 9..16: k_generations_d2 only)
+const char* (*const MEGA_LAUNCHERS[17])(const dz::MegaLaunch&) = {
+    nullptr, dz::mega_launch_nrt1, dz::mega_launch_nrt2, dz::mega_launch_nrt3, dz::mega_launch_nrt4, dz::mega_launch_nrt5, dz::mega_launch_nrt6, dz::mega_launch_nrt7, dz::mega_launch_nrt8,
+    dz::mega_launch_nrt9, dz::mega_launch_nrt10, dz::mega_launch_nrt11, dz::mega_launch_nrt12, dz::mega_launch_nrt13, dz::mega_launch_nrt14, dz::mega_launch_nrt15, dz::mega_launch_nrt16};
 int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
 {
     dz::Params& p = e->p;
@@ -1169,20 +1024,16 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
     int napps = 0, seg0 = 0;
     for (int i = 0; i < n; ++i) if ((g + (uint32_t)i) % (uint32_t)p.thin == 0) { if (!napps) seg0 = i + 1; ++napps; }
     const bool append_last = napps > 0;
-    {   // no generation of the launch may sample rows the launch itself writes: at most history_lag appends in front of any generation
-        const bool ends_with_one = ((g + (uint32_t)n - 1) % (uint32_t)p.thin) == 0;
-        const int allowed = mega_appends_per_launch(e);
-        if (napps > 1 && (e->napp < e->c.history_lag || napps > allowed - (ends_with_one ? 0 : 1))) return fail("internal: too many history appends in one launch");
-    }
+    const bool ends_with_one = ((g + (uint32_t)n - 1) % (uint32_t)p.thin) == 0;
+    // no generation of the launch may sample rows the launch itself writes: at most history_lag appends in front of any generation
+    if (napps > 1 && (e->napp < e->c.history_lag || napps > mega_appends_per_launch(e) - (ends_with_one ? 0 : 1))) return fail("internal: too many history appends in one launch");
     if (append_last && e->M + (int64_t)napps * p.N > e->c.history_capacity) return fail("history capacity exceeded");
     DZCK(join_all(e));
-    {   // the rows the launch samples have arrived: its last generation may sit behind all but the last of its own appends
-        const bool ends_with_one = ((g + (uint32_t)n - 1) % (uint32_t)p.thin) == 0;
-        DZCK(ensure_visible(e, std::max(0, napps - (ends_with_one ? 1 : 0))));
-    }
-    const bool publish = publishing(e, g);            // (then n == 1: mega_segment -- or, adapt_lag >= 1 and burnin_multi, up to adapt_lag + 1)
+    // the rows the launch samples have arrived: its last generation may sit behind all but the last of its own appends
+    DZCK(ensure_visible(e, std::max(0, napps - (ends_with_one ? 1 : 0))));
+    const bool publish = publishing(e, g);            // (then n == 1: mega_segment -- or, adapt_lag >= 1 and a burn-in mode, up to adapt_lag + 1)
     const bool ring = e->c.adapt_lag > 0;
-    const int mmode = (publish && ring) ? burnin_multi(e) : 0;
+    const int mmode = (publish && ring) ? e->mchoice.burnin : 0;
     const bool multi = mmode == 1;      // the launch applies the pending updates itself and makes its units' sums generation by generation
     const bool rmulti = mmode == 2;     // ... or leaves every generation's positions in the ring; the sums follow (k_adapt_partials_ring)
     if (ring && !mmode) DZCK(adapt_apply_due(e, (int64_t)g));   // (every generation of such a launch decides with the same state: one burn-in generation, or none)
@@ -1205,186 +1056,85 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
     pub.sh = p.cr_probs; pub.sh_out = nullptr; pub.TOT = nullptr; pub.CNT = nullptr; pub.c0 = 0; pub.c1 = p.nl;
     const bool applies = e->adapt_pending;      // the previous generation's adaptation totals: applied by this launch's prologue, new state into the other copy
     if (applies) { pub.TOT = e->d_TOT; pub.CNT = e->d_CNT; pub.sh_out = e->d_shared + (size_t)(e->sh_cur ^ 1) * 3 * (p.ncr + p.ngamma); }
-    if (multi) {      // adapt_lag >= 1: the pending updates, the rings, the table of probabilities per generation (Publish, dz_kernels.h)
-        pub.multi = 1; pub.lag = e->c.adapt_lag; pub.burnin = p.burnin; pub.nbp = e->ad_nbp; pub.pend0 = e->ad_applied + 1; pub.pend1 = e->ad_made + 1;
-        pub.DOT = e->d_DOT; pub.CNTR = e->d_CNT; pub.x0ring = e->d_x0ring; pub.x0start = e->d_x0start; pub.pr_stride = (long long)e->ad_pr_stride; pub.pc_stride = (long long)e->ad_pc_stride;
-        pub.PR = e->d_PR; pub.PC = e->d_PC;
-        pub.sh_out = e->d_shared + (size_t)(e->sh_cur ^ 1) * 3 * (p.ncr + p.ngamma);
+    if (mmode) {      // adapt_lag >= 1: the pending updates, the rings, the table of probabilities per generation (Publish, dz_kernels.h)
+        pub.multi = mmode; pub.lag = e->c.adapt_lag; pub.burnin = p.burnin; pub.nbp = e->ad_nbp; pub.pend0 = e->ad_applied + 1; pub.pend1 = e->ad_made + 1;
+        pub.DOT = e->d_DOT; pub.CNTR = e->d_CNT; pub.sh_out = e->d_shared + (size_t)(e->sh_cur ^ 1) * 3 * (p.ncr + p.ngamma);
+        if (multi) { pub.x0ring = e->d_x0ring; pub.x0start = e->d_x0start; pub.pr_stride = (long long)e->ad_pr_stride; pub.pc_stride = (long long)e->ad_pc_stride; pub.PR = e->d_PR; pub.PC = e->d_PC; }
+        else { pub.to = e->d_posring; pub.pos_stride = (long long)pos_stride; pub.PG = e->d_PG; }
     }
-    if (rmulti) {
-        pub.multi = 2; pub.lag = e->c.adapt_lag; pub.burnin = p.burnin; pub.nbp = e->ad_nbp; pub.pend0 = e->ad_applied + 1; pub.pend1 = e->ad_made + 1;
-        pub.DOT = e->d_DOT; pub.CNTR = e->d_CNT; pub.to = e->d_posring; pub.pos_stride = (long long)pos_stride; pub.PG = e->d_PG;
-        pub.sh_out = e->d_shared + (size_t)(e->sh_cur ^ 1) * 3 * (p.ncr + p.ngamma);
-    }
-    auto launched = [&]() {
-        if (applies) { e->sh_cur ^= 1; point_shared(e); e->adapt_pending = false; }
-        if (multi || rmulti) { e->sh_cur ^= 1; point_shared(e); e->ad_applied = std::max(e->ad_applied, adapt_due(e, (int64_t)g + n - 1)); }
-    };
-    // crossover burn-in on one GPU: a block of 16 chains is one unit of the adaptation's column sums (contract v3) and makes them itself
     bool fused = false;
-    auto fuse_adapt = [&]() { fused = true; pub.shift = adapt_shift(e, g); pub.PR = e->d_PR; pub.PC = e->d_PC; };
-    auto after_launch = [&]() -> int {      // end of the generation(s): positions -> adaptation -> history append (schedule S2)
-        const bool sharded = e->world > 1;      // (then the ranks own whole groups: their groups' sums travel, one exchange per launch -- adapt_finish_groups)
-        if (multi) { ProfScope ps(e, PR_ADAPT); DZCK(sharded ? adapt_finish_groups(e, g, n) : adapt_finish(e, false, g, n, true)); }      // the totals and dot products of the launch's n generations
-        else if (rmulti) {
-            ProfScope ps(e, PR_ADAPT);
-            hipLaunchKernelGGL(dz::k_adapt_partials_ring, dim3(sharded ? p.nl / 16 : (p.N + 15) / 16, n), dim3(1024), 0, e->stream, p, g, e->ad_R1, (const double*)e->d_posring, (long long)pos_stride,
-                               (const double*)e->d_PG, e->ad_nbp, e->d_PR, e->d_PC, (long long)e->ad_pr_stride, (long long)e->ad_pc_stride, e->d_x0ring, (const double*)e->d_x0start, p.off / 16);
-            DZCK(launch_check("k_adapt_partials_ring"));
-            DZCK(sharded ? adapt_finish_groups(e, g, n) : adapt_finish(e, false, g, n, true));
-            e->posring_gen = (int64_t)g + n - 1;
-            p.cp_new = e->d_posring + (size_t)(e->posring_gen % RP) * pos_stride;      // (what a later launch that is not of this kind measures its jumps from)
-        }
-        else if (publish) {
-            if (!e->adapt_groups) DZCK(exchange_rows(e, XK_POS, p.cp_new, 0));      // (ranks that own whole groups exchange their groups' sums instead: adapt_generation)
-            DZCK(adapt_generation(e, g, 0, p.N, fused, mega_follows));
-        }
-        for (int a = 0; a < napps; ++a) { DZCK(exchange_rows(e, XK_Z, p.Z, (size_t)e->M)); e->M += p.N; e->napp += 1; }
-        if (e->tempering) {          // (then n == 1) the temperature swap: after every chain's step and the updates above, as on the multi-kernel path
-            NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot0, publish ? 1 : 0));
-            DZCK(launch_check("k_pt_swap"));
-        }
-        e->need_join = true;
-        e->draws_gen = -1;
-        e->gen = (int64_t)g + n;
-        for (auto& gcv : e->gen_c) gcv = e->gen;
-        return 0;
-    };
-    if (e->lk == LK_MIX || e->lk == LK_MODULE) {
-        DZCK(upload_params(e));
-        int mw = dz::MIXW;
-        const size_t lds_probs = sizeof(double) * (size_t)((p.ncr + p.ngamma + 1) & ~1);
-        const size_t lds_xo = sizeof(double) * (size_t)16 * (4 * ((p.d + 3) / 4) + 1);
-        if (multi) mw = 16;
-        else if (publish && !ring && e->adapt_fused && (e->world == 1 || e->adapt_groups) && p.k >= 3 && p.ld <= 128 && sizeof(double) * (size_t)16 * dz::mega_mix_wave_doubles(p.d, p.k, p.J) + lds_probs + lds_xo <= (size_t)160 * 1024) { mw = 16; fuse_adapt(); }
-        const dim3 gridm((p.nl + mw - 1) / mw), blockm(64 * mw);
-        const size_t ldsm = multi ? mix_multi_lds(e) : sizeof(double) * (size_t)mw * dz::mega_mix_wave_doubles(p.d, p.k, p.J) + (rmulti ? sizeof(double) * (size_t)e->ad_R1 * e->ad_nbp : lds_probs) + (fused ? lds_xo : 0);
-        const bool pbm = p.hard || p.have_prior || p.depairs > 1;
-        if (e->lk == LK_MODULE) {      // the user's density inside the same kernel: the code object's own instantiation (dz_set_likelihood_module)
-            const dz::Params* pp_ = (const dz::Params*)e->d_params; uint32_t g_ = g; int n_ = n; uint32_t M_ = (uint32_t)visible_rows(e); int64_t s_ = slot0, z_ = append_last ? e->M : (int64_t)-1; int seg_ = seg0;
-            void* args[] = {&pp_, &g_, &n_, &M_, &s_, &z_, &seg_, &pub};
+    const dz::MegaChoice& ch = e->mchoice;
+    const dz::MegaLaunchPlan plan = dz::mega_launch_plan(ch, e->mshape, publish, applies);
+    DZCK(upload_params(e));
+    const int nrt = p.ld / 16;
+    const uint32_t Mvis = (uint32_t)visible_rows(e);
+    const int64_t zappend = append_last ? e->M : (int64_t)-1;
+    std::string variant;
+    for (int i = 0; i < plan.nparts; ++i) {
+        const dz::MegaPart& part = plan.part[i];
+        dz::Publish pp = pub; pp.c0 = part.c0; pp.c1 = part.c1;
+        // crossover burn-in on one GPU: a block of 16 chains is one unit of the adaptation's column sums (contract v3) and makes them itself
+        if (part.fused) { fused = true; pp.shift = adapt_shift(e, g); pp.PR = e->d_PR; pp.PC = e->d_PC; }
+        const dim3 grid(part.grid), block(part.block);
+        const bool full = part.f.pb;
+        if (ch.family == dz::MEGA_USER) {      // the user's density inside the mixture kernel's scheme: the code object's own instantiation (dz_set_likelihood_module)
+            const dz::Params* pp_ = (const dz::Params*)e->d_params; uint32_t g_ = g; int n_ = n; uint32_t M_ = Mvis; int64_t s_ = slot0, z_ = zappend; int seg_ = seg0;
+            void* args[] = {&pp_, &g_, &n_, &M_, &s_, &z_, &seg_, &pp};
+            const hipFunction_t fn = e->lk_gen_fn[(part.wide ? 2 : 0) + (full ? 1 : 0)];
             if (e->prof) {
                 hipEvent_t ka = prof_event(e), kb = prof_event(e);
                 e->ev[PR_GENERATIONS].emplace_back(ka, kb);
-                HIPCK(hipExtModuleLaunchKernel(e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)], gridm.x * blockm.x, 1, 1, blockm.x, 1, 1, ldsm, e->stream, args, nullptr, ka, kb, 0));
-            } else HIPCK(hipModuleLaunchKernel(e->lk_gen_fn[(p.ld > 128 ? 2 : 0) + (pbm ? 1 : 0)], gridm.x, 1, 1, blockm.x, 1, 1, (unsigned)ldsm, e->stream, args, nullptr));
-            DZCK(launch_check("dz_user_generations"));
-            launched();
-            e->last_variant = std::string(p.ld > 128 ? (pbm ? "k_generations_user<full,wide>" : "k_generations_user<wide>") : (pbm ? "k_generations_user<full>" : "k_generations_user")) + (rmulti ? " +ring" : "");
-            DZCK(after_launch());
-            if (slot0 >= 0) e->ntrace += n;
-            return 0;
+                HIPCK(hipExtModuleLaunchKernel(fn, grid.x * block.x, 1, 1, block.x, 1, 1, part.lds, e->stream, args, nullptr, ka, kb, 0));
+            } else HIPCK(hipModuleLaunchKernel(fn, grid.x, 1, 1, block.x, 1, 1, (unsigned)part.lds, e->stream, args, nullptr));
+            variant = part.wide ? (full ? "k_generations_user<full,wide>" : "k_generations_user<wide>") : (full ? "k_generations_user<full>" : "k_generations_user");
+        } else if (ch.family == dz::MEGA_MIX) {      // (wide: 128 < d <= 256, a lane owns four dimensions; multi: several burn-in generations per launch)
+            const auto kern = part.wide ? (full ? dz::k_generations_mix<true, false, 2> : dz::k_generations_mix<false, false, 2>)
+                            : part.f.multi ? (full ? dz::k_generations_mix<true, true> : dz::k_generations_mix<false, true>)
+                                           : (full ? dz::k_generations_mix<true> : dz::k_generations_mix<false>);
+            DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, kern, grid, block, part.lds, (const dz::Params*)e->d_params, g, n, Mvis, slot0, zappend, seg0, pp);
+            variant = part.wide ? (full ? "k_generations_mix<full,wide>" : "k_generations_mix<wide>")
+                    : part.f.multi ? (full ? "k_generations_mix<full,multi>" : "k_generations_mix<multi>") : (full ? "k_generations_mix<full>" : "k_generations_mix");
+        } else {      // the instantiations live in one translation unit per row-tile count (dz_mega_tu.hip)
+            dz::MegaLaunch ml;
+            static_cast<dz::MegaFlags&>(ml) = part.f;
+            ml.grid = grid; ml.block = block; ml.lds = part.lds; ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
+            ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = Mvis; ml.slot0 = slot0; ml.zappend = zappend; ml.seg0 = seg0; ml.publish = &pp;
+            if (e->prof) { ml.ka = prof_event(e); ml.kb = prof_event(e); e->ev[PR_GENERATIONS].emplace_back(ml.ka, ml.kb); }
+            if (nrt < 1 || nrt > 16) return fail("persistent kernel: ld out of range");
+            char buf[96]; snprintf(buf, sizeof buf, MEGA_LAUNCHERS[nrt](ml), part.f.ch, part.f.wpc);
+            variant += (variant.empty() ? "" : " + ") + std::string(buf);
+            e->last_kc = part.f.kc;
         }
-        if (p.ld > 128) {      // 128 < d <= 256: a lane owns four dimensions
-            if (pbm) DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, (dz::k_generations_mix<true, false, 2>), gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-            else DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, (dz::k_generations_mix<false, false, 2>), gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-        } else
-        if (multi) {
-            if (pbm) DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, (dz::k_generations_mix<true, true>), gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-            else DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, (dz::k_generations_mix<false, true>), gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-        } else
-        if (pbm) DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, dz::k_generations_mix<true>, gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-        else DZ_KLAUNCH(e, PR_GENERATIONS, e->stream, dz::k_generations_mix<false>, gridm, blockm, ldsm, (const dz::Params*)e->d_params, g, n, (uint32_t)visible_rows(e), slot0, append_last ? e->M : (int64_t)-1, seg0, pub);
-        DZCK(launch_check("k_generations_mix"));
-        launched();
-        e->last_variant = multi ? (pbm ? "k_generations_mix<full,multi>" : "k_generations_mix<multi>") : (pbm ? "k_generations_mix<full>" : "k_generations_mix");
-        if (p.ld > 128) e->last_variant = pbm ? "k_generations_mix<full,wide>" : "k_generations_mix<wide>";
-        if (rmulti) e->last_variant += " +ring";
-        DZCK(after_launch());
-        if (slot0 >= 0) e->ntrace += n;
-        return 0;
     }
-    const int nrt = p.ld / 16;
-    if (const int chd = mega_d2_chains(e)) {      // 128 < d <= 256
-        DZCK(upload_params(e));
-        dz::MegaLaunch ml;
-        const int wpcd = chd == 8 ? 2 : (chd == 4 ? 4 : 1);
-        const bool sp = (chd == 16 && mega_d2_two_pass(e)) || (chd == 8 && mega_d2_two_pass(e, 8));
-        ml.tri = p.tri != 0; ml.xlds = false; ml.pb = p.hard || p.have_prior || p.depairs > 1; ml.k1 = p.k == 1; ml.ch = chd; ml.wpc = wpcd; ml.redo = false; ml.sp = sp;
-        ml.grid = dim3((p.nl + chd - 1) / chd); ml.block = dim3(64 * chd * wpcd);
-        ml.lds = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, false, chd, false, false, true, rmulti ? e->ad_R1 : 0, sp).total;
-        ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
-        ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = (uint32_t)visible_rows(e); ml.slot0 = slot0; ml.zappend = append_last ? e->M : (int64_t)-1; ml.seg0 = seg0; ml.publish = &pub;
-        if (e->prof) { ml.ka = prof_event(e); ml.kb = prof_event(e); e->ev[PR_GENERATIONS].emplace_back(ml.ka, ml.kb); }
-        const char* name = nullptr;
-        switch (nrt) {
-            case 1: name = dz::mega_launch_d2_nrt1(ml); break; case 2: name = dz::mega_launch_d2_nrt2(ml); break;
-            case 3: name = dz::mega_launch_d2_nrt3(ml); break; case 4: name = dz::mega_launch_d2_nrt4(ml); break;
-            case 5: name = dz::mega_launch_d2_nrt5(ml); break; case 6: name = dz::mega_launch_d2_nrt6(ml); break;
-            case 7: name = dz::mega_launch_d2_nrt7(ml); break; case 8: name = dz::mega_launch_d2_nrt8(ml); break;
-            case 9: name = dz::mega_launch_nrt9(ml); break; case 10: name = dz::mega_launch_nrt10(ml); break;
-            case 11: name = dz::mega_launch_nrt11(ml); break; case 12: name = dz::mega_launch_nrt12(ml); break;
-            case 13: name = dz::mega_launch_nrt13(ml); break; case 14: name = dz::mega_launch_nrt14(ml); break;
-            case 15: name = dz::mega_launch_nrt15(ml); break; case 16: name = dz::mega_launch_nrt16(ml); break;
-            default: return fail("k_generations_d2: ld out of range");
-        }
-        char buf[96]; snprintf(buf, sizeof buf, name, chd, wpcd);
-        e->last_variant = buf;
-        if (rmulti) e->last_variant += " +ring";
-        DZCK(launch_check("k_generations_d2"));
-        launched();
-        DZCK(after_launch());
-        if (slot0 >= 0) e->ntrace += n;
-        return 0;
-    }
-    const int ch = mega_chains(e);
-    // waves per chain: 4 when a block holds only 4 chains (fewer than 8 chains per CU) -- the tries of a phase then run side by
-    // side (1024 chains: 238 -> 249 M proposals/s, 512: 120 -> 131); at 8 chains per block two waves per chain lose (405 -> 368).
-    // multitry off: one try, one wave per chain whatever the block size
-    const bool k1 = p.k == 1;
-    const bool xlds = mega_xlds(e);
-    const bool pb = p.hard || p.have_prior || p.depairs > 1 || mega_redo(e);      // the instantiations with the full proposal code
-    DZCK(upload_params(e));
-    // (a chain count just above whole rounds of blocks: the remainder in a second launch of smaller blocks -- mega_plan)
-    const MegaPlan plan = mega_plan(e);
-    const int split_c = plan.split_c, ch_b = plan.split_c != p.nl ? plan.ch_b : 0;
-    std::string variant;
-    auto launch_part = [&](int c0, int c1, int chp) -> int {
-        const int wpcp = (chp == 4 && !k1) ? 4 : 1;
-        size_t ldsp = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, pb ? true : xlds, chp, p.pb_lds != 0, false, false, rmulti ? e->ad_R1 : 0).total;
-        dz::Publish pp = pub; pp.c0 = c0; pp.c1 = c1;
-        if (multi) ldsp = mvn_multi_lds(e);      // (burnin_multi: one launch of 16-chain blocks, the states in LDS; + the states before the generation, + the table of probabilities)
-        else if (rmulti) { }
-        else
-        if (split_c != p.nl) { pp.PR = nullptr; pp.PC = nullptr; pp.shift = nullptr; }      // (a split generation's unit sums come from k_adapt_partials)
-        else if (publish && !ring && e->adapt_fused && (e->world == 1 || e->adapt_groups) && chp == 16 && wpcp == 1 && !k1 && p.k >= 3 && (pb || xlds)) {      // (the new and old states are read from LDS)
-            const size_t with_xo = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, true, chp, p.pb_lds != 0, true).total;
-            if (with_xo <= (size_t)160 * 1024) { fuse_adapt(); pp.shift = pub.shift; pp.PR = pub.PR; pp.PC = pub.PC; ldsp = with_xo; }
-        }
-        // the instantiations live in one translation unit per row-tile count (dz_mega_tu.hip)
-        dz::MegaLaunch ml;
-        ml.tri = p.tri != 0; ml.xlds = pb ? true : xlds; ml.pb = pb; ml.k1 = k1; ml.ch = chp; ml.wpc = wpcp; ml.redo = mega_redo(e);
-        ml.ahead = chp == 4 && wpcp == 4 && !pb && xlds && !k1 && p.k >= 3 && p.k <= 6;
-        ml.multi = multi;
-        // five tries (the reference's multitry=True), nothing but the chains' own steps to leave behind, ONE launch of 16-chain blocks: the instantiation with
-        // the try count compiled in and no publishing / adaptation code (same arithmetic, same draws, same name: k_generations' KC and PLAIN parameters)
-        ml.kc = (e->mega_kc && p.k == 5 && !pb && !k1 && (xlds || !p.tri) && chp == 16 && wpcp == 1 && split_c == p.nl && !pp.to && pp.multi == 0 && !pp.PR && !pp.PC && !pp.TOT && !pp.CNT) ? 5 : 0;
-        if (ml.kc) {      // ... which keeps its output cursors in LDS behind the layout (MegaLayout::off_cur); where they do not fit, the generic instantiation runs
-            const size_t with_cur = sizeof(double) * (size_t)dz::mega_layout(p.d, p.k, nrt, p.ncr, p.ngamma, p.tri != 0, xlds, chp, false, false, false, 0, false, true).total;
-            if (with_cur <= (size_t)160 * 1024) ldsp = with_cur; else ml.kc = 0;
-        }
-        ml.grid = dim3((c1 - c0 + chp - 1) / chp); ml.block = dim3(64 * chp * wpcp); ml.lds = ldsp; ml.st = e->stream; ml.ka = nullptr; ml.kb = nullptr;
-        ml.pp = (const dz::Params*)e->d_params; ml.g = g; ml.n = n; ml.M = (uint32_t)visible_rows(e); ml.slot0 = slot0; ml.zappend = append_last ? e->M : (int64_t)-1; ml.seg0 = seg0; ml.publish = &pp;
-        if (e->prof) { ml.ka = prof_event(e); ml.kb = prof_event(e); e->ev[PR_GENERATIONS].emplace_back(ml.ka, ml.kb); }
-        const char* name = nullptr;
-        switch (nrt) {
-            case 1: name = dz::mega_launch_nrt1(ml); break; case 2: name = dz::mega_launch_nrt2(ml); break;
-            case 3: name = dz::mega_launch_nrt3(ml); break; case 4: name = dz::mega_launch_nrt4(ml); break;
-            case 5: name = dz::mega_launch_nrt5(ml); break; case 6: name = dz::mega_launch_nrt6(ml); break;
-            case 7: name = dz::mega_launch_nrt7(ml); break; case 8: name = dz::mega_launch_nrt8(ml); break;
-            default: return fail("persistent kernel: ld > 128");
-        }
-        char buf[96]; snprintf(buf, sizeof buf, name, chp, wpcp);
-        variant += (variant.empty() ? "" : " + ") + std::string(buf);
-        e->last_kc = ml.kc;
-        return 0;
-    };
-    DZCK(launch_part(0, split_c, ch));
-    if (ch_b) DZCK(launch_part(split_c, p.nl, ch_b));
     e->last_variant = variant + (rmulti ? " +ring" : "");
-    DZCK(launch_check("k_generations"));
-    launched();
-    DZCK(after_launch());
+    DZCK(launch_check(ch.family == dz::MEGA_USER ? "dz_user_generations" : ch.family == dz::MEGA_MIX ? "k_generations_mix" : ch.family == dz::MEGA_D2 ? "k_generations_d2" : "k_generations"));
+    if (applies) { e->sh_cur ^= 1; point_shared(e); e->adapt_pending = false; }
+    if (mmode) { e->sh_cur ^= 1; point_shared(e); e->ad_applied = std::max(e->ad_applied, adapt_due(e, (int64_t)g + n - 1)); }
+    // end of the generation(s): positions -> adaptation -> history append (schedule S2)
+    const bool sharded = e->world > 1;      // (then the ranks own whole groups: their groups' sums travel, one exchange per launch -- adapt_finish_groups)
+    if (multi) { ProfScope ps(e, PR_ADAPT); DZCK(sharded ? adapt_finish_groups(e, g, n) : adapt_finish(e, false, g, n, true)); }      // the totals and dot products of the launch's n generations
+    else if (rmulti) {
+        ProfScope ps(e, PR_ADAPT);
+        hipLaunchKernelGGL(dz::k_adapt_partials_ring, dim3(sharded ? p.nl / 16 : (p.N + 15) / 16, n), dim3(1024), 0, e->stream, p, g, e->ad_R1, (const double*)e->d_posring, (long long)pos_stride,
+                           (const double*)e->d_PG, e->ad_nbp, e->d_PR, e->d_PC, (long long)e->ad_pr_stride, (long long)e->ad_pc_stride, e->d_x0ring, (const double*)e->d_x0start, p.off / 16);
+        DZCK(launch_check("k_adapt_partials_ring"));
+        DZCK(sharded ? adapt_finish_groups(e, g, n) : adapt_finish(e, false, g, n, true));
+        e->posring_gen = (int64_t)g + n - 1;
+        p.cp_new = e->d_posring + (size_t)(e->posring_gen % RP) * pos_stride;      // (what a later launch that is not of this kind measures its jumps from)
+    }
+    else if (publish) {
+        if (!e->adapt_groups) DZCK(exchange_rows(e, XK_POS, p.cp_new, 0));      // (ranks that own whole groups exchange their groups' sums instead: adapt_generation)
+        DZCK(adapt_generation(e, g, 0, p.N, fused, mega_follows));
+    }
+    for (int a = 0; a < napps; ++a) { DZCK(exchange_rows(e, XK_Z, p.Z, (size_t)e->M)); e->M += p.N; e->napp += 1; }
+    if (e->tempering) {          // (then n == 1) the temperature swap: after every chain's step and the updates above, as on the multi-kernel path
+        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot0, publish ? 1 : 0));
+        DZCK(launch_check("k_pt_swap"));
+    }
+    e->need_join = true;
+    e->draws_gen = -1;
+    e->gen = (int64_t)g + n;
+    for (auto& gcv : e->gen_c) gcv = e->gen;
     if (slot0 >= 0) e->ntrace += n;
     return 0;
 }
@@ -2138,7 +1888,7 @@ int dz_step(dz_engine* e, int64_t generations)
     e->gen = e->gen_c[0];
     e->p.own_cr = nullptr; e->p.own_g = nullptr;                   // lockstep generations read the shared probabilities;
     std::fill(e->own_init.begin(), e->own_init.end(), 0);          // a later single-chain step starts from them again
-    const bool mega = mega_eligible(e);
+    const bool mega = mega_select(e);
     e->stream_prop_gen = -1;
     for (int64_t i = 0; i < generations;) {
         DZCK(peer_check(e));            // a gate that gave up is fatal: nothing more is queued behind it

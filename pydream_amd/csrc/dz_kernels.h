@@ -8,10 +8,10 @@
 // Citations are to /root/reference/pydream/Dream.py unless stated.
 #pragma once
 #include "dz_device.h"
+#include "dz_mega_select.h"      // MAXK, tri_row_offset and the persistent kernels' LDS layout: shared with the host-side selection
 
 namespace dz {
 
-constexpr int MAXK = 32;      // multitry limit (tries 17..32: the multi-kernel path; the persistent kernels hold a generation's draw slots in one wave's lanes: multitry <= 15)
 constexpr int MAXPAIR = 8;    // DEpairs limit
 
 // per-chain control decisions of one generation, computed once (lane-parallel) instead of by every wave
@@ -117,9 +117,6 @@ static_assert(sizeof(Params) == 784 && sizeof(Publish) == 168, "Params / Publish
 #define DZ_WSTAMP(i_) do { } while (0)
 #define DZ_W0STAMP(i_) do { } while (0)
 #endif
-
-// offset of k-row r in the packed triangular layout: row block b = r/16 has 16*(b+1) columns
-__host__ __device__ inline int tri_row_offset(int r) { const int b = r >> 4; return 128 * b * (b + 1) + (r - 16 * b) * 16 * (b + 1); }
 
 // temperature of local chain c (Dream.astep's T argument, Dream.py:193)
 DZ_DEV double chain_T(const Params& p, int c) { return p.Tc ? p.Tc[p.off + c] : p.T; }

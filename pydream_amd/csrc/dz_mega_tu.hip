@@ -17,65 +17,40 @@ namespace dz {
 #define DZ_STR_(x) #x
 #define DZ_STR(x) DZ_STR_(x)
 
-#if DZ_TU_NRT > 8
-// 128 < ld <= 256: k_generations_d2 (dz_megakernel_d2.h) -- the matrix read from L2, two 128-dimension chunks per lane
-const char* DZ_CAT(mega_launch_nrt, DZ_TU_NRT)(const MegaLaunch& a)
+// k_generations_d2 (dz_megakernel_d2.h): the triangular factor read from L2, CH chains x WPC waves per block, multitry off (K1), the proposal set in two passes
+// (SP).  The full / lean branch is taken here and names what it launched.
+template <int CH, int WPC, bool K1, bool SP>
+static const char* launch_d2(const MegaLaunch& a)
 {
-#define DZ_D2(K1_, NAME_)                                                                                                                 \
-    do {                                                                                                                                   \
-        if (a.pb) {                                                                                                                        \
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, K1_, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, \
-                                  a.slot0, a.zappend, a.seg0, *a.publish);                                                                         \
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full" NAME_ ">";                                                 \
-        }                                                                                                                                  \
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, K1_>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, \
-                              a.slot0, a.zappend, a.seg0, *a.publish);                                                                             \
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean" NAME_ ">";                                                     \
-    } while (0)
-    if (a.k1) DZ_D2(true, ",k1");          // (the host only sends the triangular factor at 16 chains per block here: mega_d2_chains)
-    if (a.sp && a.ch == 16) {              // 16 chains per block, the proposal set in two passes over k - 1 point tiles (round 6)
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, false, true, 1, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                                  a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full,two-pass>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, false, false, 1, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                              a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean,two-pass>";
+    if (a.pb) {
+        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, CH, K1, true, WPC, SP>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
+        return K1 ? "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full,k1>" : SP ? "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full,two-pass>" : "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full>";
     }
-    if (a.ch == 4) {                       // ... 4 chains x 4 waves where not even 8 chains' tiles fit (256 dimensions at 8 tries)
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 4, false, true, 4>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                                  a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 4, false, false, 4>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                              a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean>";
-    }
-    if (a.ch == 8 && a.sp) {               // 8 chains x 2 waves with the two-pass set (256 dimensions at 8 tries)
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, true, 2, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                                  a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full,two-pass>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, false, 2, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                              a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean,two-pass>";
-    }
-    if (a.ch == 8) {                       // ... or, where the point tiles of 16 chains do not fit LDS (d > ~228 at 5 tries), at 8 chains x 2 waves (round 6)
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, true, 2>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                                  a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, false, 2>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M,
-                              a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean>";
-    }
-    DZ_D2(false, "");
-#undef DZ_D2
+    hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, CH, K1, false, WPC, SP>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
+    return K1 ? "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean,k1>" : SP ? "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean,two-pass>" : "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean>";
 }
+// 128 < ld <= 256 (two 128-dimension chunks per lane): 16 chains per block, with multitry off or the two-pass set where the tiles of k tries do not fit (229..256
+// dimensions at 5 tries, round 6); 8 chains x 2 waves where the point tiles of 16 chains do not fit (d > ~228 at 5 tries), with the two-pass set at 256 dimensions
+// and 8 tries; 4 chains x 4 waves where not even those fit.
+// ld <= 128 (one chunk per lane), where the point tiles of 16 chains do NOT fit next to the matrix in LDS (113..128 dimensions at 5 tries, 100 dimensions at 8 or
+// more) and (round 6) for more than 15 tries: multitry on and one pass only -- 16 chains per block, 8 x 2 (100 dimensions at 16..20 tries), 4 x 4 (24..32 tries at
+// 100 dimensions, 20..32 at 128).  (The host only sends the triangular factor here: mega_d2_chains.)
+// (A template so that the WIDE branch is not instantiated in the units with ld <= 128: their set of kernels holds no multitry-off or two-pass d2 instantiation.)
+template <bool WIDE = (DZ_TU_NRT > 8)>
+static const char* launch_d2_ch(const MegaLaunch& a)
+{
+    if constexpr (WIDE) {
+        if (a.k1) return launch_d2<16, 1, true, false>(a);
+        if (a.sp && a.ch == 16) return launch_d2<16, 1, false, true>(a);
+        if (a.sp && a.ch == 8) return launch_d2<8, 2, false, true>(a);
+    }
+    if (a.ch == 4) return launch_d2<4, 4, false, false>(a);
+    if (a.ch == 8) return launch_d2<8, 2, false, false>(a);
+    return launch_d2<16, 1, false, false>(a);
+}
+
+#if DZ_TU_NRT > 8
+const char* DZ_CAT(mega_launch_nrt, DZ_TU_NRT)(const MegaLaunch& a) { return launch_d2_ch<>(a); }
 #else
 template <bool TRI, bool X, int CH, int WPC, bool PB, bool K1>
 static const char* launch_one(const MegaLaunch& a)
@@ -140,45 +115,13 @@ static const char* launch_ch(const MegaLaunch& a)
     return launch_one<TRI, X, 4, 4, PB, false>(a);
 }
 
-// (priors / boundaries / several pairs: only with the chain states in LDS -- mega_eligible -- which keeps the number of kernels down)
+// (priors / boundaries / several pairs: only with the chain states in LDS -- mega_choose -- which keeps the number of kernels down)
 const char* DZ_CAT(mega_launch_nrt, DZ_TU_NRT)(const MegaLaunch& a)
 {
+    if (a.d2) return launch_d2_ch<>(a);
     if (a.pb) return a.tri ? launch_ch<true, true, true>(a) : launch_ch<false, true, true>(a);
     if (a.tri) return a.xlds ? launch_ch<true, true, false>(a) : launch_ch<true, false, false>(a);
     return a.xlds ? launch_ch<false, true, false>(a) : launch_ch<false, false, false>(a);
-}
-// d <= 128 with the point tiles of 16 chains NOT fitting next to the matrix in LDS (113..128 dimensions at 5 tries, 100 dimensions at 8 or more), and
-// (round 6) more than 15 tries at any d <= 128: k_generations_d2 with one chunk per lane -- 16 chains per block, or 8 chains x 2 waves where the tiles of 16
-// do not fit even without the matrix (100 dimensions at 16..20 tries)
-const char* DZ_CAT(mega_launch_d2_nrt, DZ_TU_NRT)(const MegaLaunch& a)
-{
-    if (a.ch == 4) {                       // 4 chains x 4 waves: 24..32 tries at 100 dimensions, 20..32 at 128
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 4, false, true, 4>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 4, false, false, 4>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean>";
-    }
-    if (a.ch == 8) {
-        if (a.pb) {
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, true, 2>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full>";
-        }
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 8, false, false, 2>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish);
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean>";
-    }
-#define DZ_D2(K1_, NAME_)                                                                                                                 \
-    do {                                                                                                                                   \
-        if (a.pb) {                                                                                                                        \
-            hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, K1_, true>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish); \
-            return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,full" NAME_ ">";                                                 \
-        }                                                                                                                                  \
-        hipExtLaunchKernelGGL((k_generations_d2<DZ_TU_NRT, true, 16, K1_>), a.grid, a.block, a.lds, a.st, a.ka, a.kb, 0, a.pp, a.g, a.n, a.M, a.slot0, a.zappend, a.seg0, *a.publish); \
-        return "k_generations_d2<" DZ_STR(DZ_TU_NRT) ",tri,xhbm,%d,%d,lean" NAME_ ">";                                                     \
-    } while (0)
-    DZ_D2(false, "");          // (multitry on only: the multitry-off kernels' 16-chain layout always fits)
-#undef DZ_D2
 }
 #endif      // DZ_TU_NRT <= 8
 

@@ -30,69 +30,8 @@ namespace dz {
 
 constexpr int DZ_MAX_REDRAWS_DEV = 64;                                  // == DZ_MAX_REDRAWS (include/dreamzs.h; checked in dz_engine.hip)
 constexpr unsigned long long DZ_REDRAW_KEY_STEP_DEV = 0x9E3779B97F4A7C15ull;   // == DZ_REDRAW_KEY_STEP
-constexpr int MEGA_CHAINS = 16;      // chains (= waves) per block at full size; 8 or 4 when there are too few chains to give every CU a block
-
-// Output cursors of the <.., KC, PLAIN> instantiations: where a chain's stores of generation index 0 go, as 64-bit byte addresses in LDS.  What a chain writes per
-// generation moves by a launch constant (a trace row: ld doubles; a history append: N rows; a scalar column: nl elements), so the prologue builds each address
-// once and the generation loop adds index x stride -- no 64-bit address is rebuilt from kernel arguments and Params fields that would have to live in scalar
-// registers (or their spill lanes) across the whole loop.  Per chain: the trace row | the append row (for an archive of 0 rows: + M rows at use) | the state row |
-// the five scalar trace columns (log p, moved, try, CR index, snooker) | log prior | log likelihood.  Per block: the chain count nl, the columns' stride (one word
-// and one of padding: the area stays a whole number of 16-byte pairs).
-constexpr int MEGA_CUR_WORDS = 10, MEGA_CUR_BLOCK = 2;
+// (MEGA_CHAINS, the output cursors' MEGA_CUR_WORDS / MEGA_CUR_BLOCK and the LDS layout, MegaLayout / mega_layout: dz_mega_select.h)
 enum { CUR_TX = 0, CUR_APP = 1, CUR_X = 2, CUR_LOGP = 3, CUR_MOVED = 4, CUR_TRY = 5, CUR_CR = 6, CUR_SNK = 7, CUR_LPRI = 8, CUR_LLIK = 9 };
-
-struct MegaLayout { int LDM, LDP, rows, off_P, off_q, off_sP, off_sS, off_sL, off_rP, off_rS, off_mu, off_pr, off_st, off_dec, off_gt, off_X, off_pc, pcn, off_Xo, off_tab, off_cur, total; };
-
-// point rows of a block: try i of chain c at row i*ch + c; tiles are 16 consecutive rows, from row 0 (k tries) or from
-// row ch (the k-1 reference tries); rows past the last point stay zero
-__host__ __device__ inline int mega_rows(int k, int ch)
-{
-    const int a = 16 * ((k * ch + 15) / 16), b = ch + 16 * (((k - 1) * ch + 15) / 16);
-    return a > b ? a : b;
-}
-// pb: room for the per-dimension prior / boundary constants of the full-code instantiations (PBConsts: five double arrays and one int
-// array of pcn = 16 nrt entries)
-// xo: room for the chains' states as they were at the start of the launch (crossover burn-in: the block's adaptation sums need the jumps)
-// nomat: the matrix is NOT staged (k_generations_d2, 128 < d <= 256: it does not fit next to the point tiles and is read from L2)
-// ntab: rows of the table of crossover / gamma-level probabilities per generation of the launch (adapt_lag >= 1: several burn-in generations per
-// launch, the MG instantiations; rows of (ncr + ngamma + 1) & ~1 doubles)
-// cur (k_generations<.., KC, PLAIN>): room for the launch's output cursors -- MEGA_CUR_WORDS 64-bit words per chain and MEGA_CUR_BLOCK for the block (see the kernel's prologue)
-// sp (k_generations_d2<.., SP>, round 6): the proposal set goes through the point tiles in two passes (tries 0 .. k-2, then the last one), the selected
-// proposal stays in registers: k - 1 tries' rows instead of k
-__host__ __device__ inline MegaLayout mega_layout(int d, int k, int nrt, int ncr, int ngamma, bool tri, bool xlds, int ch = MEGA_CHAINS, bool pb = false, bool xo = false, bool nomat = false, int ntab = 0,
-                                                  bool sp = false, bool cur = false)
-{
-    MegaLayout L;
-    const int ks4 = 4 * ((d + 3) / 4);
-    L.LDM = d + 2;                    // dense matrix row (k index c): d entries + pad; rows d..ks4-1 are zero
-    L.LDP = ks4 + 1;                  // point row: zero padded to the k-steps; odd stride keeps the A-layout reads (16 rows x 4 cols) off one bank
-    L.off_P = nomat ? 0 : (tri ? tri_row_offset(ks4) : ks4 * L.LDM + 16);       // (+16: the last row tile's column reads run past the last row's end)
-    L.rows = sp ? 16 * (((k - 1) * ch + 15) / 16) : mega_rows(k, ch);
-    L.off_q = L.off_P + L.rows * L.LDP;
-    L.off_sP = L.off_q + L.rows * nrt;
-    L.off_sS = L.off_sP + ch * k;
-    L.off_sL = L.off_sS + ch * k;
-    L.off_rP = L.off_sL + ch * k;
-    L.off_rS = L.off_rP + ch * k;
-    L.off_mu = L.off_rS + ch * k;
-    L.off_pr = L.off_mu + ks4 + 4;               // (mu zero padded to the k-steps) crossover / gamma-level probabilities
-    L.off_st = L.off_pr + ncr + ngamma + 2 - ((ncr + ngamma) & 1);      // (the offsets behind stay even; one word of the gap: the log prior of a point inside every uniform support, PBConsts::inside) per chain: lprior, llike, sel|fin
-    L.off_dec = L.off_st + 4 * ch;      // per chain and generation: u_sel, u_acc, snooker, CR index, gamma level
-    L.off_gt = L.off_dec + 8 * ch;      // gamma_arr[level-1][0][:]
-    L.off_X = L.off_gt + ngamma * d + (d & 1);   // chain states (XLDS)
-    L.total = L.off_X + (xlds ? ch * L.LDP : 0);
-    L.total += L.total & 1;
-    L.off_pc = L.total; L.pcn = 16 * nrt;
-    if (pb) L.total += 5 * L.pcn + L.pcn / 2;
-    L.total += L.total & 1;
-    L.off_Xo = L.total;
-    if (xo) L.total += ch * L.LDP + ((ch * L.LDP) & 1);
-    L.off_tab = L.total;
-    L.total += ntab * ((ncr + ngamma + 1) & ~1);
-    L.off_cur = L.total;
-    if (cur) L.total += MEGA_CUR_WORDS * ch + MEGA_CUR_BLOCK;
-    return L;
-}
 
 // Unit u (0 .. ntl*NRT-1) in dealing order: row tile first (heaviest first for the triangular factor), then point tile.
 // Wave w of tw takes the units w, 2tw-1-w, 2tw+w, ... (snake), which evens out the k-steps per wave and per SIMD.
@@ -931,10 +870,7 @@ __global__ __launch_bounds__(64 * CH * WPC) void k_generations(const Params* __r
 // generations of the launch independently (its k points in an LDS region it alone touches, its state in registers).
 // Eligibility: multitry 1 or >= 3, ld <= 128, up to 32 components; priors / boundaries / several pairs run the <true> instantiation.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int MIXW = 4;       // waves (= chains) per block
-
-__host__ __device__ inline int mega_mix_wave_doubles(int d, int k, int J) { const int n = k * (4 * ((d + 3) / 4) + 1) + 6 * k + k * J + 8; return n + (n & 1); }
-
+// (MIXW waves per block, mega_mix_wave_doubles of LDS per wave: dz_mega_select.h)
 // (blocks of MIXW waves; blocks of 16 -- one adaptation unit -- inside the crossover burn-in, where the block adds its unit's sums)
 // PB (round 4): per-dimension priors, hard boundaries, several DE pairs -- the full proposal code and the prior evaluation (constants from
 // global memory: this kernel has no block-wide staging); the flat, unbounded, one-pair case keeps the lean instantiation.

@@ -9,7 +9,7 @@ append only once history_lag of them are made, so with appends behind generation
 DZ_MEGA_SEGS says, and 25 generations end (21..24) before any launch holds two.  The next one, 21..40, does: the append of generation 30 in the
 middle of the launch -- the archive length the later generations draw from grows inside the kernel -- and that of 40 at its end, which is the
 schedule the headline runs at.  Each case checks the number of launches, and the lag-3 cases run a third time with DZ_MEGA_SEGS=1.
-Population: 3073 chains -- the smallest mega_plan (dz_engine.hip) gives 16-chain blocks on the MI355X's 256 CUs: up to 3072 chains 256 blocks
+Population: 3073 chains -- the smallest mega_block_plan (dz_mega_select.h) gives 16-chain blocks on the MI355X's 256 CUs: up to 3072 chains 256 blocks
 of 12 chains are one round at 0.82 of a 16-chain block's time; 3073 chains are two rounds of 12 (1.64), two of 8 (1.34), or ONE round of 193
 blocks of 16 (1.0), the last of which holds a single chain -- so the blocks' inactive-chain path runs as well."""
 import numpy as np
