@@ -85,6 +85,7 @@ class _Network:
         self.mono, self.events, self.equilibrate = like._monomials(), like._max_events(), like._equilibrates()
         self.items, self.lanes, self.noise = like.conditions is not None, like.lanes_per_point, like.noise
         self.inputs = [(u.species, u.gain) for u in like.inputs or ()]      # (species, gain): the tables are the data block's
+        self.view = like._view_size() if like._has_view() else 0            # P of a network whose conditions view the point (csrc/dz_ode.h, VIEWS)
         self.R = len(self.reactions)
         self.N = np.zeros((self.S, self.R), dtype=np.int64)
         for r, (reac, prod, _) in enumerate(self.reactions):
@@ -297,6 +298,7 @@ def _net_source(net, body):
     L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (net.S, net.R, len(net.observables))]
     L += ["    static constexpr int EVENTS = %d;" % net.events] if net.events else []
     L += ["    static constexpr bool EQUILIBRATE = true;"] if net.equilibrate else []
+    L += ["    static constexpr int VIEW = %d;" % net.view] if net.view else []
     L += _input_members(net, net.drive) if net.inputs else []
     L += body + (_monomial_members(net.mono) if net.mono else []) + (_noise_members(net) if net.noise else [])
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(net.S, net.observables) + ["    }", "};", entries, ""]

@@ -13,6 +13,7 @@ ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated 
 ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction
 ODE_MAX_INPUTS = 4          # inputs=[Input, ...]: piecewise-linear time courses, each on a species of its own
 ODE_MAX_INPUT_KNOTS = 128   # the working knots of one experiment, over all its inputs together (csrc/dz_ode.h: MAX_INPUT_KNOTS)
+ODE_MAX_VIEW_COORDINATES = 128      # conditions=[dict(params=...)]: P, one more than the largest index the network reads (csrc/dz_ode.h: VIEWS)
 _INT = (int, np.integer)
 _REAL = (int, np.integer, float, np.floating)
 

@@ -185,6 +185,34 @@
 //     0, the input species at the block's 0), as it ignores events.
 // Every loop stays bounded: at most T + Emax + Kmax segments.
 //
+// VIEWS (MassActionODELogLike(conditions=[dict(params={i: target}), ...])): condition-specific parameters.  Condition c does not read
+// the point x but its VIEW of it, x'_c = V_c(x), a row of P doubles, P one more than the largest index the network reads: entry i is
+// x[j] for a target j (an int) or the number v for a target v (a float; the coordinate's value, not the constant: a bare rate index
+// under "log10" then gives 10**v), and x[i] itself where the condition says nothing.  A network of an object in which some condition
+// has a non-empty mapping carries
+//     static constexpr int VIEW = P;                                   1..128
+// and every experiment's block grows at its very end -- behind the input knots, the equilibration's six doubles, the event records, or
+// sd, whichever is last -- by 2 P doubles, the pairs (j_i, v_i) for i = 0..P-1: j_i >= 0 selects x[j_i], j_i = -1 selects v_i.  A
+// condition without a mapping gets the identity (i, 0), an index nothing reads (-1, 0).  Views exist only with conditions, so the
+// table's address is the sub-block's end, blk + stride - 2 P.  The block, the source and the code object of a network without the
+// member are what they always were.  The contract, the same in both builds and every shape:
+//   * SELECT, NO ARITHMETIC: x'[i] is a select between x[j_i] and v_i (view_entry): the bits are exactly one or the other, and x[j_i]
+//     is not read where j_i < 0.  A coordinate of the point that a condition does not read has no effect on that condition's term,
+//     whatever it holds, NaN included.  An index mapped away in every condition is FORMAL: it is never read from the point and may lie
+//     at or beyond the point's length d; Python validates 0 <= j_i < d, so a table never indexes outside the point's row.
+//   * WHAT ITEM c RETURNS: its term l_c(x) has the bits of the object of condition c alone, made without a view, evaluated at the row
+//     x'_c -- everything an item evaluates (rate constants, slots, gains, noise values, y0 Monomials, scale) reads x'_c; its simulate
+//     slice, steps and resting state likewise.
+//   * LIVENESS IS PER ITEM: a non-finite coordinate that condition 1 replaces and condition 0 reads makes l_0 = -inf and leaves l_1
+//     finite.  The sum stays ((l_0 + l_1) + l_2) + ...
+//   * THE HOST BUILD evaluates the rate constants, slots, gains and noise values per condition (integrate_conditions: integrate_point
+//     at x'_c), where without a view it evaluates them once per point.
+//   * CONSTRAINTS are statements about the point: Python refuses one whose Monomial reads a coordinate that any condition replaces, so
+//     they give the same value under every view; they stay on condition 0's term and are evaluated through condition 0's view.
+//   * WHERE x' LIVES: one lane per item: a lane-private array of P doubles filled by a loop unrolled over the compile-time P, every
+//     index a constant, handed to the generated code in the point's place; a lane group or a wave per item: P more doubles at the end
+//     of the group's LDS row (dz_ode_group.h), lane r gathering i = r, r + L, ..., one block-wide barrier ahead of the rate constants.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -330,6 +358,38 @@ template <class Net, class = void> struct has_noise { static constexpr bool valu
 template <class Net> struct has_noise<Net, decltype((void)Net::NOISE)> { static constexpr bool value = true; static constexpr int count = 2 * Net::O; };
 // the doubles of a point's noise values (an array of at least one)
 template <class Net> constexpr int noise_doubles() { return has_noise<Net>::count > 0 ? has_noise<Net>::count : 1; }
+
+// ... and views (the head of the file, VIEWS): P viewed coordinates per condition, 2 P doubles at the end of every experiment's block
+template <class Net, class = void> struct has_view { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_view<Net, decltype((void)Net::VIEW)> {
+    static constexpr bool value = true;
+    static constexpr int count = Net::VIEW;
+    static_assert(Net::VIEW >= 1 && Net::VIEW <= 128, "1..128 viewed coordinates");
+};
+// the doubles of an item's viewed row (an array of at least one)
+template <class Net> constexpr int view_doubles() { return has_view<Net>::count > 0 ? has_view<Net>::count : 1; }
+
+// Entry i of a condition's view: a select between x[j_i] and v_i, no arithmetic; x is not read where j_i < 0.
+DZO_HD double view_entry(const double* x, const double* tab, int i)
+{
+    const double j = tab[2 * i], v = tab[2 * i + 1];
+    return j >= 0.0 ? x[(int)j] : v;
+}
+
+// The row an item reads in the point's place: for a network with a view xv[P], gathered from the table at the end of the item's
+// sub-block (blk, of stride doubles); else the point's own row.
+template <class Net>
+DZO_HD const double* viewed_row(const double* x, const double* blk, long long stride, double* xv)
+{
+    if constexpr (has_view<Net>::value) {
+        const double* tab = blk + stride - 2 * Net::VIEW;
+#pragma unroll
+        for (int i = 0; i < Net::VIEW; ++i) xv[i] = view_entry(x, tab, i);
+        return xv;
+    } else {
+        return x;
+    }
+}
 
 // The point's noise values nz[2 O] in the order of the contract; false if one of them says that the point is not live.
 template <class Net>
@@ -939,6 +999,20 @@ DZO_HD double integrate_conditions(const double* x, const double* hdr, double* t
 {
     const int C = (int)hdr[0];
     const long long stride = (long long)hdr[1], per = (long long)(int)hdr[2 + 5] * Alg::Net::O;
+    if constexpr (has_view<typename Alg::Net>::value) {      // (the head of the file, VIEWS: everything per condition, at its own row)
+        double xv[view_doubles<typename Alg::Net>()], total = 0.0;
+        int steps = 0;
+        for (int c = 0; c < C; ++c) {
+            const double* blk = hdr + 2 + c * stride;
+            int st = 0;
+            const double v = integrate_point<Alg>(viewed_row<typename Alg::Net>(x, blk, stride, xv), blk, sim ? sim + c * per : nullptr, &st, c == 0);
+            if (terms) terms[c] = v;
+            total = c == 0 ? v : total + v;
+            steps += st;
+        }
+        if (nsteps_out) *nsteps_out = steps;
+        return total;
+    }
     double k[rate_doubles<typename Alg::Net>()];
     double nz[noise_doubles<typename Alg::Net>()];
     const bool rated = Alg::rates(x, k);
@@ -1033,8 +1107,12 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     extern "C" void dzode_equilibrate(const double* X, long long n, int ld, const double* blk, double* yss, int* attempts)              \
     {                                                                                                                                    \
         const long long C = (long long)blk[0], stride = (long long)blk[1];                                                               \
-        for (long long w = 0; w < n * C; ++w)                                                                                            \
-            dzode::equilibrate_point<ALG>(X + (w / C) * ld, blk + 2 + (w % C) * stride, yss + w * ALG::Net::S, attempts + w);           \
+        double xv[dzode::view_doubles<ALG::Net>()];                                                                                      \
+        for (long long w = 0; w < n * C; ++w) {                                                                                          \
+            const double* sub = blk + 2 + (w % C) * stride;                                                                              \
+            dzode::equilibrate_point<ALG>(dzode::viewed_row<ALG::Net>(X + (w / C) * ld, sub, stride, xv), sub, yss + w * ALG::Net::S,    \
+                                          attempts + w);                                                                                 \
+        }                                                                                                                                \
     }                                                                                                                                    \
     DZODE_HOST_COMMON(ALG)
 
@@ -1065,7 +1143,9 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], i = w / C;                                                    \
         const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
         DZODE_FENCE(blk);          /* (one opaque pointer per lane: see below) */                                                        \
-        like[w] = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, nullptr, nullptr, w == i * C);                           \
+        double xv[dzode::view_doubles<NET>()];     /* (a network with a view: the item's own row, every index a constant) */            \
+        const double* x = dzode::viewed_row<NET>(X + i * ld, blk, stride, xv);                                                           \
+        like[w] = dzode::integrate_point<dzode::OneLane<NET>>(x, blk, nullptr, nullptr, w == i * C);                                     \
     }
 #elif defined(__HIP__)
 // PREDICTION (MassActionODELogLike.device().simulate): the same generated source behind a leading `#define DZODE_PREDICT 1` is a
@@ -1103,7 +1183,9 @@ __device__ __forceinline__ void predict_finish(double term, const double* blk, i
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], i = w / C;                                                    \
         const double* blk = hdr + 2 + (w - i * C) * stride;                                                                              \
         DZODE_FENCE(blk);                                                                                                                \
-        const double v = dzode::integrate_point<dzode::OneLane<NET>>(X + i * ld, blk, out + w * out_ld, nullptr, w == i * C);           \
+        double xv[dzode::view_doubles<NET>()];                                                                                           \
+        const double* x = dzode::viewed_row<NET>(X + i * ld, blk, stride, xv);                                                           \
+        const double v = dzode::integrate_point<dzode::OneLane<NET>>(x, blk, out + w * out_ld, nullptr, w == i * C);                     \
         like[w] = v;                                                                                                                     \
         dzode::predict_finish(v, blk, NET::O, out + w * out_ld);                                                                         \
     }

@@ -241,6 +241,30 @@ struct Replica<Net, 64> {                     // a wave: its S doubles of LDS; a
 template <class Net, int L>
 __device__ __forceinline__ double* noise_row(double* ks) { return ks + ROW_VALUES<Net> + 1 + (L == 64 ? Net::S : 0); }
 
+// The item's viewed row (dz_ode.h's VIEWS) in its row of LDS: P doubles behind everything else.
+template <class Net, int L>
+__device__ __forceinline__ double* view_row(double* ks) { return noise_row<Net, L>(ks) + has_noise<Net>::count; }
+
+// The row a group's item reads in the point's place.  A network with a view: lane r gathers the entries r, r + L, ... of the view
+// from the table at the end of the item's sub-block (item w of C to a point: sub-block w % C of the block behind hdr, stride doubles
+// each) into the group's row, and ONE block-wide barrier follows, before group_rates reads them; every group of the block gets here,
+// the padding groups with the last item's view.  Else: the point's own row, no barrier, and nothing computed from the other arguments
+// (the code objects of networks without a view are what they were).
+template <class Net, int L>
+__device__ __forceinline__ const double* group_viewed_row(const double* x, const double* hdr, long long w, long long C, long long stride, double* ks,
+                                                          int r)
+{
+    if constexpr (has_view<Net>::value) {
+        double* xv = view_row<Net, L>(ks);
+        const double* tab = hdr + 2 + (w - (w / C) * C + 1) * stride - 2 * Net::VIEW;
+        for (int i = r; i < Net::VIEW; i += L) xv[i] = view_entry(x, tab, i);
+        __syncthreads();
+        return xv;
+    } else {
+        return x;
+    }
+}
+
 template <class Net, int L>
 __device__ __forceinline__ bool group_rates(const double* x, double* ks, int r)
 {
@@ -462,9 +486,9 @@ struct Group {
 };
 
 // The doubles of static LDS a point's lanes share: R + 1 rate constants (with rate laws: R + SLOTS + 1, the Hill slots behind the rate
-// constants; with inputs: 2 I more, their gains and drives behind those), for a wave per point the S doubles of its state behind them, and for a network with sampled noise its 2 O values last.
+// constants; with inputs: 2 I more, their gains and drives behind those), for a wave per point the S doubles of its state behind them, for a network with sampled noise its 2 O values and for one with a view (dz_ode.h's VIEWS) the item's P viewed coordinates last.
 template <class Net, int L>
-constexpr int group_lds_row() { return ROW_VALUES<Net> + 1 + (L == 64 ? Net::S : 0) + has_noise<Net>::count; }
+constexpr int group_lds_row() { return ROW_VALUES<Net> + 1 + (L == 64 ? Net::S : 0) + has_noise<Net>::count + has_view<Net>::count; }
 #endif
 
 #if !defined(__HIP__)
@@ -628,7 +652,7 @@ struct HostGroup {
         const bool valid = w < n;                                                                                                        \
         const double* hdr = (const double*)data;                                                                                         \
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], wv = valid ? w : n - 1, i = wv / C;                           \
-        const double* x = X + i * ld;                                                                                                    \
+        const double* x = dzode::group_viewed_row<NET, LANES>(X + i * ld, hdr, wv, C, stride, ks[g], r);                                 \
         const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
         __syncthreads();                                                                                                                 \
         const double v = dzode::integrate(dzode::Group<NET, LANES>{ks[g], r, x}, hdr + 2 + (wv - i * C) * stride, valid && good,        \
@@ -671,7 +695,7 @@ struct HostGroup {
         const bool valid = w < n;                                                                                                        \
         const double* hdr = (const double*)data;                                                                                         \
         const long long C = (long long)hdr[0], stride = (long long)hdr[1], wv = valid ? w : n - 1, i = wv / C;                           \
-        const double* x = X + i * ld;                                                                                                    \
+        const double* x = dzode::group_viewed_row<NET, LANES>(X + i * ld, hdr, wv, C, stride, ks[g], r);                                 \
         const double* blk = hdr + 2 + (wv - i * C) * stride;                                                                             \
         const bool good = dzode::group_rates<NET, LANES>(x, ks[g], r);                                                                   \
         __syncthreads();                                                                                                                 \

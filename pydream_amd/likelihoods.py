@@ -10,7 +10,8 @@ from . import _kernel_cache, _ode_source      # noqa: F401
 from ._kernel_cache import _build_cached, _compiler_version, compile_device_kernel, csrc_dir, kernel_cache_dir      # noqa: F401
 from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate_indices, _slot_indices
 from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
-                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_INPUT_KNOTS, ODE_MAX_INPUTS, ODE_MAX_RATE_FACTORS, ODE_WAVE_LIMITS,
+                          ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_INPUT_KNOTS, ODE_MAX_INPUTS, ODE_MAX_RATE_FACTORS, ODE_MAX_VIEW_COORDINATES,
+                          ODE_WAVE_LIMITS,
                           Hill, Input, Monomial, Noise, RateLaw, _checked_constant, _is_int, _is_real)
 
 
@@ -283,7 +284,8 @@ class MassActionODELogLike:
     Monomials and events work as below.
 
     conditions: the same network measured in several experiments (a dose series, knock-outs, wash-outs) -- a sequence of 1..64
-    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events", "equilibrate", "inputs"; a missing key is the constructor's own argument,
+    (ODE_MAX_CONDITIONS) mappings with the optional keys "y0", "data", "sd", "events", "equilibrate", "inputs", "params" (below: Condition-specific
+    parameters); a missing key is the constructor's own argument,
     which (y0, data, sd) may be None when every condition gives its own.  Network, t, t0, observables, tolerances and max_steps are shared.  The log-likelihood of a
     point is ((l_0 + l_1) + l_2) + ..., l_c exactly what this class gives for condition c alone (-inf if any integration fails).  On the
     device a launch covers points x C ITEMS, item w = condition w % C of point w // C (kernel dz_ode_item_batch or
@@ -428,6 +430,37 @@ class MassActionODELogLike:
     of Nones generate the source and the data block the object always had.  Not supported: Student-t residuals, a per-condition
     noise, a sampled offset on the log scale; fixed_steps has no likelihood and ignores noise.
 
+    Condition-specific parameters: a condition's "params" = {i: target} makes the experiments differ in the SYSTEM and not only in what
+    is done to it -- a knock-down or a mutant that changes a rate constant, an inhibitor in the treated arms only, a sampled readout
+    scale per gel, a noise level per assay, a cell line's own expression level (PEtab's condition table).  i is a parameter index the
+    network reads -- bare as a rate or a Hill K, inside a Monomial, in scale, noise, a gain or a y0 Monomial --; an int target j (numpy
+    ints count, a bool is refused) means: this condition reads x[j] wherever the network says x[i]; a finite float target v means: it
+    reads the number v there -- the coordinate's value, not the constant: under "log10" a bare rate index then gives 10**v.  A missing
+    key, None or {} is the identity, and an object in which no condition has a mapping is the object it always was: source, data
+    block and code object.  Example: conds = [dict(y0=..., data=..., sd=..., params={5: 7, 9: 0.0}), ...].  The contract
+    (csrc/dz_ode.h's head, VIEWS), the same in both builds and every shape, with x'_c = V_c(x) the row of P = 1 + the largest index
+    the network reads entries that condition c sees (viewed(X, c) restates it in numpy):
+      * x'[i] is a SELECT between x[j] and v, no arithmetic: the bits are one or the other, and a coordinate of the point that a
+        condition does not read has no effect on its term, whatever it holds, NaN included;
+      * item c's term l_c(x) has the bits of the object of condition c alone, made without "params", at the row x'_c; its simulate
+        slice, steps, resting state and noise values likewise.  The sum stays ((l_0 + l_1) + l_2) + ...;
+      * liveness is per item: a non-finite coordinate that condition 1 replaces and condition 0 reads makes l_0 = -inf and leaves l_1
+        finite;
+      * an index mapped away in EVERY condition is formal: it is never read from the point and may lie at or beyond ndim -- a factor
+        that is 0.0 in control arms and -1.0 in inhibitor arms needs no sampled coordinate.  ndim is inferred as one more than the
+        largest coordinate some condition actually reads, an unmapped index or a target; an explicit ndim must be at least that;
+        P <= 128 (ODE_MAX_VIEW_COORDINATES);
+      * constraints are statements about the point: one whose Monomial reads a coordinate that some condition replaces is refused,
+        so they give the same value under every view; they stay on condition 0's term, and constraint_terms(X) evaluates them
+        through condition 0's view;
+      * with a view every experiment's block grows at its very end by 2 P doubles, the pairs (j_i, v_i), and the generated network
+        gains VIEW = P; the host build then evaluates rate constants, slots, gains and noise values per condition.
+    batch, batch_conditions, simulate, steady_state, fixed_steps(condition=c), with_outputs, pickling, device() and
+    posterior_predictive follow the view per condition; noise_values(X) returns [n, C, O, 2] for an object with a view (each
+    condition's own values, what a replicate of that condition is drawn with) and [n, O, 2] otherwise.  Not supported: targets that
+    are Monomials or expressions (x[j] + c and sums are reached through a Monomial plus a fixed formal coordinate:
+    pydream_amd/examples/knockdown), a constraint on a replaced coordinate, a view without conditions.
+
     Prediction: what follows a fit -- the trajectories of the posterior's rows against the data -- runs on the device too.
     device(device=0, max_bytes=256 << 20, chunk_items=None) returns an ODEDeviceEvaluator (a context manager; close() frees its small
     engine) with batch(X), batch_conditions(X) and simulate(X, return_terms=False): the host methods of the same names evaluated by the
@@ -491,6 +524,11 @@ class MassActionODELogLike:
                 own = conditions[c].get("inputs")
                 if own is not None:
                     cond["inputs"] = self._checked_inputs(own, "condition %d: " % c, like=self.inputs or ())
+        if self.conditions is not None:         # (a condition's view of the point: csrc/dz_ode.h, VIEWS)
+            for c, cond in enumerate(self.conditions):
+                view = self._checked_params(conditions[c].get("params"), c)
+                if view:
+                    cond["params"] = view
         self.d = self._checked_ndim(ndim)
         self.path, self._host = path, None
 
@@ -555,9 +593,9 @@ class MassActionODELogLike:
         if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
             raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
         for c, cond in enumerate(conditions):
-            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate", "inputs"}:
-                raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate", "inputs" '
-                                 '(each optional)' % c)
+            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate", "inputs", "params"}:
+                raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate", "inputs", '
+                                 '"params" (each optional)' % c)
             for key, top in own.items():
                 if cond.get(key) is None and top is None:
                     raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
@@ -628,12 +666,79 @@ class MassActionODELogLike:
             raise ValueError("MassActionODELogLike: noise must be None or a sequence of O entries, each None or a Noise (got %r)" % (noise,))
         return entries
 
-    def _checked_ndim(self, ndim):
-        """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K, a Monomial or a Noise reads."""
+    def _indices(self):
+        """The parameter indices the network reads -- a rate, a Hill K, a Monomial, a Noise or a gain --, ascending."""
         outside = list(self.y0_monomials.values()) + [f for f in self.scale or [] if isinstance(f, Monomial)] + [c[0] for c in self.constraints]
         outside += [c for z in self.noise or [] if z is not None for c in (z.sigma, z.rel) if c is not None and not isinstance(c, float)]
         outside += [u.gain for u in self.inputs or () if u.gain is not None and not isinstance(u.gain, float)]
-        idx = _rate_indices(self.reactions) + _slot_indices(_hill_slots(self.reactions)) + _indices_read(outside)
+        return sorted(set(_rate_indices(self.reactions) + _slot_indices(_hill_slots(self.reactions)) + _indices_read(outside)))
+
+    def _checked_params(self, params, c):
+        """Condition c's view as {index the network reads: int j (read x[j]) | float v (read the number v)}; {}: the identity."""
+        if params is None:
+            return {}
+        if not hasattr(params, "items"):
+            raise ValueError('MassActionODELogLike: condition %d: "params" must be a mapping {parameter index: parameter index (int) or value (float)} '
+                             '(got %r)' % (c, params))
+        read, view = self._indices(), {}
+        for i, target in params.items():
+            if not _is_int(i) or int(i) not in read:
+                raise ValueError('MassActionODELogLike: condition %d: "params" names %r, which is not a parameter index the network reads (%s)'
+                                 % (c, i, ", ".join(str(k) for k in read)))
+            if _is_int(target, 0):
+                view[int(i)] = int(target)
+            elif isinstance(target, (float, np.floating)) and np.isfinite(target):
+                view[int(i)] = float(target)
+            else:
+                raise ValueError('MassActionODELogLike: condition %d: "params"[%d] must be a parameter index (an int >= 0; a bool is refused) or a '
+                                 'finite value (float) (got %r)' % (c, i, target))
+        if view and read[-1] + 1 > ODE_MAX_VIEW_COORDINATES:
+            raise ValueError('MassActionODELogLike: condition %d: "params" views at most %d coordinates (ODE_MAX_VIEW_COORDINATES); the largest '
+                             'parameter index the network reads is %d' % (c, ODE_MAX_VIEW_COORDINATES, read[-1]))
+        for m, (mono, _, _) in enumerate(self.constraints):        # (constraints are statements about the point: the same under every view)
+            for i in mono.indices:
+                if i in view and (isinstance(view[i], float) or view[i] != i):
+                    raise ValueError('MassActionODELogLike: constraint %d reads parameter %d, which condition %d replaces through "params"; '
+                                     'a constraint is a statement about the point, the same under every view' % (m, i, c))
+        return view
+
+    def _has_view(self):
+        """Some condition carries a non-empty "params": the generated network's VIEW and the 2 P doubles at each block's end."""
+        return self.conditions is not None and any(cond.get("params") for cond in self.conditions)
+
+    def _view_size(self):
+        """P: one more than the largest index the network reads."""
+        read = self._indices()
+        return read[-1] + 1 if read else 0
+
+    def _view_table(self, params):
+        """A condition's view as the block holds it (csrc/dz_ode.h, VIEWS): P pairs (j_i, v_i) -- j_i >= 0 selects x[j_i], j_i = -1 the number
+        v_i; an index without an entry in `params` is itself, an index nothing reads (-1, 0)."""
+        read = set(self._indices())
+        tab = np.zeros((self._view_size(), 2))
+        for i in range(len(tab)):
+            target = params.get(i, i) if i in read else 0.0
+            tab[i] = (-1.0, target) if isinstance(target, float) else (float(target), 0.0)
+        return tab.reshape(-1)
+
+    def viewed(self, X, c=None):
+        """The rows of X as condition c reads them, x'_c = V_c(x): [n, P], or for c None [n, C, P] -- P one more than the largest index
+        the network reads; an index nothing reads holds 0.  Plain numpy, a restatement of what the kernels gather."""
+        if self.conditions is None:
+            raise ValueError("MassActionODELogLike: viewed needs an object made with conditions=[...]")
+        X = self._rows(X)
+        if c is None:
+            return np.stack([self.viewed(X, k) for k in range(len(self.conditions))], axis=1)
+        tab = self._view_table(self.conditions[c].get("params") or {}).reshape(-1, 2)
+        j = tab[:, 0].astype(int)
+        return np.where(j >= 0, X[:, np.maximum(j, 0)], tab[:, 1])
+
+    def _checked_ndim(self, ndim):
+        """The number of coordinates of a point: ndim, or one more than the largest index that a rate, a Hill K, a Monomial or a Noise
+        reads -- with views: that some condition reads from the point, an unmapped index or a target."""
+        idx = self._indices()
+        if self._has_view():
+            idx = sorted({t for cond in self.conditions for t in (cond.get("params", {}).get(i, i) for i in idx) if not isinstance(t, float)})
         d = (max(idx) + 1 if idx else 0) if ndim is None else int(ndim)
         if idx and max(idx) >= d:
             raise ValueError("MassActionODELogLike: parameter index %d is not < ndim = %d" % (max(idx), d))
@@ -785,8 +890,9 @@ class MassActionODELogLike:
         [C, stride] header, the kernels are the item kernels and the host build's results have an axis of conditions."""
         own = [dict(y0=self.y0, data=self.data, sd=self.sd, events=self.events, equilibrate=self.equilibrate)]
         with_inputs = lambda e: dict(inputs=e.get("inputs") or self.inputs) if self.inputs else {}      # noqa: E731
-        return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None, **with_inputs(e))
-                for e in (own if self.conditions is None else self.conditions)]
+        with_view = lambda e: dict(params=e.get("params") or {}) if self._has_view() else {}      # noqa: E731
+        return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None, **with_inputs(e),
+                     **with_view(e)) for e in (own if self.conditions is None else self.conditions)]
 
     def _input_knots(self, inputs):
         """One experiment's working knots as records (time, input, value, slope), sorted by time and at one time by input
@@ -814,7 +920,7 @@ class MassActionODELogLike:
         """Some experiment of the object equilibrates: the generated network's EQUILIBRATE and the six doubles at each block's end."""
         return any(eq is not None for eq in self._equilibrate_list())
 
-    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=()):
+    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=(), params=None):
         seen = np.isfinite(data)
         if self.noise is None:
             C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
@@ -846,6 +952,8 @@ class MassActionODELogLike:
             rec = np.zeros((self._max_input_knots(), 4))
             rec[:len(knots)] = np.asarray(knots, dtype=float).reshape(-1, 4)
             blk += [[float(len(knots))], rec.reshape(-1)]
+        if params is not None:                  # (csrc/dz_ode.h, VIEWS: the P pairs (j_i, v_i) at the very end)
+            blk += [self._view_table(params)]
         return np.concatenate(blk)
 
     def condition_block(self, c=0):
@@ -1017,6 +1125,8 @@ class MassActionODELogLike:
         experiment's value, or condition 0's term, holds beyond the data's likelihood (0 without constraints; -inf where a coordinate
         that a monomial or a rate reads, or a monomial's value, is not finite)."""
         X = self._rows(X)
+        if self._has_view():                    # (through condition 0's view: the term the constraints are added to)
+            X = np.ascontiguousarray(self.viewed(X, 0))
         g = np.zeros(len(X))
         self._host_call("dzode_constraints", X, len(X), X.shape[1], g)
         return g
@@ -1025,6 +1135,11 @@ class MassActionODELogLike:
         """The per-point noise values of the rows of X, [n, O, 2], from the host build: (a_q, b_q) = (sigma_q, rel_q) as the kernels hold
         them (csrc/dz_ode.h, NOISE), whether or not the point is live.  NaN for an observable without a Noise; b is 0 without rel."""
         X = self._rows(X)
+        if self._has_view():                    # (each condition's own values: [n, C, O, 2])
+            return np.stack([self._noise_values(np.ascontiguousarray(self.viewed(X, c))) for c in range(len(self.conditions))], axis=1)
+        return self._noise_values(X)
+
+    def _noise_values(self, X):
         ab = np.full((len(X), len(self.observables), 2), np.nan)
         self._host_call("dzode_noise", X, len(X), X.shape[1], ab)
         return ab
@@ -1034,6 +1149,8 @@ class MassActionODELogLike:
         condition: whose y0, for an object made with conditions.  Inputs are ignored, as events are: every drive is 0 and an input
         species stays at its y0 entry, 0."""
         x = np.ascontiguousarray(np.asarray(x, dtype=float).reshape(-1))
+        if self._has_view():                    # (the condition's view of the point)
+            x = np.ascontiguousarray(self.viewed(x.reshape(1, -1), condition)[0])
         y = np.zeros(self.n_species)
         ok = self._host_call("dzode_fixed", x, self.condition_block(condition), float(t1), int(nsteps), int(bool(embedded)), y)
         return y if ok else np.full(self.n_species, np.nan)

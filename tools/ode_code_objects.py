@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The lane-group ODE kernels (csrc/dz_ode_group.h) of a fixed list of networks, cross-compiled for gfx950 from the checkout given as
+"""The ODE kernels (csrc/dz_ode_group.h; the view networks: also csrc/dz_ode.h's one lane per item) of a fixed list of networks, cross-compiled for gfx950 from the checkout given as
 the argument: one line per code object with its resources and a digest of its instructions, to lay two checkouts side by side (no GPU
 needed).
 
@@ -55,6 +55,17 @@ def objects():
         if MN.spec_and_data(name)[0]["lanes"] != 1:
             out["monomials." + name] = lambda name=name: MN.build(name)[0]
     out["wave.%s_conditions+events+monomials" % wave] = lambda: WN.chain_conditions(int(wave[5:]), 3, events=True, monomials=True)[0]
+    try:                                    # (a checkout from before conditions had "params": the list ends here)
+        from tests import ode_view_networks as VN
+    except ImportError:
+        return out
+    # the networks whose conditions view the point, each beside its twin without a view (one lane per item among them)
+    for name in ("mm", "enzyme13", "chain17", VN.WAVE):
+        out["view.%s" % name] = lambda name=name: VN.basic(name)[0]
+        out["view.%s.twin" % name] = lambda name=name: VN.basic(name, view=False)[0]
+    for lanes in (1, 16, 32, 64):
+        out["view.readers@%d" % lanes] = lambda lanes=lanes: VN.readers(lanes)[0]
+        out["view.readers@%d.twin" % lanes] = lambda lanes=lanes: VN.readers(lanes, view=False)[0]
     return out
 
 

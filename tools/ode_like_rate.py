@@ -10,7 +10,7 @@
     (DREAMZS_HOST_WORKERS=16), both for the host build of the same solver and (Robertson) for the reference example's odeint likelihood.
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
-                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise] [--input]
+                                  [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise] [--input] [--view]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -39,6 +39,13 @@ chain40 of tests/ode_input_networks.py, a network with an input species driven b
 be built before inputs existed: the same species and reactions with the input species a plain species fed by a fixed zero-order source,
 a single ramp, on the same points; alternately, the median of 7 rounds of 10 calls each and the rounds' spread; proposals/s and the host
 build's steps per point for both.  The work per step is the same; knots only add clipped steps.  Kernel only.
+
+--view: what a view of the point per condition costs (MassActionODELogLike(conditions=[dict(params=...)]), csrc/dz_ode.h, VIEWS) --
+--network mm | enzyme13 | chain17 | chain33 of tests/ode_view_networks.py (1, 16, 32 and 64 lanes per item) under 3 conditions whose
+mappings are explicit identities {i: i} for every coordinate read, so the kernels gather every item's view and the values are the
+same, against the same object without "params", on the same points; alternately, the median of 7 rounds of 10 calls each and the
+rounds' spread; proposals/s for both, their registers, scratch and LDS from the code objects' notes, and the two launches' values
+compared bit for bit (the host build's on the first 64 points).  Kernel only.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -301,6 +308,34 @@ def input_rate(N, k, name, rounds=7, reps=10):
     return out
 
 
+def view_rate(N, k, name, rounds=7, reps=10):
+    """Explicit identity views under 3 conditions against the same object without "params": see the head"""
+    from tests import ode_view_networks as VN
+    from tests.ode_support import notes
+    values = (0.5, 1.0, 2.0) if name != "mm" else None
+    objs = dict(without_view=VN.basic(name, view=False, identity=True, values=values)[0], with_view=VN.basic(name, identity=True, values=values)[0])
+    like = objs["with_view"]
+    assert len(like.conditions) == 3 and "VIEW" in like.source() and "VIEW" not in objs["without_view"].source()
+    n, d = N * k, like.d
+    nominal = VN.nominal_of(name)[:d]
+    X = box_points(nominal, 1.0, n)
+    engines = {key: engine_for(obj, N, k, nominal, 1.0) for key, obj in objs.items()}
+    last, t = timed({key: (lambda eng=eng: eng.eval_logp(X)[1]) for key, eng in engines.items()}, rounds, reps)
+    assert last["with_view"].tobytes() == last["without_view"].tobytes(), "the launches with and without a view differ"
+    assert last["with_view"][:64].tobytes() == like.batch(X[:64]).tobytes(), "device and host builds differ"
+    out = dict(network=name + " x 3", lanes=like.lanes_per_point, species=like.n_species, viewed_coordinates=like._view_size(), chains=N, tries=k, points=n,
+               items=3 * n, failed_points=int(np.sum(last["with_view"] == -np.inf)))
+    for key in objs:
+        us = float(np.median(t[key]))
+        out[key] = dict(us_per_launch=round(us, 1), us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6),
+                        code_object=notes(objs[key].code_object()))
+    out["with_over_without"] = round(out["with_view"]["us_per_launch"] / out["without_view"]["us_per_launch"], 4)
+    lo, hi = (min(t["with_view"]) / max(t["without_view"]), max(t["with_view"]) / min(t["without_view"]))
+    out["ratio_over_the_rounds_spread"] = [round(lo, 4), round(hi, 4)]
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def _host_part(args):
     like, part = args
     return like.batch(part, return_steps=True)
@@ -404,6 +439,8 @@ if __name__ == "__main__":
         noise_rate(*nums, name, lanes)
     elif "--input" in argv:
         input_rate(*nums, name)
+    elif "--view" in argv:
+        view_rate(*nums, name)
     elif "--equilibrate" in argv:
         assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
         events_rate(*nums, name, lanes, int(opt["--conditions"]), 0, equilibrate=True)
