@@ -9,6 +9,7 @@
 #include "dz_kernels.h"
 #include "dz_megakernel.h"
 #include "dz_mega_launch.h"
+#include "dz_multi_select.h"
 
 #include <hip/hip_ext.h>
 #include <dlfcn.h>
@@ -116,7 +117,7 @@ struct dz_engine {
     // independent chain groups ("lanes") run their propose/logp/accept kernels on separate streams: between two
     // history appends the groups share nothing, so one group's likelihood (matrix pipe) overlaps another's
     // proposal generation (VALU) -- lane 0 is `stream`
-    int nlanes = 1; hipStream_t lane_stream[8] = {nullptr}; hipEvent_t lane_ev[8] = {nullptr}; bool need_join = true;
+    int nlanes = 1; hipStream_t lane_stream[8] = {nullptr}; hipEvent_t lane_ev[8] = {nullptr};
     // bounded host run-ahead: a marker every RA_STRIDE generations, the host never gets more than 3 markers ahead
     dz::Params p_shadow; bool params_uploaded = false;    // what d_params holds
     void* h_pin = nullptr; hipEvent_t pin_ev[2] = {nullptr, nullptr};          // page-locked bounce buffer (two halves) for downloads into pageable memory (d2h_2d)
@@ -124,7 +125,7 @@ struct dz_engine {
     double* d_qpart = nullptr; size_t qpart_len = 0; bool logp_gemm = true;    // row-tile sums of the tiled large-d likelihood; DZ_LOGP_GEMM=0: no LDS-tiled product
     hipEvent_t ra_ev[4] = {nullptr}; bool ra_used[4] = {false, false, false, false}; int64_t ra_n = 0;
     int nch = 1;
-    int64_t M = 0, gen = 0, ntrace = 0, draws_gen = -1;
+    int64_t M = 0, gen = 0, ntrace = 0;
     int64_t napp = 0;               // appends made since the archive was set (dz_config.history_lag: the last `lag` of them are not sampleable yet)
     std::vector<int64_t> gen_c;     // per-chain generation counters (differ only under single-chain stepping)
     uint4* d_draws[2] = {nullptr, nullptr};
@@ -189,7 +190,6 @@ struct dz_engine {
     std::vector<double> h_stage;     // host staging (callback likelihood / exchange)
     bool prof = false;
     int num_cu = 256;
-    int64_t stream_prop_gen = -1;   // the generation whose proposal set k_accept_propose has already made
     bool q_defer = true;            // streamed generations: no k_q_finish launches, the proposal / Metropolis kernels add the row-tile sums (DZ_QFIN=0: off)
     double* last_qpart = nullptr;   // the scratch slice the last tiled likelihood launch wrote
     bool mega = true;               // the persistent generation kernel serves every eligible configuration (mega_choose, dz_mega_select.h); DZ_MEGA=0 forces the multi-kernel path
@@ -208,11 +208,10 @@ struct dz_engine {
     double *d_own_cr = nullptr, *d_own_g = nullptr; std::vector<char> own_init;      // per-instance probabilities of single-chain stepping (Params::own_cr)
     std::string broken;             // non-empty: a failed dz_continue_run left the engine without some of its buffers -- dz_step refuses
     dz::MegaShape mshape; dz::MegaChoice mchoice;      // the persistent kernels' selection, made at the start of every dz_step (mega_select)
+    dz::MultiShape multi;           // what the multi-kernel path's selection reads (multi_shape), refreshed by every entry point that reaches eval_logp or one_generation
+    dz::MultiCarry carry;           // what the last generation of that path left for the next one (GenerationPlan::next)
     std::string last_variant;       // what the last dz_step launched for its generations (dz_last_kernel_variant)
     int last_kc = 0;                // ... and the try count compiled into it (MegaLaunch::kc; dz_last_kernel_tries)
-    bool pending_accept = false;    // generation gen-1's Metropolis step has been deferred into the next proposal kernel
-    const double* pending_qfin_r = nullptr;      // ... and with it the reference set's row-tile sums (Params::qfin_r), still in the scratch array
-    int64_t pending_slot = -1;
     int propose_split = 0;          // waves per chain in k_propose (DZ_PROPOSE_SPLIT); 0 = by problem shape
     std::vector<hipEvent_t> ev_pool;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[PR_COUNT];
@@ -341,126 +340,95 @@ int launch_check(const char* what)
     return 0;
 }
 
-// Model.total_logp for n points stored [n,ld] on the device
+// A device buffer of doubles that only grows: *have counts in the caller's units (`want` of them are `alloc` doubles); zeroed or not.  On failure
+// the buffer is gone, *have is 0 and the HIP error comes back for the caller's message.
+hipError_t grow_doubles(double** buf, size_t* have, size_t want, size_t alloc, bool zeroed)
+{
+    if (*have >= want) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    hipError_t err = hipMalloc((void**)buf, sizeof(double) * (alloc ? alloc : 1));
+    if (err == hipSuccess && zeroed) {      // (as dalloc: the fill is queued on the NULL stream, which the engine's streams do not wait for)
+        err = hipMemset(*buf, 0, sizeof(double) * (alloc ? alloc : 1));
+        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+    }
+    if (err != hipSuccess) { (void)hipGetLastError(); if (*buf) (void)hipFree(*buf); *buf = nullptr; return err; }
+    *have = want;
+    return hipSuccess;
+}
+// Every chain-group stream has its own slice of a scratch array of `need` doubles per stream (grown behind sync_all) -> the slice of `st`
+int stream_slice(dz_engine* e, hipStream_t st, double** buf, size_t* len, size_t need, const std::string& what, double** slice)
+{
+    int sl = 0;
+    for (int s2 = 1; s2 < e->nlanes; ++s2) if (e->lane_stream[s2] == st) sl = s2;
+    if (need * e->nlanes > *len) {
+        DZCK(sync_all(e));
+        const hipError_t err = grow_doubles(buf, len, need * e->nlanes, need * e->nlanes, true);
+        if (err != hipSuccess) return fail(what + hipGetErrorString(err));
+    }
+    *slice = *buf + (size_t)sl * (*len / e->nlanes);
+    return 0;
+}
+
+// The instantiations of the two small-d MVN kernels, indexed by the plan's template arguments (both take the same arguments)
+using MvnKernel = void (*)(dz::Params, const double*, int, double*, double*);
+template <int NRT> constexpr MvnKernel mvn_lds_kernel(bool tri) { return tri ? dz::k_logp_mvn_lds<NRT, true> : dz::k_logp_mvn_lds<NRT, false>; }
+template <int NRT> constexpr MvnKernel mvn_mfma_kernel(int pt, bool tri)
+{
+    return pt == 2 ? (tri ? dz::k_logp_mvn_mfma<2, NRT, true> : dz::k_logp_mvn_mfma<2, NRT, false>) : (tri ? dz::k_logp_mvn_mfma<1, NRT, true> : dz::k_logp_mvn_mfma<1, NRT, false>);
+}
+template <size_t... I> MvnKernel mvn_kernel(const dz::LogpPlan& P, std::index_sequence<I...>)
+{
+    const MvnKernel lds[] = {mvn_lds_kernel<I + 1>(P.tri)...}, mfma[] = {mvn_mfma_kernel<I + 1>(P.pt, P.tri)...};
+    return (P.family == dz::LOGP_LDS ? lds : mfma)[P.nrt - 1];
+}
+inline dim3 g3(const dz::MultiLaunch& l) { return dim3(l.grid); }
+inline dim3 b3(const dz::MultiLaunch& l) { return dim3(l.block); }
+
+// Model.total_logp for n points stored [n,ld] on the device; what is launched, with what geometry: dz::logp_plan (dz_multi_select.h)
 // defer_finish (large-d MVN only): the row-tile sums stay in the scratch array (e->last_qpart) for the consuming kernel to add
 // (Params::qfin_*) instead of a k_q_finish launch
 int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* like, hipStream_t st = nullptr, bool defer_finish = false)
 {
     if (n <= 0) return 0;
     if (!st) st = e->stream;
-    const int nrt = e->p.ld / 16;
-    const int ks4 = 4 * ((e->p.d + 3) / 4);
-    // LDS kernel: matrix (packed triangle or square) + mean + at least 4 wave tiles must fit 160 KB
-    // (the dense 128-D square does not: 131 KB + 66 KB; it runs on the register-operand MFMA kernel)
-    const bool lds_fits = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld + (size_t)4 * 16 * (e->p.ld + 1)) <= dz::LDS_LIMIT;
-    const bool one_kernel = e->lk == LK_MVN && !e->p.have_prior && nrt <= 8 && lds_fits;   // the LDS kernel alone: timed by the launch's own events
-    ProfScope ps(e, PR_LOGP, st, !one_kernel);
-    const dim3 grid((n + 3) / 4), block(256);
-    if (e->lk == LK_MVN) {
-        {
-            if (nrt <= 8 && lds_fits) {
-                const int ntiles = (n + 15) / 16;
-                // one wave per point tile of the CU's share when LDS allows (4..8 waves): 1280 tiles on 256 CUs run as
-                // 5-wave blocks instead of 4-wave blocks of which a quarter does a second tile
-                const size_t lds_fixed = sizeof(double) * ((e->p.tri ? (size_t)e->p.mtp_len : (size_t)ks4 * e->p.ld) + e->p.ld), lds_wave = sizeof(double) * (size_t)16 * (e->p.ld + 1);
-                int nwv = std::max(4, std::min(8, (ntiles + e->num_cu - 1) / e->num_cu));
-                while (nwv > 4 && lds_fixed + nwv * lds_wave > dz::LDS_LIMIT) --nwv;
-                const size_t lds = lds_fixed + nwv * lds_wave;
-                const dim3 gl((unsigned)std::min(e->num_cu, (ntiles + nwv - 1) / nwv)), bl(64 * nwv);
-#define DZ_LDS_CASE(NRT_)                                                                                                      \
-    case NRT_:                                                                                                                 \
-        if (!one_kernel) {                                                                                                     \
-            if (e->p.tri) hipLaunchKernelGGL((dz::k_logp_mvn_lds<NRT_, true>), gl, bl, lds, st, e->p, pts, n, prior, like);   \
-            else hipLaunchKernelGGL((dz::k_logp_mvn_lds<NRT_, false>), gl, bl, lds, st, e->p, pts, n, prior, like);           \
-        } else if (e->p.tri) DZ_KLAUNCH(e, PR_LOGP, st, (dz::k_logp_mvn_lds<NRT_, true>), gl, bl, lds, e->p, pts, n, prior, like); \
-        else DZ_KLAUNCH(e, PR_LOGP, st, (dz::k_logp_mvn_lds<NRT_, false>), gl, bl, lds, e->p, pts, n, prior, like);           \
+    const dz::LogpPlan P = dz::logp_plan(e->multi, n, defer_finish);
+    ProfScope ps(e, PR_LOGP, st, !P.one_kernel);
+    switch (P.family) {
+    case dz::LOGP_LDS: case dz::LOGP_MFMA: {
+        const MvnKernel kern = mvn_kernel(P, std::make_index_sequence<8>());
+        if (P.one_kernel) DZ_KLAUNCH(e, PR_LOGP, st, kern, g3(P.main), b3(P.main), P.main.lds, e->p, pts, n, prior, like);
+        else hipLaunchKernelGGL(kern, g3(P.main), b3(P.main), P.main.lds, st, e->p, pts, n, prior, like);
+    } break;
+    case dz::LOGP_TILED: case dz::LOGP_GEMM: {
+        double* qpart = nullptr;
+        DZCK(stream_slice(e, st, &e->d_qpart, &e->qpart_len, P.qpart_doubles, "hipMalloc((void**)p, sizeof(T) * (n ? n : 1)): ", &qpart));
+        if (P.family == dz::LOGP_TILED) hipLaunchKernelGGL((dz::k_logp_mvn_mfma_tiled<dz::TILED_PT, dz::TILED_RTC>), g3(P.main), b3(P.main), 0, st, e->p, pts, n, qpart);
+        else if (P.gemm_tile == 1) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<1>, g3(P.main), b3(P.main), P.main.lds, st, e->p, pts, n, qpart, e->num_cu);
+        else if (P.gemm_tile == 2) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<2>, g3(P.main), b3(P.main), P.main.lds, st, e->p, pts, n, qpart, e->num_cu);
+        else hipLaunchKernelGGL(dz::k_logp_mvn_gemm<4>, g3(P.main), b3(P.main), P.main.lds, st, e->p, pts, n, qpart, e->num_cu);
+        e->last_qpart = qpart;
+        if (P.q_finish) hipLaunchKernelGGL(dz::k_q_finish, g3(P.finish), b3(P.finish), 0, st, e->p, (const double*)qpart, n, P.nrtb, prior, like);
+    } break;
+    case dz::LOGP_MIX:
+        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_logp_mix<NCH>, g3(P.main), b3(P.main), 0, st, e->p, pts, n, prior, like));
         break;
-                switch (nrt) { DZ_LDS_CASE(1) DZ_LDS_CASE(2) DZ_LDS_CASE(3) DZ_LDS_CASE(4) DZ_LDS_CASE(5) DZ_LDS_CASE(6) DZ_LDS_CASE(7) DZ_LDS_CASE(8) }
-#undef DZ_LDS_CASE
-            } else if (nrt <= 8) {
-                const int ntiles = (n + 15) / 16;
-                const int pt = ntiles > 1024 ? 2 : 1;   // 1024 SIMDs: share B operands between two point tiles once every SIMD has work
-                const dim3 g2((n + 64 * pt - 1) / (64 * pt));
-#define DZ_MFMA_CASE(NRT_)                                                                                                                     \
-    case NRT_:                                                                                                                                 \
-        if (pt == 2) { if (e->p.tri) hipLaunchKernelGGL((dz::k_logp_mvn_mfma<2, NRT_, true>), g2, block, 0, st, e->p, pts, n, prior, like);   \
-                       else hipLaunchKernelGGL((dz::k_logp_mvn_mfma<2, NRT_, false>), g2, block, 0, st, e->p, pts, n, prior, like); }  \
-        else { if (e->p.tri) hipLaunchKernelGGL((dz::k_logp_mvn_mfma<1, NRT_, true>), g2, block, 0, st, e->p, pts, n, prior, like);           \
-               else hipLaunchKernelGGL((dz::k_logp_mvn_mfma<1, NRT_, false>), g2, block, 0, st, e->p, pts, n, prior, like); }          \
-        break;
-                switch (nrt) { DZ_MFMA_CASE(1) DZ_MFMA_CASE(2) DZ_MFMA_CASE(3) DZ_MFMA_CASE(4) DZ_MFMA_CASE(5) DZ_MFMA_CASE(6) DZ_MFMA_CASE(7) DZ_MFMA_CASE(8) }
-#undef DZ_MFMA_CASE
-            } else {
-                // tiled product: waves = point-tile groups x row-tile groups; per-row-tile sums through a scratch array
-                constexpr int PT = 2, RTC = 4;
-                const int nrtb = (e->p.d + 15) / 16, nrg = (nrtb + RTC - 1) / RTC, npg = (n + 16 * PT - 1) / (16 * PT);
-                // every chain-group stream has its own slice of the row-tile scratch array
-                int sl = 0;
-                for (int s2 = 1; s2 < e->nlanes; ++s2) if (e->lane_stream[s2] == st) sl = s2;
-                const size_t need = (size_t)n * nrtb;
-                if (need * e->nlanes > e->qpart_len) {
-                    DZCK(sync_all(e));
-                    if (e->d_qpart) (void)hipFree(e->d_qpart);
-                    e->d_qpart = nullptr; e->qpart_len = 0;
-                    DZCK(dalloc(&e->d_qpart, need * e->nlanes));
-                    e->qpart_len = need * e->nlanes;
-                }
-                double* qpart = e->d_qpart + (size_t)sl * (e->qpart_len / e->nlanes);
-                if (e->logp_gemm && n >= 512) {            // enough points to fill the chip with 64 x 64 block tiles
-                    const int nbn = (nrtb * 16 + 63) / 64;
-                    const size_t ldsm = e->p.mu_zero ? 0 : sizeof(double) * (size_t)e->p.ld;
-                    // Points per block (128 / 64 / 32): the kernel is bound by how many blocks a CU has in flight (each one is a
-                    // chain of barrier -> LDS reads -> MFMAs -> LDS store), so the largest tile that still leaves five blocks per
-                    // CU: 2560 points x 1000 rows: 32 points 65 us, 64 points 70 us, 128 points 98 us per launch.
-                    const int bmsel = ((n + 127) / 128) * nbn >= 5 * e->num_cu ? 128 : ((n + 63) / 64) * nbn >= 5 * e->num_cu ? 64 : 32;
-                    const dim3 gridg(((n + bmsel - 1) / bmsel) * nbn);
-                    if (bmsel == 32) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<1>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                    else if (bmsel == 64) hipLaunchKernelGGL(dz::k_logp_mvn_gemm<2>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                    else hipLaunchKernelGGL(dz::k_logp_mvn_gemm<4>, gridg, block, ldsm, st, e->p, pts, n, qpart, e->num_cu);
-                } else
-                    hipLaunchKernelGGL((dz::k_logp_mvn_mfma_tiled<PT, RTC>), dim3((npg * nrg + 3) / 4), block, 0, st, e->p, pts, n, qpart);
-                e->last_qpart = qpart;
-                if (!defer_finish) hipLaunchKernelGGL(dz::k_q_finish, dim3((n + 63) / 64), dim3(64), 0, st, e->p, (const double*)qpart, n, nrtb, prior, like);
-            }
-            if (e->p.have_prior) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_only<NCH>, grid, block, 0, st, e->p, pts, n, prior));
-        }
-    } else if (e->lk == LK_MIX) {
-        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_logp_mix<NCH>, grid, block, 0, st, e->p, pts, n, prior, like));
-    } else if (e->lk == LK_MODULE) {
-        // the user's kernel writes like[n]; the engine zeroes prior[n] first and then adds the device priors and maps nan -> -inf (k_prior_add),
-        // exactly what follows a host callback
+    case dz::LOGP_MODULE: {
         struct { const double* X; long long n; int d; int ld; double* like; const void* data; } a = {pts, (long long)n, e->p.d, e->p.ld, like, e->d_lk_data};
         size_t asz = sizeof(a);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
         HIPCK(hipMemsetAsync(prior, 0, sizeof(double) * (size_t)n, st));
-        const unsigned per_block = 256u / (unsigned)e->lk_lanes;      // 1, 16, 32 or 64 lanes per point, 256 threads per block
-        if (e->lk_items == 1) {
-            HIPCK(hipModuleLaunchKernel(e->lk_fn, ((unsigned)n + per_block - 1) / per_block, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
-        } else {
-            // several items per point (dz_set_likelihood_items): the kernel's n is the item count and its like the engine's scratch, item w
-            // of it belonging to point w / C; k_sum_items then leaves each point's sum where a one-item kernel would have written
-            const int C = e->lk_items;
-            const long long items = (long long)n * C, blocks = (items + per_block - 1) / per_block;
-            if (blocks > 0x7fffffffll) return fail("dz_set_likelihood_items: " + std::to_string(items) + " items are more than one launch's grid holds");
-            int sl = 0;
-            for (int s2 = 1; s2 < e->nlanes; ++s2) if (e->lane_stream[s2] == st) sl = s2;
-            if ((size_t)items * e->nlanes > e->items_len) {
-                DZCK(sync_all(e));
-                if (e->d_items) (void)hipFree(e->d_items);
-                e->d_items = nullptr; e->items_len = 0;
-                if (dalloc(&e->d_items, (size_t)items * e->nlanes)) {
-                    (void)hipGetLastError(); e->d_items = nullptr;
-                    return fail("dz_set_likelihood_items: cannot allocate the scratch for " + std::to_string(items) + " items x " + std::to_string(e->nlanes) + " streams: " + g_err);
-                }
-                e->items_len = (size_t)items * e->nlanes;
-            }
-            double* scratch = e->d_items + (size_t)sl * (e->items_len / e->nlanes);
-            a.n = items; a.like = scratch;
-            HIPCK(hipModuleLaunchKernel(e->lk_fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
-            hipLaunchKernelGGL(dz::k_sum_items, dim3(((unsigned)n + 255) / 256), dim3(256), 0, st, (const double*)scratch, n, C, like);
+        if (P.grid_overflow) return fail("dz_set_likelihood_items: " + std::to_string(P.items) + " items are more than one launch's grid holds");
+        double* scratch = nullptr;
+        if (P.sum_items) {
+            DZCK(stream_slice(e, st, &e->d_items, &e->items_len, P.scratch_doubles,
+                              "dz_set_likelihood_items: cannot allocate the scratch for " + std::to_string(P.items) + " items x " + std::to_string(e->nlanes) + " streams: hipMalloc((void**)p, sizeof(T) * (n ? n : 1)): ", &scratch));
+            a.n = P.items; a.like = scratch;
         }
-        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, grid, block, 0, st, e->p, pts, n, prior, like));
-    } else if (e->lk == LK_HOST) {
+        HIPCK(hipModuleLaunchKernel(e->lk_fn, P.main.grid, 1, 1, P.main.block, 1, 1, 0, st, nullptr, extra));
+        if (P.sum_items) hipLaunchKernelGGL(dz::k_sum_items, g3(P.sum), b3(P.sum), 0, st, (const double*)scratch, n, e->multi.lk_items, like);
+    } break;
+    case dz::LOGP_HOST: {
         const int d = e->p.d;
         e->h_stage.resize((size_t)n * (d + 2));
         double* hx = e->h_stage.data(); double* hp = hx + (size_t)n * d; double* hl = hp + n;
@@ -470,8 +438,11 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
         HIPCK(hipMemcpyAsync(prior, hp, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
         HIPCK(hipMemcpyAsync(like, hl, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
         DZCK(sync_all(e));
-        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, grid, block, 0, st, e->p, pts, n, prior, like));
-    } else return fail("no likelihood set");
+    } break;
+    default: return fail("no likelihood set");
+    }
+    if (P.prior_only) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_only<NCH>, g3(P.prior), b3(P.prior), 0, st, e->p, pts, n, prior));
+    if (P.prior_add) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, g3(P.prior), b3(P.prior), 0, st, e->p, pts, n, prior, like));
     return launch_check("logp kernel");
 }
 
@@ -750,16 +721,17 @@ int join_all(dz_engine* e)
 // The list comes from one read-back of the flags; up to four rounds are queued per read-back (chains that succeed in between drop
 // out by their flag: same result as a round-by-round loop, fewer host round trips).  The reference's loop is unbounded; after
 // DZ_MAX_REDRAWS rounds the step is a rejection (k_accept: no finite try), deviation D1.
-int redraw_impossible_sets(dz_engine* e, uint32_t g, int lc0, int lnc, int sp0, int wpb, hipStream_t st)
+int redraw_impossible_sets(dz_engine* e, uint32_t g, int lc0, int lnc, hipStream_t st)
 {
     dz::Params& p = e->p;
-    const int k = p.k;
     if (!e->d_redo) DZCK(ealloc(e, &e->d_redo, (size_t)p.nl));
     if (!e->d_redo_list) DZCK(ealloc(e, &e->d_redo_list, (size_t)p.nl));
     if (!e->h_redo && hipHostMalloc((void**)&e->h_redo, (size_t)p.nl, hipHostMallocDefault) != hipSuccess) { e->h_redo = nullptr; return fail("hipHostMalloc (redraw flags) failed"); }
     if (!e->h_redo_list && hipHostMalloc((void**)&e->h_redo_list, sizeof(int32_t) * (size_t)p.nl, hipHostMallocDefault) != hipSuccess) { e->h_redo_list = nullptr; return fail("hipHostMalloc (redraw list) failed"); }
+    static_assert(dz::MULTI_MAX_REDRAWS == DZ_MAX_REDRAWS, "redraw rounds");
     for (int round = 1; round <= DZ_MAX_REDRAWS;) {
-        hipLaunchKernelGGL(dz::k_redo_flags, dim3((lnc + 255) / 256), dim3(256), 0, st, p, lc0, lnc, e->d_redo);
+        const dz::MultiLaunch fl = dz::redraw_plan(e->multi, lnc, 0, round).flags;
+        hipLaunchKernelGGL(dz::k_redo_flags, g3(fl), b3(fl), 0, st, p, lc0, lnc, e->d_redo);
         DZCK(launch_check("k_redo_flags"));
         HIPCK(hipMemcpyAsync(e->h_redo, e->d_redo + lc0, (size_t)lnc, hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));
@@ -767,20 +739,18 @@ int redraw_impossible_sets(dz_engine* e, uint32_t g, int lc0, int lnc, int sp0, 
         for (int t = 0; t < lnc; ++t) if (e->h_redo[t]) e->h_redo_list[n++] = lc0 + t;
         if (n == 0) break;
         HIPCK(hipMemcpyAsync(e->d_redo_list, e->h_redo_list, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-        // (a host likelihood costs more than a round trip: one round per read-back, no point is evaluated that did not have to be)
-        const int batch = e->lk == LK_HOST ? 1 : std::min(DZ_MAX_REDRAWS - round + 1, n >= 16 ? 4 : (n >= 4 ? 3 : 2));
-        for (int b = 0; b < batch; ++b, ++round) {
-            if (b) hipLaunchKernelGGL(dz::k_redo_flags, dim3((lnc + 255) / 256), dim3(256), 0, st, p, lc0, lnc, e->d_redo);
+        const dz::RedrawPlan R = dz::redraw_plan(e->multi, lnc, n, round);
+        for (int b = 0; b < R.batch; ++b, ++round) {
+            if (b) hipLaunchKernelGGL(dz::k_redo_flags, g3(R.flags), b3(R.flags), 0, st, p, lc0, lnc, e->d_redo);
             dz::Params pr = p;
             const uint64_t key = e->c.seed + (uint64_t)round * DZ_REDRAW_KEY_STEP;
             pr.k0 = (uint32_t)key; pr.k1 = (uint32_t)(key >> 32);
             pr.draws = nullptr; pr.redo_list = e->d_redo_list; pr.redo = e->d_redo;
-            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, dim3((n * sp0 + wpb - 1) / wpb), dim3(64 * wpb), 0, pr, 0, g, (uint32_t)visible_rows(e), 0, n, sp0, 0, (int64_t)-1));
+            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, g3(R.propose), b3(R.propose), 0, pr, 0, g, (uint32_t)visible_rows(e), 0, n, R.sp0, 0, (int64_t)-1));
             DZCK(launch_check("propose(redraw)"));
-            const size_t nd2 = (size_t)n * k * p.ld / 2;
-            hipLaunchKernelGGL(dz::k_gather_sets, dim3((unsigned)((nd2 + 255) / 256)), dim3(256), 0, st, p, (const int32_t*)e->d_redo_list, n, p.R);
-            DZCK(eval_logp(e, p.R, n * k, p.r_prior, p.r_like, st));
-            hipLaunchKernelGGL(dz::k_scatter_logp, dim3((n * k + 255) / 256), dim3(256), 0, st, p, (const int32_t*)e->d_redo_list, n, (const double*)p.r_prior, (const double*)p.r_like);
+            hipLaunchKernelGGL(dz::k_gather_sets, g3(R.gather), b3(R.gather), 0, st, p, (const int32_t*)e->d_redo_list, n, p.R);
+            DZCK(eval_logp(e, p.R, R.points, p.r_prior, p.r_like, st));
+            hipLaunchKernelGGL(dz::k_scatter_logp, g3(R.scatter), b3(R.scatter), 0, st, p, (const int32_t*)e->d_redo_list, n, (const double*)p.r_prior, (const double*)p.r_like);
             DZCK(launch_check("redraw gather/scatter"));
             e->redraw_rounds++;
         }
@@ -791,22 +761,21 @@ int redraw_impossible_sets(dz_engine* e, uint32_t g, int lc0, int lnc, int sp0, 
 // one transition of local chains [c0, c0+nc) at generation g.  Full range = a lockstep generation
 // (schedule S2); a sub-range is the single-chain view used by Dream.astep: its end-of-generation
 // updates (append, publish, adaptation) take effect immediately, as when the reference is driven
-// round-robin in one process.
+// round-robin in one process.  What is launched, on which stream group, with what geometry, and what the
+// generation leaves for the next one: dz::generation_plan (dz_multi_select.h).
 int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool more_follow)
 {
     dz::Params& p = e->p;
-    const int k = p.k;
-    const bool full = (c0 == 0 && nc == p.nl);
-    if (!full && e->world > 1) return fail("single-chain stepping is not available on a sharded engine");
-    if (!full && e->c.history_lag) return fail("single-chain stepping (Dream.astep) appends with immediate effect: history_lag must be 0");
-    if (!full && e->c.adapt_lag) return fail("single-chain stepping (Dream.astep) updates the crossover probabilities with immediate effect: adapt_lag must be 0");
+    const dz::GenerationPlan G = dz::generation_plan(e->multi, dz::MultiStep{c0, nc, g, traced, more_follow, (long long)e->ntrace}, e->carry);
+    if (G.refuse == dz::REFUSE_SHARDED) return fail("single-chain stepping is not available on a sharded engine");
+    if (G.refuse == dz::REFUSE_HISTORY_LAG) return fail("single-chain stepping (Dream.astep) appends with immediate effect: history_lag must be 0");
+    if (G.refuse == dz::REFUSE_ADAPT_LAG) return fail("single-chain stepping (Dream.astep) updates the crossover probabilities with immediate effect: adapt_lag must be 0");
     DZCK(adapt_flush(e));               // (these kernels read the shared probabilities in place)
     DZCK(ensure_visible(e));
     const uint32_t Mv = (uint32_t)visible_rows(e);
-    const int L = (full && e->lk != LK_HOST && !redo_possible(e)) ? e->nlanes : 1;     // the host-callback likelihood is synchronous anyway; redraw rounds use shared buffers
-    if (e->need_join || !full) { DZCK(join_all(e)); e->need_join = false; }
+    if (G.join_first) DZCK(join_all(e));
     p.own_cr = nullptr; p.own_g = nullptr;
-    if (!full && e->adapt) {
+    if (G.own_probs) {
         // Dream.astep chain by chain: every Dream instance decides with its OWN copy of the crossover / gamma-level probabilities
         // (Dream.py:134, :143; refreshed at :375, :383, :409-415) -- the shared vectors may have moved on through other chains' updates
         if (!e->d_own_cr) {
@@ -819,7 +788,7 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
         }
         p.own_cr = e->d_own_cr; p.own_g = e->d_own_g;
     }
-    if (full && g == 0 && e->adapt) {   // publish the start positions (Dream_shared_vars.current_positions)
+    if (G.publish_start) {   // publish the start positions (Dream_shared_vars.current_positions)
         const size_t n = (size_t)p.nl * p.ld;
         hipLaunchKernelGGL(dz::k_copy_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, p.X, p.cp_new + (size_t)p.off * p.ld, n);
         DZCK(exchange_rows(e, XK_POS, p.cp_new, 0));
@@ -828,102 +797,68 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
     }
     p.draws = e->d_draws[g & 1]; p.draws_next = e->d_draws[(g + 1) & 1];
     p.ctl = e->d_ctl[g & 1]; p.ctl_next = e->d_ctl[(g + 1) & 1];
-    const bool fused_in = full && e->pending_accept;                  // generation g-1's accept rides in front of this phase-0 kernel
-    const bool need_draws = !fused_in && (!full || e->draws_gen != (int64_t)g);     // not prepared by the accept of the previous generation
-    const bool append = (g % (uint32_t)p.thin) == 0;                           // Dream.py:360
-    const bool publish = e->adapt && (int64_t)g < (int64_t)p.burnin + 1;      // Dream.py:364
-    const int nrows = full ? p.N : nc;
-    if (append && e->M + nrows > e->c.history_capacity) return fail("history capacity exceeded");
-    if (publish) {
-        if (full) { e->cp_idx = (e->cp_idx + 1) % 3; p.cp_prev = p.cp_new; p.cp_new = e->d_cp[e->cp_idx]; }      // (three buffers: a peer may be one generation ahead)
+    if (G.append && e->M + G.nrows > e->c.history_capacity) return fail("history capacity exceeded");
+    if (G.publish) {
+        if (G.full) { e->cp_idx = (e->cp_idx + 1) % 3; p.cp_prev = p.cp_new; p.cp_new = e->d_cp[e->cp_idx]; }      // (three buffers: a peer may be one generation ahead)
         else {   // the jump of a single chain is measured from its state at the start of the step
             const size_t n = (size_t)nc * p.ld;
             hipLaunchKernelGGL(dz::k_copy_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, p.X + (size_t)c0 * p.ld, p.cp_prev + (size_t)(p.off + c0) * p.ld, n);
         }
     }
-    // waves per block: 16 (one block fills a CU's 4 SIMDs evenly) once there is at least one such block per CU
-    const int wpb = e->nch >= 4 ? 4 : ((nc / L) >= 16 * e->num_cu ? 16 : 4);    // (k_propose<NCH >= 4> is built for 4-wave blocks)
-    // one wave per (chain, try) pays when a try is long and the chains are few: d > 512 (measured at 512 x 1000-D: +17%;
-    // at d <= 200 the per-chain wave with its fused Metropolis step is faster)
-    const int split = e->propose_split > 0 ? e->propose_split : (e->nch >= 8 ? k : 1);
-    const int sp0 = std::max(1, std::min(k, split)), sp1 = std::max(1, std::min(k - 1, split));
-    const int64_t slot = (traced && e->c.trace_capacity) ? e->ntrace : -1;
-    // the Metropolis step of this generation can ride in front of the next generation's proposal kernel when
-    // nothing shared changes in between (no history append, no published positions) and a generation follows
-    // ld > 256, one DE pair, multi-try: one wave per (chain, try) streaming over the dimension chunks (dz_kernels.h)
-    const bool streamed = e->nch >= 4 && p.depairs == 1 && k >= 3 && !redo_possible(e);     // (redraw rounds go through k_propose)
-    const bool redo = redo_possible(e);         // (then the proposal set's evaluation is followed by a check on the host: nothing is deferred)
-    const bool have_prop = streamed && full && e->stream_prop_gen == (int64_t)g;
-    e->stream_prop_gen = -1;
-    // ... and the streamed form of the same: accept(g) + proposal set(g+1) in one launch (k_accept_propose)
-    const bool fuse_next = streamed && full && more_follow && !append && !publish && !e->tempering && k <= 16;
-    const bool defer = full && more_follow && !append && !publish && split == 1 && e->lk != LK_HOST && !e->tempering && !streamed && !redo;
-    const int64_t zbase = full ? e->M : e->M - (int64_t)(p.off + c0);
-    // large d: the row-tile sums of the likelihood product are added by the kernels that use them (no k_q_finish launches)
-    // (round 5: also the per-chain proposal kernels of 128 < d <= 256 -- the reference example's own d = 200 --: two launches of six fewer)
-    const bool qdefer = e->q_defer && e->lk == LK_MVN && p.ld / 16 > 8 && (streamed || (full && k >= 3 && !redo_possible(e) && e->nch < 4 && e->nlanes == 1));
+    const int k = p.k;
+    const int64_t slot = G.slot, zbase = G.full ? e->M : e->M - (int64_t)(p.off + c0);
+    const double* pending_qfin_r = e->carry.pending_qfin ? e->last_qpart : nullptr;      // the deferred accept's reference-set sums, still in the scratch array
     p.qfin_p = nullptr; p.qfin_r = nullptr; p.qfin_nrt = (p.d + 15) / 16;
-    for (int s = 0; s < L; ++s) {
-        const int lc0 = c0 + (int)((int64_t)nc * s / L), lc1 = c0 + (int)((int64_t)nc * (s + 1) / L), lnc = lc1 - lc0;
-        if (lnc <= 0) continue;
-        hipStream_t st = e->lane_stream[s];
-        if (need_draws)
-            hipLaunchKernelGGL(dz::k_draws, dim3((lnc * p.nslots + 255) / 256), dim3(256), 0, st, p, g, lc0, lnc, e->d_draws[g & 1], e->d_ctl[g & 1]);
-        if (streamed && have_prop) { }                      // made by the k_accept_propose launch of the generation before
-        else if (streamed && !fused_in) DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose_stream, dim3((lnc * k + 3) / 4), dim3(256), 0, p, 0, g, Mv, lc0, lnc);
-        else {
-            if (fused_in) {      // (the Metropolis step of generation g - 1 in front: its reference set's row-tile sums may still be in the scratch array)
-                p.qfin_r = e->pending_qfin_r; p.qfin_c0 = lc0; p.qfin_nc = lnc;
-                NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, dim3((lnc + wpb - 1) / wpb), dim3(64 * wpb), 0, p, 0, g, Mv, lc0, lnc, 1, 1, e->pending_slot));
-                p.qfin_r = nullptr;
-            }
-            else { NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, dim3((lnc * sp0 + wpb - 1) / wpb), dim3(64 * wpb), 0, p, 0, g, Mv, lc0, lnc, sp0, 0, (int64_t)-1)); }
-        }
-        DZCK(launch_check("propose"));
-        DZCK(eval_logp(e, p.P + (size_t)lc0 * k * p.ld, lnc * k, p.p_prior + (size_t)lc0 * k, p.p_like + (size_t)lc0 * k, st, qdefer));
-        if (redo) DZCK(redraw_impossible_sets(e, g, lc0, lnc, sp0, wpb, st));
-        if (k > 1) {
-            if (qdefer) { p.qfin_p = e->last_qpart; p.qfin_c0 = lc0; p.qfin_nc = lnc; }
-            if (streamed) DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose_stream, dim3((lnc * (k - 1) + 3) / 4), dim3(256), 0, p, 1, g, Mv, lc0, lnc);
-            else {
-                NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, dim3((lnc * sp1 + wpb - 1) / wpb), dim3(64 * wpb), 0, p, 1, g, Mv, lc0, lnc, sp1, 0, (int64_t)-1));
-            }
+    for (int i = 0; i < G.ngroups; ++i) {
+        const dz::MultiGroup& q = G.grp[i];
+        const int lc0 = q.c0, lnc = q.nc;
+        hipStream_t st = e->lane_stream[q.stream];
+        if (G.need_draws) hipLaunchKernelGGL(dz::k_draws, g3(q.draws), b3(q.draws), 0, st, p, g, lc0, lnc, e->d_draws[g & 1], e->d_ctl[g & 1]);
+        if (G.prop0 == dz::PROP_STREAM) DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose_stream, g3(q.prop0), b3(q.prop0), 0, p, 0, g, Mv, lc0, lnc);
+        else if (G.prop0 == dz::PROP_FUSED_ACCEPT) {      // (the Metropolis step of generation g - 1 in front: its reference set's row-tile sums may still be in the scratch array)
+            p.qfin_r = pending_qfin_r; p.qfin_c0 = lc0; p.qfin_nc = lnc;
+            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, g3(q.prop0), b3(q.prop0), 0, p, 0, g, Mv, lc0, lnc, 1, 1, e->carry.pending_slot));
+            p.qfin_r = nullptr;
+        } else if (G.prop0 == dz::PROP_CHAIN)
+            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, g3(q.prop0), b3(q.prop0), 0, p, 0, g, Mv, lc0, lnc, G.sp0, 0, (int64_t)-1));
+        DZCK(launch_check("propose"));                    // (PROP_NONE: made by the k_accept_propose launch of the generation before)
+        DZCK(eval_logp(e, p.P + (size_t)lc0 * k * p.ld, q.n0, p.p_prior + (size_t)lc0 * k, p.p_like + (size_t)lc0 * k, st, G.qdefer));
+        if (G.redo) DZCK(redraw_impossible_sets(e, g, lc0, lnc, st));
+        if (q.n1 > 0) {
+            if (G.qdefer) { p.qfin_p = e->last_qpart; p.qfin_c0 = lc0; p.qfin_nc = lnc; }
+            if (G.streamed) DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose_stream, g3(q.prop1), b3(q.prop1), 0, p, 1, g, Mv, lc0, lnc);
+            else NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_PROPOSE, st, dz::k_propose<NCH>, g3(q.prop1), b3(q.prop1), 0, p, 1, g, Mv, lc0, lnc, G.sp1, 0, (int64_t)-1));
             DZCK(launch_check("propose(ref)"));
             p.qfin_p = nullptr;
-            DZCK(eval_logp(e, p.R + (size_t)lc0 * (k - 1) * p.ld, lnc * (k - 1), p.r_prior + (size_t)lc0 * (k - 1), p.r_like + (size_t)lc0 * (k - 1), st, qdefer));
-            if (qdefer) { p.qfin_r = e->last_qpart; p.qfin_c0 = lc0; p.qfin_nc = lnc; }
+            DZCK(eval_logp(e, p.R + (size_t)lc0 * (k - 1) * p.ld, q.n1, p.r_prior + (size_t)lc0 * (k - 1), p.r_like + (size_t)lc0 * (k - 1), st, G.qdefer));
+            if (G.qdefer) { p.qfin_r = e->last_qpart; p.qfin_c0 = lc0; p.qfin_nc = lnc; }
         }
-        if (fuse_next) {
-            const size_t lds = sizeof(double) * (size_t)p.ld + 64 * sizeof(uint4) + sizeof(dz::ChainCtl);
-            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_ACCEPT, st, dz::k_accept_propose<NCH>, dim3(lnc), dim3(64 * k), lds, p, g, zbase, lc0, lnc, slot, Mv));
+        if (G.acc == dz::ACC_ACCEPT_PROPOSE) {
+            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_ACCEPT, st, dz::k_accept_propose<NCH>, g3(q.accept), b3(q.accept), q.accept.lds, p, g, zbase, lc0, lnc, slot, Mv));
             DZCK(launch_check("accept + propose"));
-        } else if (!defer) {
-            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_ACCEPT, st, dz::k_accept<NCH>, dim3((lnc + wpb - 1) / wpb), dim3(64 * wpb), 0, p, g, zbase, lc0, lnc, slot, append ? 1 : 0, publish ? 1 : 0, (full && !publish) ? 1 : 0));
+        } else if (G.acc == dz::ACC_ACCEPT) {
+            NCH_DISPATCH(e, DZ_KLAUNCH(e, PR_ACCEPT, st, dz::k_accept<NCH>, g3(q.accept), b3(q.accept), 0, p, g, zbase, lc0, lnc, slot, G.append ? 1 : 0, G.publish ? 1 : 0, G.prep_next ? 1 : 0));
             DZCK(launch_check("accept"));
         }
         p.qfin_r = nullptr;
     }
-    if (fuse_next) e->stream_prop_gen = (int64_t)g + 1;
-    e->pending_accept = defer; e->pending_slot = defer ? slot : -1;
-    e->pending_qfin_r = (defer && qdefer && k > 1) ? e->last_qpart : nullptr;      // (one chain group when deferred sums are in play: see L below)
-    e->draws_gen = (full && !publish) ? (int64_t)g + 1 : -1;   // while adapting, next generation's decisions must wait for the new probabilities
-    if (publish || append) {         // shared state changed: the lanes meet before anything reads it
-        if (L > 1) DZCK(join_all(e));
-        if (publish) {
-            if (full && !e->adapt_groups) DZCK(exchange_rows(e, XK_POS, p.cp_new, 0));      // (ranks that own whole groups exchange their groups' sums: adapt_generation)
-            DZCK(adapt_generation(e, g, full ? 0 : p.off + c0, full ? p.N : nc));
+    e->carry = G.next;
+    if (G.publish || G.append) {         // shared state changed: the lanes meet before anything reads it
+        if (G.join_last) DZCK(join_all(e));
+        if (G.publish) {
+            if (G.exchange_positions) DZCK(exchange_rows(e, XK_POS, p.cp_new, 0));      // (ranks that own whole groups exchange their groups' sums: adapt_generation)
+            DZCK(adapt_generation(e, g, G.full ? 0 : p.off + c0, G.nrows));
         }
-        if (append) { if (full) DZCK(exchange_rows(e, XK_Z, p.Z, (size_t)e->M)); e->M += nrows; e->napp += 1; }
-        e->need_join = true;
+        if (G.append) { if (G.full) DZCK(exchange_rows(e, XK_Z, p.Z, (size_t)e->M)); e->M += G.nrows; e->napp += 1; }
     }
-    if (e->tempering && full) {      // temperature swap (core.py:185-221): after every chain's step and the updates above
-        if (L > 1) { DZCK(join_all(e)); e->need_join = true; }
-        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot, publish ? 1 : 0));
+    if (G.swap) {      // temperature swap (core.py:185-221): after every chain's step and the updates above
+        if (G.swap_join) DZCK(join_all(e));
+        NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot, G.publish ? 1 : 0));
         DZCK(launch_check("k_pt_swap"));
     }
     e->last_variant = "multi-kernel path"; e->last_kc = 0;
     for (int c = c0; c < c0 + nc; ++c) e->gen_c[c] = (int64_t)g + 1;
-    if (full) e->gen = (int64_t)g + 1;
+    if (G.full) e->gen = (int64_t)g + 1;
     if (slot >= 0) e->ntrace++;
     return 0;
 }
@@ -934,6 +869,22 @@ int one_generation(dz_engine* e, int c0, int nc, uint32_t g, bool traced, bool m
 // Which instantiation runs, with what grid, block and LDS size, is decided in dz_mega_select.h: mega_choose once per dz_step from the facts gathered
 // here -- the only selection code that reads the engine -- and mega_launch_plan once per launch.
 static_assert(LK_MVN == dz::MEGA_LK_MVN && LK_MIX == dz::MEGA_LK_MIX && LK_MODULE == dz::MEGA_LK_MODULE, "likelihood kinds");
+// ... and dz_multi_select.h decides the multi-kernel path's launches from the facts gathered here, the only selection code of that path that reads the engine
+static_assert(LK_MVN == dz::MULTI_LK_MVN && LK_MIX == dz::MULTI_LK_MIX && LK_HOST == dz::MULTI_LK_HOST && LK_MODULE == dz::MULTI_LK_MODULE, "likelihood kinds");
+dz::MultiShape multi_shape(const dz_engine* e)
+{
+    const dz::Params& p = e->p;
+    dz::MultiShape s;
+    s.d = p.d; s.ld = p.ld; s.k = p.k; s.depairs = p.depairs; s.nslots = p.nslots; s.nch = e->nch;
+    s.tri = p.tri != 0; s.mtp_len = p.mtp_len; s.mu_zero = p.mu_zero != 0; s.have_prior = p.have_prior != 0;
+    s.nl = p.nl; s.N = p.N; s.ncu = e->num_cu; s.nlanes = e->nlanes;
+    s.lk = e->lk; s.lk_lanes = e->lk_lanes; s.lk_items = e->lk_items;
+    s.redo_possible = redo_possible(e);
+    s.adapt = e->adapt; s.tempering = e->tempering; s.world = e->world; s.thin = p.thin; s.burnin = p.burnin; s.history_lag = e->c.history_lag; s.adapt_lag = e->c.adapt_lag;
+    s.adapt_groups = e->adapt_groups; s.trace = e->c.trace_capacity != 0;
+    s.propose_split = e->propose_split; s.q_defer = e->q_defer; s.logp_gemm = e->logp_gemm;
+    return s;
+}
 dz::MegaShape mega_shape(const dz_engine* e)
 {
     const dz::Params& p = e->p;
@@ -942,7 +893,7 @@ dz::MegaShape mega_shape(const dz_engine* e)
     s.tri = p.tri != 0; s.mtp = p.Mtp != nullptr; s.hard = p.hard != 0; s.have_prior = p.have_prior != 0;
     s.nl = p.nl; s.N = p.N; s.ncu = e->num_cu;
     s.lk = e->lk; s.lk_items = e->lk_items; for (int i = 0; i < 4; ++i) s.gen_fn[i] = e->lk_gen_fn[i] != nullptr;
-    s.redo_possible = redo_possible(e);
+    s.redo_possible = e->multi.redo_possible;      // (multi_shape's evaluation: mega_select)
     s.ad_multi = e->ad_multi; s.ad_R1 = e->ad_R1; s.ad_nbp = e->ad_nbp; s.adapt_lag = e->c.adapt_lag; s.adapt_fused = e->adapt_fused; s.adapt_groups = e->adapt_groups;
     s.tempering = e->tempering; s.world = e->world;
     s.mega = e->mega; s.mega_d2 = e->mega_d2; s.mega_kc = e->mega_kc; s.mega_redo = e->mega_redo_on;
@@ -1131,8 +1082,8 @@ int run_mega_segment(dz_engine* e, uint32_t g, int n, bool mega_follows)
         NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_pt_swap<NCH>, dim3(1), dim3(64), 0, e->stream, p, g, slot0, publish ? 1 : 0));
         DZCK(launch_check("k_pt_swap"));
     }
-    e->need_join = true;
-    e->draws_gen = -1;
+    e->carry.need_join = true;
+    e->carry.draws_gen = -1;
     e->gen = (int64_t)g + n;
     for (auto& gcv : e->gen_c) gcv = e->gen;
     if (slot0 >= 0) e->ntrace += n;
@@ -1413,7 +1364,7 @@ int dz_set_cr_probs(dz_engine* e, const double* pr, int32_t n)
     DZCK(sync_all(e));
     HIPCK(hipMemcpy(e->p.cr_probs, pr, sizeof(double) * n, hipMemcpyHostToDevice));
     std::fill(e->own_init.begin(), e->own_init.end(), 0);
-    e->draws_gen = -1;
+    e->carry.draws_gen = -1;
     return 0;
 }
 int dz_set_gamma_probs(dz_engine* e, const double* pr, int32_t n)
@@ -1424,7 +1375,7 @@ int dz_set_gamma_probs(dz_engine* e, const double* pr, int32_t n)
     DZCK(sync_all(e));
     HIPCK(hipMemcpy(e->p.g_probs, pr, sizeof(double) * n, hipMemcpyHostToDevice));
     std::fill(e->own_init.begin(), e->own_init.end(), 0);
-    e->draws_gen = -1;
+    e->carry.draws_gen = -1;
     return 0;
 }
 
@@ -1500,6 +1451,30 @@ int dz_set_likelihood_host(dz_engine* e, dz_logp_cb cb, void* user)
     return 0;
 }
 
+// A user's code object, one kernel of it and its data block on the device: all three or, on failure, none (the engine's module, function and data change
+// together, and only once every step has succeeded -- a failure leaves the engine as it was: advisor, round 5).  `who`: the caller's name in the messages.
+static int load_user_module(dz_engine* e, const char* who, const char* code_object_path, const char* kernel_name, const void* data, int64_t data_bytes, hipModule_t* mod, hipFunction_t* fn, void** d_data)
+{
+    HIPCK(hipSetDevice(e->c.device));
+    DZCK(sync_all(e));
+    hipError_t err = hipModuleLoad(mod, code_object_path);
+    if (err != hipSuccess) { (void)hipGetLastError(); return fail(std::string("hipModuleLoad(") + code_object_path + "): " + hipGetErrorString(err) + " (a gfx950 code object is expected: hipcc --offload-arch=gfx950 --genco)"); }
+    err = hipModuleGetFunction(fn, *mod, kernel_name);
+    if (err != hipSuccess) { (void)hipGetLastError(); (void)hipModuleUnload(*mod); return fail(std::string("hipModuleGetFunction(") + kernel_name + "): " + hipGetErrorString(err) + " (the kernel must be extern \"C\")"); }
+    *d_data = nullptr;
+    if (data_bytes > 0) {
+        hipError_t me = hipMalloc(d_data, (size_t)data_bytes);
+        if (me == hipSuccess) me = hipMemcpy(*d_data, data, (size_t)data_bytes, hipMemcpyHostToDevice);
+        if (me != hipSuccess) {
+            (void)hipGetLastError();
+            if (*d_data) (void)hipFree(*d_data);
+            (void)hipModuleUnload(*mod);
+            return fail(std::string(who) + ": data block: " + hipGetErrorString(me));
+        }
+    }
+    return 0;
+}
+
 int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const char* kernel_name, int32_t lanes_per_point, int32_t flags,
                              const void* data, int64_t data_bytes)
 {
@@ -1507,32 +1482,12 @@ int dz_set_likelihood_module(dz_engine* e, const char* code_object_path, const c
     if (lanes_per_point != 1 && lanes_per_point != 16 && lanes_per_point != 32 && lanes_per_point != 64)
         return fail("dz_set_likelihood_module: lanes_per_point must be 1 (a thread per point), 16 or 32 (a lane group per point) or 64 (a wave per point)");
     if (data_bytes < 0 || (data_bytes > 0 && !data)) return fail("dz_set_likelihood_module: bad data block");
-    HIPCK(hipSetDevice(e->c.device));
-    DZCK(sync_all(e));
-    hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
-    hipError_t err = hipModuleLoad(&mod, code_object_path);
-    if (err != hipSuccess) { (void)hipGetLastError(); return fail(std::string("hipModuleLoad(") + code_object_path + "): " + hipGetErrorString(err) + " (a gfx950 code object is expected: hipcc --offload-arch=gfx950 --genco)"); }
-    err = hipModuleGetFunction(&fn, mod, kernel_name);
-    if (err != hipSuccess) { (void)hipGetLastError(); (void)hipModuleUnload(mod); return fail(std::string("hipModuleGetFunction(") + kernel_name + "): " + hipGetErrorString(err) + " (the kernel must be extern \"C\")"); }
+    hipModule_t mod = nullptr; hipFunction_t fn = nullptr; void* d_new = nullptr;
+    DZCK(load_user_module(e, "dz_set_likelihood_module", code_object_path, kernel_name, data, data_bytes, &mod, &fn, &d_new));
     hipFunction_t gen[4] = {nullptr, nullptr, nullptr, nullptr};      // optional: the persistent kernels around the same density (a code object built by DeviceFunctionLogLike has them)
-    if (hipModuleGetFunction(&gen[0], mod, "dz_user_generations_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[0] = nullptr; }
-    if (hipModuleGetFunction(&gen[1], mod, "dz_user_generations_full_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[1] = nullptr; }
-    if (hipModuleGetFunction(&gen[2], mod, "dz_user_generations_wide_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[2] = nullptr; }
-    if (hipModuleGetFunction(&gen[3], mod, "dz_user_generations_wide_full_v" DZ_USER_STR(DZ_USER_ABI)) != hipSuccess) { (void)hipGetLastError(); gen[3] = nullptr; }
-    if (!e->mega_user) for (auto& gfn : gen) gfn = nullptr;
-    // the new data block first, into a temporary: the engine's module, function and data change together, and only once every step has
-    // succeeded -- a failure leaves the engine as it was (advisor, round 5)
-    void* d_new = nullptr;
-    if (data_bytes > 0) {
-        hipError_t me = hipMalloc(&d_new, (size_t)data_bytes);
-        if (me == hipSuccess) me = hipMemcpy(d_new, data, (size_t)data_bytes, hipMemcpyHostToDevice);
-        if (me != hipSuccess) {
-            (void)hipGetLastError();
-            if (d_new) (void)hipFree(d_new);
-            (void)hipModuleUnload(mod);
-            return fail(std::string("dz_set_likelihood_module: data block: ") + hipGetErrorString(me));
-        }
-    }
+    const char* gen_name[4] = {"dz_user_generations_v" DZ_USER_STR(DZ_USER_ABI), "dz_user_generations_full_v" DZ_USER_STR(DZ_USER_ABI), "dz_user_generations_wide_v" DZ_USER_STR(DZ_USER_ABI),
+                               "dz_user_generations_wide_full_v" DZ_USER_STR(DZ_USER_ABI)};
+    for (int i = 0; i < 4; ++i) if (!e->mega_user || hipModuleGetFunction(&gen[i], mod, gen_name[i]) != hipSuccess) { (void)hipGetLastError(); gen[i] = nullptr; }
     if (e->lk_module) { (void)hipModuleUnload(e->lk_module); e->lk_module = nullptr; e->lk_fn = nullptr; }
     if (e->d_lk_data) { (void)hipFree(e->d_lk_data); e->d_lk_data = nullptr; }
     e->d_lk_data = d_new;
@@ -1564,24 +1519,8 @@ int dz_set_output_module(dz_engine* e, const char* code_object_path, const char*
         return fail("dz_set_output_module: items_per_point must be 1.." DZ_USER_STR(DZ_MAX_LIKELIHOOD_ITEMS) " (got " + std::to_string(items_per_point) + ")");
     if (doubles_per_item < 1) return fail("dz_set_output_module: doubles_per_item must be >= 1 (got " + std::to_string(doubles_per_item) + ")");
     if (data_bytes < 0 || (data_bytes > 0 && !data)) return fail("dz_set_output_module: bad data block");
-    HIPCK(hipSetDevice(e->c.device));
-    DZCK(sync_all(e));
-    hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
-    hipError_t err = hipModuleLoad(&mod, code_object_path);
-    if (err != hipSuccess) { (void)hipGetLastError(); return fail(std::string("hipModuleLoad(") + code_object_path + "): " + hipGetErrorString(err) + " (a gfx950 code object is expected: hipcc --offload-arch=gfx950 --genco)"); }
-    err = hipModuleGetFunction(&fn, mod, kernel_name);
-    if (err != hipSuccess) { (void)hipGetLastError(); (void)hipModuleUnload(mod); return fail(std::string("hipModuleGetFunction(") + kernel_name + "): " + hipGetErrorString(err) + " (the kernel must be extern \"C\")"); }
-    void* d_new = nullptr;      // (as dz_set_likelihood_module: module, function and data change together, once every step has succeeded)
-    if (data_bytes > 0) {
-        hipError_t me = hipMalloc(&d_new, (size_t)data_bytes);
-        if (me == hipSuccess) me = hipMemcpy(d_new, data, (size_t)data_bytes, hipMemcpyHostToDevice);
-        if (me != hipSuccess) {
-            (void)hipGetLastError();
-            if (d_new) (void)hipFree(d_new);
-            (void)hipModuleUnload(mod);
-            return fail(std::string("dz_set_output_module: data block: ") + hipGetErrorString(me));
-        }
-    }
+    hipModule_t mod = nullptr; hipFunction_t fn = nullptr; void* d_new = nullptr;
+    DZCK(load_user_module(e, "dz_set_output_module", code_object_path, kernel_name, data, data_bytes, &mod, &fn, &d_new));
     if (e->out_module) (void)hipModuleUnload(e->out_module);
     if (e->d_out_data) (void)hipFree(e->d_out_data);
     e->d_out_data = d_new;
@@ -1791,7 +1730,7 @@ int dz_set_temperatures(dz_engine* e, const double* T, int32_t swaps)
     e->p.Tc = e->d_Tc;
     e->tempering = swaps != 0;
     if (e->tempering && !e->d_tswap) { DZCK(ealloc(e, &e->d_tswap, (size_t)3 * std::max<int64_t>(1, e->c.trace_capacity))); e->p.tswap = e->d_tswap; }
-    e->draws_gen = -1;
+    e->carry.draws_gen = -1;
     return 0;
 }
 int dz_get_swaps(dz_engine* e, int64_t g0, int64_t ng, int32_t* out)
@@ -1863,8 +1802,8 @@ int dz_continue_run(dz_engine* e, int64_t history_capacity, int64_t trace_capaci
     if (e->d_redraw_count) HIPCK(hipMemset(e->d_redraw_count, 0, sizeof(unsigned long long)));
     HIPCK(hipStreamSynchronize(nullptr));
     e->gen = 0; std::fill(e->gen_c.begin(), e->gen_c.end(), (int64_t)0);
-    e->napp = 0; e->ntrace = 0; e->draws_gen = -1; e->pending_accept = false; e->pending_slot = -1; e->stream_prop_gen = -1;
-    e->have_logp = false; e->need_join = true; e->redraw_rounds = 0;
+    e->napp = 0; e->ntrace = 0; e->carry = dz::MultiCarry();
+    e->have_logp = false; e->redraw_rounds = 0;
     e->ad_applied = -1; e->ad_made = -1;
     std::fill(e->own_init.begin(), e->own_init.end(), 0);
     if (e->adapt) { p.cp_prev = e->d_cp[0]; p.cp_new = e->d_cp[1]; e->cp_idx = 1; }
@@ -1880,6 +1819,7 @@ int dz_step(dz_engine* e, int64_t generations)
     if (e->lk == LK_NONE) return fail("no likelihood set");
     if (e->M < 2 * e->c.depairs) return fail("history not seeded");
     if (e->c.trace_capacity && e->ntrace + generations > e->c.trace_capacity) return fail("trace capacity exceeded");
+    e->multi = multi_shape(e);      // (nothing either selection reads changes inside a dz_step)
     if (!e->have_logp) {   // Dream.py:266-268
         DZCK(eval_logp(e, e->p.X, e->p.nl, e->p.lprior, e->p.llike));
         e->have_logp = true;
@@ -1889,7 +1829,7 @@ int dz_step(dz_engine* e, int64_t generations)
     e->p.own_cr = nullptr; e->p.own_g = nullptr;                   // lockstep generations read the shared probabilities;
     std::fill(e->own_init.begin(), e->own_init.end(), 0);          // a later single-chain step starts from them again
     const bool mega = mega_select(e);
-    e->stream_prop_gen = -1;
+    e->carry.stream_prop_gen = -1;
     for (int64_t i = 0; i < generations;) {
         DZCK(peer_check(e));            // a gate that gave up is fatal: nothing more is queued behind it
         const int n = mega ? mega_segment(e, (uint32_t)e->gen, generations - i) : 0;
@@ -1916,6 +1856,7 @@ int dz_step_range(dz_engine* e, int32_t c0, int32_t nc)
     if (c0 < 0 || nc < 1 || c0 + nc > e->p.nl) return fail("bad chain range");
     if (e->lk == LK_NONE) return fail("no likelihood set");
     if (e->M < 2 * e->c.depairs) return fail("history not seeded");
+    e->multi = multi_shape(e);
     if (!e->have_logp) { DZCK(eval_logp(e, e->p.X, e->p.nl, e->p.lprior, e->p.llike)); e->have_logp = true; }
     for (int c = c0 + 1; c < c0 + nc; ++c) if (e->gen_c[c] != e->gen_c[c0]) return fail("chains of the range are at different generations");
     return one_generation(e, c0, nc, (uint32_t)e->gen_c[c0], false, false);
@@ -1925,6 +1866,7 @@ int dz_set_chain_state(dz_engine* e, int32_t c, const double* x, const double* p
 {
     HIPCK(hipSetDevice(e->c.device));
     if (c < 0 || c >= e->p.nl) return fail("bad chain index");
+    e->multi = multi_shape(e);
     if (!e->have_logp) { DZCK(eval_logp(e, e->p.X, e->p.nl, e->p.lprior, e->p.llike)); e->have_logp = true; }
     DZCK(upload_padded(e, e->p.X + (size_t)c * e->p.ld, x, 1, 0.0));
     if (prior && like) {
@@ -2223,11 +2165,8 @@ int dz_get_rhat(dz_engine* e, double* rhat)
 
 static int need_scratch(dz_engine* e, size_t rows)
 {
-    if (e->scratch_rows >= rows) return 0;
-    if (e->d_scratch) (void)hipFree(e->d_scratch);
-    e->d_scratch = nullptr; e->scratch_rows = 0;
-    HIPCK(hipMalloc((void**)&e->d_scratch, sizeof(double) * (rows * e->p.ld + 4 * rows)));
-    e->scratch_rows = rows;
+    const hipError_t err = grow_doubles(&e->d_scratch, &e->scratch_rows, rows, rows * e->p.ld + 4 * rows, false);
+    if (err != hipSuccess) return fail(std::string("hipMalloc((void**)&e->d_scratch, sizeof(double) * (rows * e->p.ld + 4 * rows)): ") + hipGetErrorString(err));
     return 0;
 }
 
@@ -2238,21 +2177,11 @@ int dz_eval_logp(dz_engine* e, const double* X, int64_t n, double* prior, double
     DZCK(need_scratch(e, (size_t)n));
     double* pts = e->d_scratch; double* dp = pts + (size_t)n * e->p.ld; double* dl = dp + n;
     DZCK(upload_padded(e, pts, X, (int)n, 0.0));
+    e->multi = multi_shape(e);
     DZCK(eval_logp(e, pts, (int)n, dp, dl));
     DZCK(sync_all(e));
     HIPCK(hipMemcpy(prior, dp, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIPCK(hipMemcpy(like, dl, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-static int need_doubles(double** buf, size_t* have, size_t want, const char* what)
-{
-    if (*have >= want) return 0;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-    hipError_t err = hipMalloc((void**)buf, sizeof(double) * want);
-    if (err != hipSuccess) { (void)hipGetLastError(); *buf = nullptr; return fail(std::string("dz_eval_outputs: cannot allocate ") + std::to_string(want) + " doubles for " + what + ": " + hipGetErrorString(err)); }
-    *have = want;
     return 0;
 }
 
@@ -2268,8 +2197,11 @@ int dz_eval_outputs(dz_engine* e, const double* X, int64_t n, double* like_items
     if (blocks > 0x7fffffffll) return fail("dz_eval_outputs: " + std::to_string(items) + " items are more than one launch's grid holds");
     DZCK(need_scratch(e, (size_t)n));
     DZCK(sync_all(e));
-    DZCK(need_doubles(&e->d_out, &e->out_len, (size_t)items * (size_t)e->out_doubles, "the outputs"));
-    DZCK(need_doubles(&e->d_out_like, &e->out_like_len, (size_t)items, "the terms"));
+    const struct { double** buf; size_t* have; size_t want; const char* what; } outs[] = {{&e->d_out, &e->out_len, (size_t)items * (size_t)e->out_doubles, "the outputs"}, {&e->d_out_like, &e->out_like_len, (size_t)items, "the terms"}};
+    for (const auto& o : outs) {
+        const hipError_t err = grow_doubles(o.buf, o.have, o.want, o.want, false);
+        if (err != hipSuccess) return fail(std::string("dz_eval_outputs: cannot allocate ") + std::to_string(o.want) + " doubles for " + o.what + ": " + hipGetErrorString(err));
+    }
     double* pts = e->d_scratch;
     DZCK(upload_padded(e, pts, X, (int)n, 0.0));
     struct { const double* X; long long n; int d; int ld; double* like; const void* data; double* out; long long out_ld; } a =

@@ -9,6 +9,7 @@
 #pragma once
 #include "dz_device.h"
 #include "dz_mega_select.h"      // MAXK, tri_row_offset and the persistent kernels' LDS layout: shared with the host-side selection
+#include "dz_multi_select.h"     // ... and the LDS carvings of k_logp_mvn_lds and k_accept_propose
 
 namespace dz {
 
@@ -16,6 +17,7 @@ constexpr int MAXPAIR = 8;    // DEpairs limit
 
 // per-chain control decisions of one generation, computed once (lane-parallel) instead of by every wave
 struct ChainCtl { int snk, cr_idx, delta, glev; double u_sel, u_acc; };
+static_assert(sizeof(ChainCtl) == MULTI_CHAINCTL_BYTES && sizeof(uint4) == MULTI_UINT4_BYTES, "accept_propose_layout (dz_multi_select.h)");
 
 struct Params {
     int N, nl, off, d, ld, k, depairs, ncr, ngamma, thin, burnin, adapt_cr, adapt_g, hard;
@@ -1261,9 +1263,10 @@ __global__ __launch_bounds__(512) void k_logp_mvn_lds(Params p, const double* __
     const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, nwv = blockDim.x >> 6, bdim = blockDim.x;   // 4..8 waves: one per point tile of the CU's share
     const int d = p.d;
     const int KS = (d + 3) >> 2;
+    const LogpLdsLayout lay = logp_lds_layout(d, LD, TRI, p.mtp_len, nwv);
     double* Ms = smem;                                    // [4*KS][LD], or the packed triangle
-    double* mus = Ms + (TRI ? (size_t)p.mtp_len : (size_t)4 * KS * LD);      // [LD]
-    double* Vt = mus + LD + (size_t)wv * 16 * LDT;        // [16][LDT] per wave
+    double* mus = Ms + lay.off_mu;                        // [LD]
+    double* Vt = smem + lay.off_tiles + (size_t)wv * lay.tile;        // [16][LDT] per wave
     const int pi = l & 15, kq = l >> 4;
     const int ntiles = (npts + 15) >> 4;
     const double* mbase = Ms + (size_t)kq * LD + pi;
@@ -1749,8 +1752,9 @@ __global__ __launch_bounds__(1024) void k_accept_propose(Params p, uint32_t g, i
     extern __shared__ __attribute__((aligned(16))) double xs[];           // [ld] state | 64 uint4 draws | ChainCtl
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int c = c0 + blockIdx.x;
-    uint4* sdraw = reinterpret_cast<uint4*>(xs + p.ld);
-    ChainCtl* sctl = reinterpret_cast<ChainCtl*>(sdraw + 64);
+    const AcceptProposeLayout lay = accept_propose_layout(p.ld);
+    uint4* sdraw = reinterpret_cast<uint4*>(xs + lay.off_draws);
+    ChainCtl* sctl = reinterpret_cast<ChainCtl*>(xs + lay.off_ctl);
     if (wv == 0) {
         double xn[NCH][2]; DrawSrc dn; ChainCtl cn;
         accept_chain<NCH>(p, g, zbase, c, lane, trace_slot, 0, 0, 1, p.ctl, p.ctl_next, p.draws_next, xn, dn, cn);
