@@ -84,6 +84,7 @@ class _Network:
         self.S, self.reactions, self.observables, self.log10 = like.n_species, like.reactions, like.observables, like.log10
         self.mono, self.events, self.equilibrate = like._monomials(), like._max_events(), like._equilibrates()
         self.items, self.lanes, self.noise = like.conditions is not None, like.lanes_per_point, like.noise
+        self.settle = like._settles()          # the last output time is +inf (csrc/dz_ode.h, STEADY OUTPUT)
         self.inputs = [(u.species, u.gain) for u in like.inputs or ()]      # (species, gain): the tables are the data block's
         self.view = like._view_size() if like._has_view() else 0            # P of a network whose conditions view the point (csrc/dz_ode.h, VIEWS)
         self.R = len(self.reactions)
@@ -290,7 +291,7 @@ def _net_source(net, body):
     """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
     closing brace of the last one), the members of a network with inputs (net.drive: where the emitter put their drives), of one with monomials, the observables and the entry macro.  net.events: the
     largest event count over the object's experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  net.equilibrate: some
-    experiment equilibrates first; the member EQUILIBRATE only then."""
+    experiment equilibrates first; the member EQUILIBRATE only then.  net.settle: the object's t ends in inf; the member SETTLE only then."""
     if net.lanes == 1:
         header, entries = "dz_ode.h", "DZODE_ITEM_ENTRIES(Net)" if net.items else "DZODE_ENTRIES(Net)"
     else:
@@ -298,6 +299,7 @@ def _net_source(net, body):
     L = ["struct Net {", "    static constexpr int S = %d, R = %d, O = %d;" % (net.S, net.R, len(net.observables))]
     L += ["    static constexpr int EVENTS = %d;" % net.events] if net.events else []
     L += ["    static constexpr bool EQUILIBRATE = true;"] if net.equilibrate else []
+    L += ["    static constexpr bool SETTLE = true;"] if net.settle else []
     L += ["    static constexpr int VIEW = %d;" % net.view] if net.view else []
     L += _input_members(net, net.drive) if net.inputs else []
     L += body + (_monomial_members(net.mono) if net.mono else []) + (_noise_members(net) if net.noise else [])

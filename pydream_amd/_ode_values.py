@@ -8,6 +8,7 @@ ODE_WAVE_LIMITS = dict(species=64, reactions=256, observables=16, times=4096, la
 ODE_MAX_CONSTRAINTS = 16    # constraints=[(Monomial, loc, sd), ...]
 ODE_MAX_EVENTS = 16         # events=[(time, species, factor, amount), ...] per experiment
 ODE_EQUILIBRATE_MAX_STEPS = 2000    # equilibrate=...: the attempted steps of the phase before the experiment, unless its "max_steps" says otherwise
+ODE_SETTLE_MAX_STEPS = 2000         # settle=...: the attempted steps of the phase ahead of a steady output (t[-1] = inf), unless its "max_steps" says otherwise
 ODE_MAX_CONDITIONS = 64     # conditions=[...], either shape: the engine's DZ_MAX_LIKELIHOOD_ITEMS (ODE_LIMITS: the one-lane shape's own four limits)
 ODE_MAX_HILL_EXPONENT = 8   # Hill(species, K, n): n = 1..8, powers as repeated products
 ODE_MAX_RATE_FACTORS = 4    # RateLaw(rate, factors): at most 4 Hill factors per reaction

@@ -213,6 +213,43 @@
 //     index a constant, handed to the generated code in the point's place; a lane group or a wave per item: P more doubles at the end
 //     of the group's LDS row (dz_ode_group.h), lane r gathering i = r, r + L, ..., one block-wide barrier ahead of the rate constants.
 //
+// STEADY OUTPUT (MassActionODELogLike(t=[..., inf], settle=...)): a measurement of the steady state the experiment ends in -- a dose-response
+// point, a binding equilibrium, PEtab's time = inf --, the counterpart of EQUILIBRATION at the other end of the experiment.  The object's
+// last output time is +inf; t_last is the last finite output time, or t0 if there is none (T = 1).  A network of such an object carries
+//     static constexpr bool SETTLE = true;
+// tt[T-1] is +inf, row T-1 of data and sd is the steady-state measurement, and EVERY experiment's block (each sub-block, with conditions)
+// grows by the phase's six doubles
+//     on (always 1: t is shared by the conditions),   rtol_ss,   atol_ss,   horizon,   max_step,   max_steps_ss
+// which sit BEHIND the equilibration's six doubles (if the network has them; else behind the event records if there are any, else behind
+// sd) and IN FRONT OF the input knots' count K_c and records and of the view pairs, which stay at the block's very end:
+//     header, y0, t, data, sd | E_c, events | equilibration's six | SETTLE's six | K_c, knots | view pairs
+// The block, the source and the code object of a network without the member are what they always were.  The contract, the same in both
+// builds and every shape:
+//   1. AT t_last.  The finite outputs run exactly as without the member, with t_last wherever the solver reads "the end of the
+//      experiment" (the start step's span at t0 and after events).  At t_last the order at one time holds: the output at t_last, then
+//      the knots that are due, then the events that are due in the order given -- an event at t_last, which has no effect in an object
+//      with a finite last output, is "measure, intervene, let it settle".  The inputs are then HELD at their value at t_last with every
+//      drive 0, as ahead of an equilibration: Python ends the working knots of such an object with one record (t_last, i, u_i(t_last), 0)
+//      per input, in ascending i, behind every other knot (also behind the knots at t0 when t_last = t0), so the knots that are due at
+//      t_last do the holding and the solver has no code of its own for it.
+//   2. THE PHASE is dzode::equilibrate's loop (its instantiation AT_END, below: one loop in the source) on the SETTLE record:
+//      h = start_step(y, rtol, atol, horizon), not finite or not > 0: -inf; the steady-state test drift2(y, rtol_ss, atol_ss) * horizon^2
+//      <= 1 before every attempted step, so also on the state as it arrives; the step, the error test, the negativity rule and the
+//      rejection rule are the experiment's, with its rtol and atol; no step is clipped; after an accepted step h = min(h * fac,
+//      max_step); -inf when the state is not steady after max_steps_ss attempts, a state is not finite, the matrix is singular or a step
+//      is not > 0.  No clock, no cursor and no record is carried through the loop; the six doubles are read where they are used.
+//      Hence the HAND-OVER IDENTITY: the phase applied to a state y gives the bits of the equilibration phase of a second object that
+//      starts from y0 = y with `equilibrate` set to the same five numbers.  nsteps_out includes the phase's accepted steps.
+//   3. THE OUTPUT.  At the state where the test passed: observe, then the terms of row T-1 by the statements the finite rows run (the
+//      network's noise_terms, or the fixed-sd residual): in integrate the phase stands where the steps to a finite output time stand,
+//      and the pass then falls into the same output code.  A failure there is -inf, as at a finite row.
+//   4. CONTROL FLOW stays uniform within a lane group and a wave: the record comes from the block and the test's result is one value
+//      per group.  Lanes of the one-lane shape leave the phase at different counts.  A point that is not live takes no step but stays
+//      with its wave.
+// Every loop stays bounded: the phase adds at most max_steps_ss attempted steps.  integrate_fixed ignores the phase, as it ignores events.
+// Not supported: more than one steady row, a steady state between two finite outputs, Newton polishing of the state (conservation laws
+// make the Jacobian singular).
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -329,6 +366,10 @@ template <class Net> struct has_events<Net, decltype((void)Net::EVENTS)> {
 // ... and the equilibration phase (the head of the file): the network of an object that equilibrates in at least one experiment
 template <class Net, class = void> struct has_equilibrate { static constexpr bool value = false; };
 template <class Net> struct has_equilibrate<Net, decltype((void)Net::EQUILIBRATE)> { static constexpr bool value = Net::EQUILIBRATE; };
+
+// ... and the steady output (the head of the file, STEADY OUTPUT): the network of an object whose last output time is +inf
+template <class Net, class = void> struct has_settle { static constexpr bool value = false; };
+template <class Net> struct has_settle<Net, decltype((void)Net::SETTLE)> { static constexpr bool value = Net::SETTLE; };
 
 // ... and rate laws (the head of the file): SLOTS is the number of distinct Hill (K, n) pairs, the doubles behind the rate constants
 template <class Net, class = void> struct has_slots { static constexpr bool value = false; static constexpr int count = 0; };
@@ -639,7 +680,8 @@ DZO_HD double start_h(double h0, double d1, double d2h, double span)      // d2h
 //     sh.any_negative(yn, y, rtol, atol)               an amount of yn below -(atol + rtol |y|)
 //     sh.observe(y, o)                                 o[O]
 //     Shape::EVENTS, sh.apply(y, species, factor, amount)   (a network with events: Emax, and y[species] = factor * y[species] + amount)
-//     Shape::EQUILIBRATE, sh.drift2(y, rtol, atol)     (a network that equilibrates: the steady-state test's wnorm2(f(y), y, rtol, atol))
+//     Shape::EQUILIBRATE, Shape::SETTLE, sh.drift2(y, rtol, atol)   (a network that equilibrates or has a steady output -- either member
+//                                                      alone asks for it --: the steady-state test's wnorm2(f(y), y, rtol, atol))
 //     Shape::Net, sh.noise()                           (a network with sampled noise: where the point's 2 O noise values are)
 //     Shape::INPUTS, sh.knot(y, i, value, slope)       (a network with inputs: I, and y[species_i] = g_i * value, drive_i = g_i * slope)
 // and there are three: Array<OneLane<Net>> (below: one lane or one host loop iteration per point), Array<HostGroup<Net, L>> and
@@ -662,7 +704,8 @@ template <class Shape>
 DZO_HD const double* input_knots(const double* blk)
 {
     const long long per = (long long)(int)blk[5] * Shape::O;
-    return blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0) + (Shape::EQUILIBRATE ? 6 : 0);
+    return blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0) + (Shape::EQUILIBRATE ? 6 : 0) +
+           (Shape::SETTLE ? 6 : 0);
 }
 
 // The start of an experiment of a network with inputs: every input held at its value at t0 with drive 0 (the knots at t0 with slope 0).
@@ -697,11 +740,14 @@ DZO_HD double next_knot(const double* blk, int kn)
     return kn < (int)dmin(inp[0], (double)MAX_INPUT_KNOTS) ? inp[1 + 4 * kn] : __builtin_huge_val();
 }
 
-template <class Shape>
+// (AT_END: the same loop on the steady output's record, which sits behind the equilibration's, from the state at t_last -- the head of
+// the file, STEADY OUTPUT; dzode::settle below.  One loop in the source, an instantiation per phase.)
+template <class Shape, bool AT_END = false>
 DZO_HD bool equilibrate(const Shape& sh, const double* blk, typename Shape::State& y, bool ok, int& nsteps, int* attempts)
 {
     const long long per = (long long)(int)blk[5] * Shape::O;
-    const double* eq = blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0);
+    const double* eq = blk + 6 + Shape::S + (int)blk[5] + 2 * per + (Shape::EVENTS > 0 ? 1 + 4 * Shape::EVENTS : 0) +
+                       (AT_END && Shape::EQUILIBRATE ? 6 : 0);
     if (attempts) *attempts = 0;
     if (eq[0] == 0.0) return ok;
     const double rtol = blk[1], atol = blk[2], rtol_ss = eq[1], atol_ss = eq[2], horizon = eq[3], max_step = eq[4];
@@ -736,8 +782,22 @@ DZO_HD bool equilibrate(const Shape& sh, const double* blk, typename Shape::Stat
     return ok;
 }
 
+// The steady output's phase (the head of the file, STEADY OUTPUT): equilibrate's loop on the record behind the equilibration's.
 template <class Shape>
-DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* sim, int* nsteps_out)
+DZO_HD bool settle(const Shape& sh, const double* blk, typename Shape::State& y, bool ok, int& nsteps, int* attempts)
+{
+    return equilibrate<Shape, true>(sh, blk, y, ok, nsteps, attempts);
+}
+
+// The end of the experiment as the start steps' span reads it: the last output time, or for a network with a steady output t_last, the
+// last finite one (t0 if there is none).  Read where it is used and not carried through the loop.  (Only a network with a steady
+// output calls it: the others keep the statements they always had, and so their code objects.)
+DZO_HD double last_finite_time(const double* tt, int T, double t0) { return T > 1 ? tt[T - 2] : t0; }
+
+// settled (optional; array shapes): the state at which the steady output's test passed; settle_attempts: the phase's attempted steps.
+template <class Shape>
+DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* sim, int* nsteps_out,
+                        typename Shape::State* settled = nullptr, int* settle_attempts = nullptr)
 {
     constexpr int S = Shape::S, O = Shape::O;
     const double rtol = blk[1], atol = blk[2], t0 = blk[4];
@@ -759,8 +819,15 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     [[maybe_unused]] int kn = 0;                                             // the knot cursor
     if constexpr (IN > 0) kn = due_knots(sh, blk, y, kn, t0);               // the knots at t0 are part of the start: the first slopes
     if constexpr (EV == 0) {
-        h = ok ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
-        ok = ok && finite(h) && h > 0.0;
+        if constexpr (Shape::SETTLE) {
+            if (T > 1) {                                                     // (a steady output alone: no finite stretch, no start step for one)
+                h = ok ? sh.start_step(y, rtol, atol, dmax(last_finite_time(tt, T, t0) - t0, 1e-300)) : 0.0;
+                ok = ok && finite(h) && h > 0.0;
+            }
+        } else {
+            h = ok ? sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t0, 1e-300)) : 0.0;
+            ok = ok && finite(h) && h > 0.0;
+        }
     }
     // (without events the block ends with sd: evt is then the pointer one past its end, only formed and never read)
     [[maybe_unused]] const double* evt = sd + (long long)T * O + (EV > 0 ? 1 : 0);      // records of (time, species, factor, amount)
@@ -777,8 +844,12 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
                 sh.apply(y, (int)evt[4 * ev + 1], evt[4 * ev + 2], evt[4 * ev + 3]);
                 fresh = true;
             }
+            if constexpr (Shape::SETTLE) {
+                if (j == T - 1) fresh = false;                               // (the steady output's pass: the phase has a start step of its own)
+            }
             if (fresh) {
-                h = sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t, 1e-300));
+                if constexpr (Shape::SETTLE) h = sh.start_step(y, rtol, atol, dmax(last_finite_time(tt, T, t0) - t, 1e-300));
+                else h = sh.start_step(y, rtol, atol, dmax(tt[T - 1] - t, 1e-300));
                 rejected = false;
                 fresh = false;
                 if (!(finite(h) && h > 0.0)) { ok = false; break; }
@@ -786,6 +857,17 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             if (ev < E && evt[4 * ev] < tout) tend = evt[4 * ev];            // (an event at tout: after the output, in the next pass)
         }
         if constexpr (IN > 0) tend = dmin(tend, next_knot<Shape>(blk, kn));  // (a knot at tout: after the output; the controller is not restarted)
+        if constexpr (Shape::SETTLE) {
+            if (j == T - 1) {                                                // the steady output's pass (tout = +inf): everything due at t_last is applied, the inputs are held
+                ok = settle(sh, blk, y, ok, nsteps, settle_attempts);
+                if (ok && settled) *settled = y;
+                // INVARIANT: nothing is due after t_last -- Python refuses an event beyond it and cuts the working knots there --, so
+                // tend is +inf here.  It is set all the same: with a record left over, `tend < tout` below would send the pass round
+                // again and the phase would run twice.
+                tend = tout;
+                t = tout;                                                    // (the clock is not read again)
+            }
+        }
         for (int n = 0; t < tend; ++n) {
             const bool clip = t + h >= tend;
             const double hs = clip ? tend - t : h;
@@ -872,7 +954,7 @@ template <class Alg>
 struct Array {
     static constexpr int S = Alg::Net::S, O = Alg::Net::O, EVENTS = has_events<typename Alg::Net>::count;
     static constexpr int INPUTS = has_inputs<typename Alg::Net>::count;
-    static constexpr bool EQUILIBRATE = has_equilibrate<typename Alg::Net>::value;
+    static constexpr bool EQUILIBRATE = has_equilibrate<typename Alg::Net>::value, SETTLE = has_settle<typename Alg::Net>::value;
     typedef typename Alg::Net Net;
     struct State { double v[S]; };
     const double* k;                                   // the rate constants
@@ -934,7 +1016,8 @@ struct Array {
 // One point through an array shape.  The rate constants are tested here, ahead of the loop, and the loop runs with live a constant.
 // first: the single experiment, or condition 0 of several -- the term that a network's constraints are added to.
 template <class Alg>
-DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out, bool first = true)
+DZO_HD double integrate_point(const double* x, const double* blk, double* sim, int* nsteps_out, bool first = true,
+                              typename Array<Alg>::State* settled = nullptr, int* settle_attempts = nullptr)
 {
     double k[rate_doubles<typename Alg::Net>()];
     [[maybe_unused]] double nz[noise_doubles<typename Alg::Net>()];
@@ -943,9 +1026,9 @@ DZO_HD double integrate_point(const double* x, const double* blk, double* sim, i
     clear_drives<typename Alg::Net>(k);
     if constexpr (has_noise<typename Alg::Net>::value) {
         if (!noise_point<typename Alg::Net>(x, nz)) return -__builtin_huge_val();
-        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x, nz}, blk, true, sim, nsteps_out), x, first);
+        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x, nz}, blk, true, sim, nsteps_out, settled, settle_attempts), x, first);
     } else {
-        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out), x, first);
+        return add_constraints<typename Alg::Net>(integrate(Array<Alg>{k, x}, blk, true, sim, nsteps_out, settled, settle_attempts), x, first);
     }
 }
 
@@ -970,6 +1053,20 @@ DZO_HD void equilibrate_point(const double* x, const double* blk, double* yss, i
             ok = equilibrate(sh, blk, y, ok, steps, attempts);
         }
     }
+    for (int s = 0; s < S; ++s) yss[s] = ok ? y.v[s] : __builtin_nan("");
+}
+
+// The host build's settled state of one point's experiment (blk: one experiment's block; the head of the file, STEADY OUTPUT): the state
+// at which the steady output's test passed, NaN where the item failed -- the point is not live, the experiment or the phase failed, or
+// row T-1's terms did -- and throughout for a network without a steady output.  attempts: the phase's attempted steps.
+template <class Alg>
+DZO_HD void settle_point(const double* x, const double* blk, double* yss, int* attempts)
+{
+    constexpr int S = Alg::Net::S;
+    typename Array<Alg>::State y;
+    *attempts = 0;
+    const double v = integrate_point<Alg>(x, blk, nullptr, nullptr, false, &y, attempts);      // (no constraints: the item's own term)
+    const bool ok = Array<Alg>::SETTLE && v != -__builtin_huge_val() && v == v;
     for (int s = 0; s < S; ++s) yss[s] = ok ? y.v[s] : __builtin_nan("");
 }
 
@@ -1089,6 +1186,10 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
     {                                                                                                                                    \
         for (long long i = 0; i < n; ++i) dzode::equilibrate_point<ALG>(X + i * ld, blk, yss + i * ALG::Net::S, attempts + i);          \
     }                                                                                                                                    \
+    extern "C" void dzode_settle(const double* X, long long n, int ld, const double* blk, double* yss, int* attempts)                   \
+    {                                                                                                                                    \
+        for (long long i = 0; i < n; ++i) dzode::settle_point<ALG>(X + i * ld, blk, yss + i * ALG::Net::S, attempts + i);               \
+    }                                                                                                                                    \
     DZODE_HOST_COMMON(ALG)
 
 // ... and those of C conditions (blk: the block with the [C, stride] header): dzode_loglike gives the points' sums (nsteps: over the
@@ -1112,6 +1213,16 @@ DZO_HD bool integrate_fixed(const double* x, const double* blk, double t1, int n
             const double* sub = blk + 2 + (w % C) * stride;                                                                              \
             dzode::equilibrate_point<ALG>(dzode::viewed_row<ALG::Net>(X + (w / C) * ld, sub, stride, xv), sub, yss + w * ALG::Net::S,    \
                                           attempts + w);                                                                                 \
+        }                                                                                                                                \
+    }                                                                                                                                    \
+    extern "C" void dzode_settle(const double* X, long long n, int ld, const double* blk, double* yss, int* attempts)                   \
+    {                                                                                                                                    \
+        const long long C = (long long)blk[0], stride = (long long)blk[1];                                                               \
+        double xv[dzode::view_doubles<ALG::Net>()];                                                                                      \
+        for (long long w = 0; w < n * C; ++w) {                                                                                          \
+            const double* sub = blk + 2 + (w % C) * stride;                                                                              \
+            dzode::settle_point<ALG>(dzode::viewed_row<ALG::Net>(X + (w / C) * ld, sub, stride, xv), sub, yss + w * ALG::Net::S,         \
+                                     attempts + w);                                                                                      \
         }                                                                                                                                \
     }                                                                                                                                    \
     DZODE_HOST_COMMON(ALG)

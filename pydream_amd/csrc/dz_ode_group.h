@@ -51,7 +51,8 @@
 // applied (Group::knot) and the generated rhs_row of the input's row selects; the host twin keeps the same 2 I entries in its array k.
 // Data block: dz_ode.h's (with several conditions: its [C, stride] header and C sub-blocks; with events: its records after sd; with the
 // equilibration phase: its six doubles at the end; with inputs: the knot records behind those.  The phase itself is dz_ode.h's loop on this shape's drift2: the lane's rhs_row and
-// the group's norm, a group-wide value).
+// the group's norm, a group-wide value; with a steady output, dz_ode.h's STEADY OUTPUT: its six doubles behind the equilibration's and in
+// front of the knots, and the same loop on the same drift2 at the experiment's end).
 #pragma once
 #include "dz_ode.h"
 
@@ -431,7 +432,7 @@ template <class NET, int L>
 struct Group {
     typedef NET Net;
     static constexpr int S = Net::S, O = Net::O, EVENTS = has_events<Net>::count, INPUTS = has_inputs<Net>::count;
-    static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value;
+    static constexpr bool EQUILIBRATE = has_equilibrate<Net>::value, SETTLE = has_settle<Net>::value;
     typedef double State;
     double* ks;                                        // the point's row of LDS: its rate constants (64 lanes: and its state behind them)
     int r;
@@ -442,7 +443,9 @@ struct Group {
     {
         return group_start_step<Net, L>(ks, y, rtol, atol, span, r);
     }
-    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const      // the steady-state test's norm of f(y), group-wide
+    // the steady-state test's norm of f(y), group-wide: for the equilibration phase and for the steady output's (dz_ode.h's STEADY OUTPUT)
+    // alike -- a member template's function exists only where a loop calls it, so EQUILIBRATE or SETTLE alone brings it in
+    __device__ __forceinline__ double drift2(double y, double rtol, double atol) const
     {
         Replica<Net, L> rep(ks);
         rep.fill(r, y);

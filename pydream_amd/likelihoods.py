@@ -11,7 +11,7 @@ from ._kernel_cache import _build_cached, _compiler_version, compile_device_kern
 from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate_indices, _slot_indices
 from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
                           ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_INPUT_KNOTS, ODE_MAX_INPUTS, ODE_MAX_RATE_FACTORS, ODE_MAX_VIEW_COORDINATES,
-                          ODE_WAVE_LIMITS,
+                          ODE_SETTLE_MAX_STEPS, ODE_WAVE_LIMITS,
                           Hill, Input, Monomial, Noise, RateLaw, _checked_constant, _is_int, _is_real)
 
 
@@ -336,6 +336,43 @@ class MassActionODELogLike:
     equilibration shared between the conditions of a point -- every condition equilibrates on its own, also where two of them start
     from the same y0 --; a setting of the phase that is a Monomial; fixed_steps ignores equilibrate, as it ignores events.
 
+    settle: a measurement AT STEADY STATE -- a dose-response point, a binding equilibrium, a blot "after the system has settled", PEtab's
+    time = inf -- is an output time of +inf: t may end in exactly one np.inf (every other entry finite, sorted and >= t0; t = [inf]
+    alone is a pure steady-state read-out with T = 1), and row T-1 of data and sd is that measurement (NaN: not observed, as
+    everywhere).  t_last is the last finite output time, or t0 if there is none; wherever this text says t[-1] -- the events' and the
+    input tables' span, equilibrate's default horizon, the start step's span -- such an object uses t_last.  The phase ahead of the
+    steady row is set with settle=None | True | a mapping with equilibrate's keys, meanings and checks:
+      * rtol, atol: the tolerances of the steady-state test (default: the constructor's rtol and atol);
+      * horizon: the length of time over which the state is to stand still (default t_last - t0 when that is > 0; otherwise, so for
+        t = [inf], the key is required: an experiment without a finite length has no honest default);
+      * max_step (default 1e6 * horizon), max_steps (default 2000, ODE_SETTLE_MAX_STEPS; >= 1).
+    None means True when t ends in inf.  A condition may carry its own "settle": a missing key or None inherits the constructor's, True
+    and a mapping stand for themselves.  The phase cannot be switched off per condition, because t is shared: settle=False with a t
+    that ends in inf is refused, and so is True or a mapping with a t that does not.  The contract (csrc/dz_ode.h's head, STEADY OUTPUT),
+    the same in both builds and every shape:
+      * the finite outputs run exactly as in the object without the steady row.  At t_last the order at one time holds: the output,
+        then the knots that are due, then the events that are due in the order given -- an event at t_last, which has no effect in an
+        object with a finite last output, is "measure, intervene, let it settle".  Inputs are then held at their value at t_last with
+        every drive 0, as ahead of an equilibration;
+      * the phase is equilibrate's loop from that state: start_step(y, rtol, atol, horizon) (not finite or not > 0: -inf), the
+        steady-state test before every attempted step, so also on the state as it arrives, the experiment's step, error test,
+        negativity and rejection rules, no step clipped, h = min(h * factor, max_step) after an accepted step; -inf when the state is
+        not steady after max_steps attempts, a state is not finite, the matrix is singular or a step is not > 0.  The phase applied to a
+        state y therefore gives the bits of the equilibration of a second object started from y0 = y with equilibrate set to the same
+        five numbers;
+      * at the state where the test passed the observables are taken and row T-1's terms added by the code of the finite rows (a
+        Noise's, or the fixed-sd residual); a failure there is -inf.
+    settled_state(X) returns that state, [n, S] or [n, C, S], NaN where the item failed (host build; return_attempts=True: also the
+    phase's attempted steps), the twin of steady_state at the other end.  simulate, batch, batch_conditions, batch(return_steps=True) --
+    which includes the phase's accepted steps --, noise_values, pickling, with_outputs (whose t may end in inf likewise; the phase's
+    settings carry over; with the object's own t every row, the steady one included, has the same bits -- another grid clips other
+    steps, so its rows and the state the phase starts from agree to the integration tolerance and not to the bit, as for every
+    with_outputs), device(), posterior_predictive and the host path of run_dream treat row T-1 as any row.  Every experiment's
+    block grows by the phase's six doubles and the generated network gains SETTLE = true; an object whose t is finite generates the
+    source, the data block and the cache key it always did.  Not supported: more than one steady row per experiment; a steady state
+    between two finite outputs (use two conditions); Newton polishing of the state (conservation laws make the Jacobian singular); a
+    setting of the phase that is a Monomial; fixed_steps ignores the phase, as it ignores events, and gives NaN for t1 = inf.
+
     Products of parameters: a Monomial(exponents, log10_factor) = 10**(log10_factor + sum_i exponents[i] x[i]) may stand
       * as a reaction's rate (kr = KD kf with a fixed kf: Monomial({i: 1}, log10(kf)); a closed cycle: Monomial({0: 1, 1: 1, 2: -1}));
       * as an entry of y0, the constructor's or a condition's: a sampled total amount.  A species has the same Monomial wherever a y0
@@ -484,13 +521,14 @@ class MassActionODELogLike:
     conditions = None       # (an object pickled before the keyword existed)
     events = None           # (likewise)
     equilibrate = None      # (likewise)
+    settle = None           # (likewise: before the steady output existed)
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
     noise = None            # (likewise: before Noise existed)
     inputs = None           # (likewise: before Input existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
-                 equilibrate=None, noise=None, inputs=None):
+                 equilibrate=None, noise=None, inputs=None, settle=None):
         self.n_species, self.lanes_per_point, lim = self._checked_shape(n_species, lanes_per_point, len(reactions))
         noise = self._checked_noise(noise)      # None, or the entries (None | Noise); their number is tested below, once O is known
         if sd is None and noise is not None and all(z is not None for z in noise):
@@ -513,6 +551,7 @@ class MassActionODELogLike:
         self.rtol, self.atol, self.max_steps = float(rtol), float(atol), int(max_steps)
         self.events = events or None            # None, or the checked (time, species, factor, amount) tuples sorted by time
         self.equilibrate = self._checked_equilibrate(equilibrate, "")       # None, or dict(rtol, atol, horizon, max_step, max_steps), every default filled in
+        self.settle = self._checked_settle(settle, "")                      # likewise: None exactly when t is finite throughout
         # None, or a list of dict(y0, data, sd, events[, equilibrate]): checked, the fallbacks filled in -- every condition as the single
         # experiment: its own values, else the constructor's (checked above)
         self.conditions = conditions and [self._checked_condition(cond, "condition %d: " % c, events) for c, cond in enumerate(conditions)]
@@ -593,9 +632,9 @@ class MassActionODELogLike:
         if not 1 <= len(conditions) <= ODE_MAX_CONDITIONS:
             raise ValueError("MassActionODELogLike: 1..%d conditions are supported (got %d)" % (ODE_MAX_CONDITIONS, len(conditions)))
         for c, cond in enumerate(conditions):
-            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate", "inputs", "params"}:
+            if not hasattr(cond, "keys") or set(cond.keys()) - {"y0", "data", "sd", "events", "equilibrate", "inputs", "params", "settle"}:
                 raise ValueError('MassActionODELogLike: condition %d must be a mapping with the keys "y0", "data", "sd", "events", "equilibrate", "inputs", '
-                                 '"params" (each optional)' % c)
+                                 '"params", "settle" (each optional)' % c)
             for key, top in own.items():
                 if cond.get(key) is None and top is None:
                     raise ValueError("MassActionODELogLike: condition %d has no %s, and the constructor's %s is None" % (c, key, key))
@@ -607,8 +646,10 @@ class MassActionODELogLike:
         t = np.asarray(t, dtype=float).reshape(-1)
         if not 1 <= len(t) <= lim["times"]:
             raise ValueError("MassActionODELogLike: 1..%d output times are supported (got %d)" % (lim["times"], len(t)))
-        if not np.isfinite(t0) or not np.all(np.isfinite(t)) or np.any(np.diff(t) < 0) or t[0] < t0:
-            raise ValueError("MassActionODELogLike: output times must be finite, sorted and >= t0 = %r" % t0)
+        fin = t[:-1] if t[-1] == np.inf else t      # (the last may be +inf: a steady output, csrc/dz_ode.h's STEADY OUTPUT)
+        if not np.isfinite(t0) or not np.all(np.isfinite(fin)) or np.any(np.diff(fin) < 0) or t[0] < t0:
+            raise ValueError("MassActionODELogLike: output times must be finite, sorted and >= t0 = %r; only the last may be inf, a steady "
+                             "output (got %r)" % (t0, t.tolist()))
         obs = np.atleast_2d(np.asarray(observables, dtype=float))
         if obs.ndim != 2 or obs.shape[1] != S or not 1 <= len(obs) <= lim["observables"] or not np.all(np.isfinite(obs)):
             raise ValueError("MassActionODELogLike: observables must be an O x %d finite matrix with O = 1..%d" % (S, lim["observables"]))
@@ -623,7 +664,8 @@ class MassActionODELogLike:
         if cond.get("events") is not None:
             events = self._checked_events(cond["events"], who)
         eq = self.equilibrate if cond.get("equilibrate") is None else self._checked_equilibrate(cond["equilibrate"], who)
-        return dict(y0=y0, data=data, sd=sd, events=events, **({"equilibrate": eq} if eq else {}))
+        st = self.settle if cond.get("settle") is None else self._checked_settle(cond["settle"], who)
+        return dict(y0=y0, data=data, sd=sd, events=events, **({"equilibrate": eq} if eq else {}), **({"settle": st} if st else {}))
 
     @staticmethod
     def _checked_scale(scale, O):
@@ -778,19 +820,19 @@ class MassActionODELogLike:
             raise ValueError("MassActionODELogLike: %sinputs must be a sequence of Input objects (got %r)" % (who, inputs))
         if len(inputs) > ODE_MAX_INPUTS:
             raise ValueError("MassActionODELogLike: %sat most %d inputs are supported (got %d)" % (who, ODE_MAX_INPUTS, len(inputs)))
-        t0, t_end = self.t0, float(self.t[-1])
+        t0, t_end = self.t0, self.t_last
         for i, u in enumerate(inputs):
             if not u.species < self.n_species:
                 raise ValueError("MassActionODELogLike: %sinput %d names species %r (an int in 0..%d)" % (who, i, u.species, self.n_species - 1))
             if u.species in [v.species for v in inputs[:i]]:
                 raise ValueError("MassActionODELogLike: %sinput %d: species %d already carries an input: one input per species" % (who, i, u.species))
             if not (u.times[0] <= t0 and u.times[-1] >= t_end):
-                raise ValueError("MassActionODELogLike: %sinput %d: its table must cover t0 = %r .. t[-1] = %r (it covers %r .. %r)"
+                raise ValueError("MassActionODELogLike: %sinput %d: its table must cover t0 = %r .. t[-1] = %r (with a steady output: t_last; it covers %r .. %r)"
                                  % (who, i, t0, t_end, u.times[0], u.times[-1]))
         if like is not None and [(u.species, type(u.gain), u.gain) for u in inputs] != [(u.species, type(u.gain), u.gain) for u in like]:
             raise ValueError("MassActionODELogLike: %sinputs must name the constructor's input species in the same order with the same gains; "
                              "only the tables may differ" % who)
-        knots = sum(len(u.working_knots(t0, t_end)) for u in inputs)
+        knots = sum(len(u.working_knots(t0, t_end)) for u in inputs) + (len(inputs) if self._settles() else 0)
         if knots > ODE_MAX_INPUT_KNOTS:
             raise ValueError("MassActionODELogLike: %sat most %d working knots per experiment are supported, over all its inputs together (got %d)"
                              % (who, ODE_MAX_INPUT_KNOTS, knots))
@@ -814,32 +856,63 @@ class MassActionODELogLike:
                     if ev[1] == u.species:
                         raise ValueError("MassActionODELogLike: %sinput %d: event %d targets the input species %d" % (who, i, n, u.species))
 
+    @property
+    def t_last(self):
+        """The end of the experiment's finite stretch: t[-1], or for an object with a steady output (t[-1] = inf) the last finite output
+        time -- t0 if there is none."""
+        t = self.t
+        return float(t[-1]) if np.isfinite(t[-1]) else float(t[-2]) if len(t) > 1 else float(self.t0)
+
+    def _settles(self):
+        """t ends in inf: the generated network's SETTLE and the phase's six doubles in every experiment's block."""
+        return bool(np.isinf(self.t[-1]))
+
     def _checked_equilibrate(self, eq, who):
         """None (no phase) or the phase's settings, every default filled in: dict(rtol, atol, horizon, max_step, max_steps)."""
         if eq is None or eq is False:
             return None
-        if eq is True:
+        return self._checked_phase(eq, who + "equilibrate", "None, False, True", max(self.t_last - self.t0, 1e-300), ODE_EQUILIBRATE_MAX_STEPS)
+
+    def _checked_settle(self, st, who):
+        """None (t is finite throughout) or the settings of the phase ahead of the steady output, as _checked_equilibrate gives them."""
+        if not self._settles():
+            if st is None or st is False:
+                return None
+            raise ValueError("MassActionODELogLike: %ssettle is given but t does not end in inf: the phase runs ahead of a steady output, "
+                             "t = [..., inf] (got settle = %r)" % (who, st))
+        if st is False:
+            raise ValueError("MassActionODELogLike: %ssettle=False but t ends in inf: the output times are shared by all conditions, so the "
+                             "phase ahead of the steady output cannot be switched off" % who)
+        span = self.t_last - self.t0
+        if span <= 0 and (st is None or st is True or (hasattr(st, "keys") and "horizon" not in st)):
+            raise ValueError('MassActionODELogLike: %ssettle: "horizon" is required when no finite output time lies after t0 (t_last = t0): there is '
+                             "no experiment whose length could say how long the state must stand still" % who)
+        return self._checked_phase(st, who + "settle", "None, True", span, ODE_SETTLE_MAX_STEPS)
+
+    def _checked_phase(self, eq, name, values, horizon, max_steps):
+        """A steady-state phase's settings (equilibrate's or settle's; name: whose), every default filled in."""
+        if eq is True or eq is None:
             eq = {}
         keys = ("rtol", "atol", "horizon", "max_step", "max_steps")
         if not hasattr(eq, "keys") or set(eq.keys()) - set(keys):
-            raise ValueError('MassActionODELogLike: %sequilibrate must be None, False, True or a mapping with the keys "rtol", "atol", "horizon", '
-                             '"max_step", "max_steps" (each optional; got %r)' % (who, eq))
-        out = dict(rtol=eq.get("rtol", self.rtol), atol=eq.get("atol", self.atol), horizon=eq.get("horizon", max(float(self.t[-1]) - self.t0, 1e-300)))
+            raise ValueError('MassActionODELogLike: %s must be %s or a mapping with the keys "rtol", "atol", "horizon", '
+                             '"max_step", "max_steps" (each optional; got %r)' % (name, values, eq))
+        out = dict(rtol=eq.get("rtol", self.rtol), atol=eq.get("atol", self.atol), horizon=eq.get("horizon", horizon))
         for key in ("rtol", "atol", "horizon", "max_step"):
             if key == "max_step":
                 out[key] = eq.get(key, 1e6 * out["horizon"])
             if not _is_real(out[key]) or not out[key] > 0:
-                raise ValueError("MassActionODELogLike: %sequilibrate: %s must be finite and > 0 (got %r)" % (who, key, out[key]))
+                raise ValueError("MassActionODELogLike: %s: %s must be finite and > 0 (got %r)" % (name, key, out[key]))
             out[key] = float(out[key])
-        n = eq.get("max_steps", ODE_EQUILIBRATE_MAX_STEPS)
+        n = eq.get("max_steps", max_steps)
         if not _is_int(n, 1):
-            raise ValueError("MassActionODELogLike: %sequilibrate: max_steps must be an integer >= 1 (got %r)" % (who, n))
+            raise ValueError("MassActionODELogLike: %s: max_steps must be an integer >= 1 (got %r)" % (name, n))
         out["max_steps"] = int(n)
         return out
 
     def _checked_events(self, events, who):
         """The events as a tuple of (time, species, factor, amount), stably sorted by time (events at one time keep the order given)."""
-        S, t0, t = self.n_species, self.t0, self.t
+        S, t0 = self.n_species, self.t0
         if events is None:
             return ()
         try:
@@ -853,9 +926,9 @@ class MassActionODELogLike:
             if not isinstance(event, (tuple, list)) or len(event) != 4:
                 raise ValueError("MassActionODELogLike: %sevent %d must be (time, species, factor, amount)" % (who, e))
             time, species, factor, amount = event
-            if not _is_real(time) or not t0 <= time <= t[-1]:
+            if not _is_real(time) or not t0 <= time <= self.t_last:     # (with a steady output: t_last, the last finite output time)
                 raise ValueError("MassActionODELogLike: %sevent %d: the time must be finite and lie in t0 = %r <= time <= t[-1] = %r (got %r)"
-                                 % (who, e, t0, float(t[-1]), time))
+                                 % (who, e, t0, self.t_last, time))
             if not _is_int(species, 0, S - 1):
                 raise ValueError("MassActionODELogLike: %sevent %d names species %r (an int in 0..%d)" % (who, e, species, S - 1))
             if isinstance(factor, Monomial) or isinstance(amount, Monomial):
@@ -888,17 +961,22 @@ class MassActionODELogLike:
         constructor's own values.  events () and equilibrate None where there are none (so for an object from before the keywords
         existed).  What tells the two kinds of object apart is `self.conditions is not None`: only then the data block has its
         [C, stride] header, the kernels are the item kernels and the host build's results have an axis of conditions."""
-        own = [dict(y0=self.y0, data=self.data, sd=self.sd, events=self.events, equilibrate=self.equilibrate)]
+        own = [dict(y0=self.y0, data=self.data, sd=self.sd, events=self.events, equilibrate=self.equilibrate, settle=self.settle)]
         with_inputs = lambda e: dict(inputs=e.get("inputs") or self.inputs) if self.inputs else {}      # noqa: E731
         with_view = lambda e: dict(params=e.get("params") or {}) if self._has_view() else {}      # noqa: E731
+        with_settle = lambda e: dict(settle=e.get("settle") or self.settle) if self._settles() else {}      # noqa: E731
         return [dict(y0=e["y0"], data=e["data"], sd=e["sd"], events=e.get("events") or (), equilibrate=e.get("equilibrate") or None, **with_inputs(e),
-                     **with_view(e)) for e in (own if self.conditions is None else self.conditions)]
+                     **with_view(e), **with_settle(e)) for e in (own if self.conditions is None else self.conditions)]
 
     def _input_knots(self, inputs):
         """One experiment's working knots as records (time, input, value, slope), sorted by time and at one time by input
-        (csrc/dz_ode.h, INPUTS)."""
-        t0, t_end = self.t0, float(self.t[-1])
-        return sorted((tau, float(i), v, s) for i, u in enumerate(inputs) for tau, v, s in u.working_knots(t0, t_end))
+        (csrc/dz_ode.h, INPUTS).  Ahead of a steady output (csrc/dz_ode.h, STEADY OUTPUT) every input is held: one more record per input
+        behind all others, (t_last, i, u_i(t_last), 0)."""
+        t0, t_end = self.t0, self.t_last
+        knots = sorted((tau, float(i), v, s) for i, u in enumerate(inputs) for tau, v, s in u.working_knots(t0, t_end))
+        if self._settles():
+            knots += [(t_end, float(i), u.working_knots(t_end, t_end)[0][1], 0.0) for i, u in enumerate(inputs)]
+        return knots
 
     def _max_input_knots(self):
         """Kmax: the largest count of working knots over the object's experiments (0: a network without inputs)."""
@@ -920,7 +998,7 @@ class MassActionODELogLike:
         """Some experiment of the object equilibrates: the generated network's EQUILIBRATE and the six doubles at each block's end."""
         return any(eq is not None for eq in self._equilibrate_list())
 
-    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=(), params=None):
+    def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=(), params=None, settle=None):
         seen = np.isfinite(data)
         if self.noise is None:
             C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
@@ -947,6 +1025,8 @@ class MassActionODELogLike:
         if self._equilibrates():                # (csrc/dz_ode.h: on, rtol_ss, atol_ss, horizon, max_step, max_steps_ss at the very end)
             eq = equilibrate
             blk += [[1.0, eq["rtol"], eq["atol"], eq["horizon"], eq["max_step"], float(eq["max_steps"])] if eq else [0.0] * 6]
+        if settle is not None:                  # (csrc/dz_ode.h, STEADY OUTPUT: the phase's six doubles behind the equilibration's, in front of the knots)
+            blk += [[1.0, settle["rtol"], settle["atol"], settle["horizon"], settle["max_step"], float(settle["max_steps"])]]
         if self.inputs:                         # (csrc/dz_ode.h: K_c, then Kmax records padded with zeros, behind everything else)
             knots = self._input_knots(inputs)
             rec = np.zeros((self._max_input_knots(), 4))
@@ -1029,10 +1109,14 @@ class MassActionODELogLike:
         new.t, new.t0, _ = self._checked_times(t, self.t0 if t0 is None else t0, self.observables, self.n_species, lim)
         shape = (len(self.observables), len(new.t))
         new.data, new.sd = np.full(shape, np.nan), np.ones(shape)
+        resettle = lambda st, who: (st or new._checked_settle(None, who)) if new._settles() else None      # noqa: E731  (the phase's settings carry over)
+        new.settle = resettle(self.settle, "")
         new.events = new._checked_events(self.events, "") or None
         new.inputs = new._checked_inputs(self.inputs, "") or None       # (the tables must cover the new span; the working knots follow it)
         if self.conditions is not None:
-            new.conditions = [dict(cond, data=new.data, sd=new.sd, events=new._checked_events(cond["events"], "condition %d: " % c),
+            new.conditions = [dict({k: v for k, v in cond.items() if k != "settle"}, data=new.data, sd=new.sd,
+                                   events=new._checked_events(cond["events"], "condition %d: " % c),
+                                   **({"settle": resettle(cond.get("settle"), "condition %d: " % c)} if new._settles() else {}),
                                    **({"inputs": new._checked_inputs(cond["inputs"], "condition %d: " % c)} if cond.get("inputs") else {}))
                               for c, cond in enumerate(self.conditions)]
         new.path, new._host, new._predict_path = None, None, None
@@ -1060,6 +1144,7 @@ class MassActionODELogLike:
             L.dzode_fixed.restype = I
             L.dzode_constraints.argtypes = [P, I64, I, P]
             L.dzode_equilibrate.argtypes = [P, I64, I, P, P, C.POINTER(C.c_int)]
+            L.dzode_settle.argtypes = [P, I64, I, P, P, C.POINTER(C.c_int)]
             L.dzode_noise.argtypes = [P, I64, I, P]
             L.dzode_exp.argtypes = L.dzode_log.argtypes = [D]
             L.dzode_exp.restype = L.dzode_log.restype = D
@@ -1119,6 +1204,19 @@ class MassActionODELogLike:
         y, st = np.full(lead + (self.n_species,), np.nan), np.zeros(lead, dtype=np.int32)
         self._host_call("dzode_equilibrate", X, len(X), X.shape[1], self.data_block(), y, st)
         return (self._per_point(y), self._per_point(st)) if return_steps else self._per_point(y)
+
+    def settled_state(self, X, return_attempts=False):
+        """The state the steady output is measured at, from the host build: [n, S], with conditions [n, C, S] -- the state at which the
+        phase's steady-state test passed, after everything due at t_last (csrc/dz_ode.h, STEADY OUTPUT); NaN where the item failed.
+        return_attempts: also the ATTEMPTED steps of the phase, [n] or [n, C] -- what settle's max_steps counts.  The twin of
+        steady_state at the experiment's other end; only for an object whose t ends in inf."""
+        if not self._settles():
+            raise ValueError("MassActionODELogLike: settled_state needs an object with a steady output, t = [..., inf]")
+        X = self._rows(X)
+        lead = (len(X), len(self._experiments()))
+        y, st = np.full(lead + (self.n_species,), np.nan), np.zeros(lead, dtype=np.int32)
+        self._host_call("dzode_settle", X, len(X), X.shape[1], self.data_block(), y, st)
+        return (self._per_point(y), self._per_point(st)) if return_attempts else self._per_point(y)
 
     def constraint_terms(self, X):
         """g(x) = sum over the constraints of norm(loc, sd).logpdf(monomial) for the rows of X, from the host build: what the single

@@ -11,6 +11,7 @@
 
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
                                   [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise] [--input] [--view]
+                                  [--settle [--t-big T | --search-only] [--before CODE_OBJECT]]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -46,6 +47,20 @@ mappings are explicit identities {i: i} for every coordinate read, so the kernel
 same, against the same object without "params", on the same points; alternately, the median of 7 rounds of 10 calls each and the
 rounds' spread; proposals/s for both, their registers, scratch and LDS from the code objects' notes, and the two launches' values
 compared bit for bit (the host build's on the first 64 points).  Kernel only.
+
+--settle: a steady output (MassActionODELogLike(t=[..., inf]), csrc/dz_ode.h, STEADY OUTPUT) against what a user did before t could
+end in inf -- --network mm | enzyme13 | chain17 | chain33 of tests/ode_settle_networks.py (1, 16, 32 and 64 lanes per point) with its
+last output at inf against the same network, data and points with a FINITE last output at t_last + t_big; alternately, the median of 7
+rounds of 10 calls each and the rounds' spread; proposals/s and the host build's steps per point for both, their registers, scratch and
+LDS from the code objects' notes, the phase's attempted steps, and how far the late output lies from the steady row.  t_big is chosen
+with the reference (scipy's Radau, tests/ode_reference.py): the first power of ten at which Radau's state from the network's y0 passes
+numpy's restatement of the steady-state test (the object's horizon and tolerances) at EVERY one of the timed points -- one Radau run per
+point on the host (carried on from power to power, ended at the first that passes; about a second per point), before anything is timed,
+over DREAMZS_HOST_WORKERS processes (default 16); --search-only does that search alone, needs no GPU and prints t_big and how many
+points first rest at each power of ten; --t-big T skips the search and takes T, the value such a run found on the same points.
+Kernel only.  The same run times the network WITHOUT the phase (t = [.., t_last]) in the same rounds, and with --before CODE_OBJECT also the
+code object that another checkout -- the commit before the phase existed -- built for that network (MassActionODELogLike(path=...)):
+networks without the phase generate the source they always did, so the two should take the same time within the rounds' spread.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -336,6 +351,86 @@ def view_rate(N, k, name, rounds=7, reps=10):
     return out
 
 
+def _first_rest(args):
+    """(S, reactions, y0, k, horizon, rtol, atol, t_last) -> the first exponent p at which Radau's state at t_last + 10**p passes numpy's
+    drift test; 99 if none up to 10**9.  One Radau run per point, carried on from power to power and ended at the first that passes
+    (ode_settle_networks.radau_at: ode_reference.radau with a numpy Jacobian)."""
+    from tests import ode_settle_networks as SN
+    S, rx, y0, k, horizon, rtol, atol, t_last = args
+    y, now = np.asarray(y0, dtype=float), 0.0
+    for p in range(0, 10):
+        y, now = SN.radau_at(S, rx, k, y, [t_last + 10.0 ** p], t0=now)[0], t_last + 10.0 ** p
+        if SN.drift(S, rx, k, y, horizon, rtol, atol) <= 1.0:
+            return p
+    return 99
+
+
+def settle_rate(N, k, name, t_big=None, rounds=7, reps=10, search_only=False, before=None):
+    """The last output at inf against a finite last output at t_last + t_big: see the head"""
+    import multiprocessing
+    from pydream_amd.likelihoods import MassActionODELogLike
+    from tests import ode_reference as R
+    from tests import ode_settle_networks as SN
+    from tests.ode_support import notes
+    like = SN.single(name)
+    S, rx, y0, _, _, nominal, _, _ = SN.network(name)
+    st, n, t_last = like.settle, N * k, like.t_last
+    X = box_points(nominal, 1.0, n)
+    workers = int(os.environ.get("DREAMZS_HOST_WORKERS", "16"))
+    searched = t_big is None
+    if searched:                                                         # (the workers are forked before this process opens the device)
+        with multiprocessing.get_context("fork").Pool(workers) as pool:
+            exps = pool.map(_first_rest, [(S, rx, y0, R.rate_constants(rx, x, "log10"), st["horizon"], st["rtol"], st["atol"], t_last) for x in X], chunksize=8)
+        assert max(exps) < 99, "Radau did not come to rest at some point"
+        t_big = 10.0 ** max(exps)
+        if search_only:                                                  # (no device is opened: the search alone, for a later run's --t-big)
+            out = dict(network=name, lanes=like.lanes_per_point, chains=N, tries=k, points=n, t_last=t_last, t_big=t_big,
+                       points_first_at_rest_by_power_of_ten=np.bincount(exps).tolist())
+            print(json.dumps(out), flush=True)
+            return out
+    late = MassActionODELogLike(S, rx, like.y0, np.r_[like.t[:-1], t_last + t_big], like.observables, like.data, like.sd, lanes_per_point=like.lanes_per_point)
+    objs = dict(late_output=late, steady_output=like)
+    # the same network without the phase (t = [.., t_last]): this checkout's kernel and, with --before, the code object another checkout
+    # (the commit before the phase existed) built from the same generated source
+    objs["without_phase"] = SN.finite_twin(like)
+    if before is not None:
+        objs["without_phase_before"] = SN.finite_twin(like, path=before)
+    for obj in objs.values():
+        obj.host_library()
+    with multiprocessing.get_context("fork").Pool(workers) as pool:
+        hosts = {key: pool.map(_host_part, [(obj, part) for part in np.array_split(X, workers)]) for key, obj in objs.items()}
+        sims = {key: np.concatenate(pool.map(_host_rows, [(obj, part) for part in np.array_split(X[:256], workers)])) for key, obj in objs.items()}
+    engines = {key: engine_for(obj, N, k, nominal, 1.0) for key, obj in objs.items()}
+    last, t = timed({key: (lambda eng=eng: eng.eval_logp(X)[1]) for key, eng in engines.items()}, rounds, reps)
+    out = dict(network=name, lanes=like.lanes_per_point, species=S, chains=N, tries=k, points=n, t_last=t_last, t_big=t_big,
+               t_big_from="Radau's state passes numpy's drift test at every point" if searched else "--t-big", settle=st)
+    for key, lk in last.items():
+        host, steps = np.concatenate([p[0] for p in hosts[key]]), np.concatenate([p[1] for p in hosts[key]])
+        assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
+        us = float(np.median(t[key]))
+        out[key] = dict(steps_median=float(np.median(steps)), steps_max=int(steps.max()), failed_points=int(np.sum(lk == -np.inf)), us_per_launch=round(us, 1),
+                        us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6),
+                        code_object=notes(objs[key].code_object()))
+    both = np.all(np.isfinite(sims["late_output"][:, -1]), axis=1) & np.all(np.isfinite(sims["steady_output"][:, -1]), axis=1)
+    gap = np.abs(sims["late_output"][both, -1] - sims["steady_output"][both, -1]) / (st["atol"] + st["rtol"] * np.abs(sims["steady_output"][both, -1]))
+    out["last_rows_apart_in_units_of_the_tolerance_max_over_256_points"] = round(float(gap.max()), 3)
+    if before is not None:
+        assert last["without_phase"].tobytes() == last["without_phase_before"].tobytes(), "the two code objects of the phase-less network differ in their values"
+        a, b = t["without_phase"], t["without_phase_before"]
+        out["without_phase_after_over_before"] = round(float(np.median(a)) / float(np.median(b)), 4)
+        out["without_phase_ratio_over_the_rounds_spread"] = [round(min(a) / max(b), 4), round(max(a) / min(b), 4)]
+    out["steady_over_late"] = round(out["steady_output"]["us_per_launch"] / out["late_output"]["us_per_launch"], 4)
+    lo, hi = (min(t["steady_output"]) / max(t["late_output"]), max(t["steady_output"]) / min(t["late_output"]))
+    out["ratio_over_the_rounds_spread"] = [round(lo, 4), round(hi, 4)]
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def _host_rows(args):
+    like, part = args
+    return like.simulate(part)
+
+
 def _host_part(args):
     like, part = args
     return like.batch(part, return_steps=True)
@@ -425,7 +520,7 @@ def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--network", "--lanes", "--conditions", "--events"):
+    for flag in ("--network", "--lanes", "--conditions", "--events", "--t-big", "--before"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
@@ -441,6 +536,8 @@ if __name__ == "__main__":
         input_rate(*nums, name)
     elif "--view" in argv:
         view_rate(*nums, name)
+    elif "--settle" in argv:
+        settle_rate(*nums, name, float(opt["--t-big"]) if "--t-big" in opt else None, search_only="--search-only" in argv, before=opt.get("--before"))
     elif "--equilibrate" in argv:
         assert "--conditions" in opt and "--events" not in opt, "--equilibrate goes with --conditions C (and without --events)"
         events_rate(*nums, name, lanes, int(opt["--conditions"]), 0, equilibrate=True)
