@@ -100,6 +100,20 @@ int dz_set_gamma_probs(dz_engine* e, const double* p, int32_t ngamma);          
 /* per-dimension priors evaluated on the device (parameters.py:37-47, 62-63):
  * kind 0 flat, 1 scipy.stats.norm(loc=a, scale=b), 2 scipy.stats.uniform(loc=a, scale=b) */
 int dz_set_prior(dz_engine* e, const int32_t* kind, const double* a, const double* b);
+/* ... and eleven more scipy families, each in scipy's parametrisation (loc = a, scale = b > 0, shapes s1, s2; d entries per array, the
+ * shapes ignored where the kind has none):
+ *     3 laplace   4 cauchy   5 t (s1 = nu)   6 lognorm (s1 = s)   7 gamma (s1 = k; expon is k = 1)   8 beta (s1 = alpha, s2 = beta)
+ *     9 halfnorm   10 halfcauchy   11 truncnorm (s1 = lo < s2 = hi, either may be infinite)   12 loguniform (0 < s1 = lo < s2 = hi)
+ *     13 invgamma (s1 = k)
+ * The arithmetic of every kind is stated once, in csrc/dz_prior_ext.h.  Refused, with the dimension named: a kind outside 0..13, a scale
+ * that is not finite or not > 0 under a non-flat kind, a shape outside its domain, a truncated mass that is not > 0.  When every kind is
+ * <= 2 the call is dz_set_prior(kind, a, b).  Otherwise the priors are added by a kernel of the multi-kernel path (k_prior_ext), which
+ * every generation then takes, whatever the likelihood; dz_eval_logp takes the same route.  dz_set_prior replaces what this call set. */
+int dz_set_prior_ext(dz_engine* e, const int32_t* kind, const double* a, const double* b, const double* s1, const double* s2);
+/* The host twin of that kernel: out[i] = the log prior of row i of X [n, d], added in the kernel's order from the same functions -- the
+ * device's bits.  Needs no engine and no GPU. */
+int dz_prior_ext_host(const int32_t* kind, const double* a, const double* b, const double* s1, const double* s2, int32_t d, const double* X,
+                      int64_t n, double* out);
 /* built-in device likelihoods ("batched device callback"):
  * MVN, examples/ndim_gaussian/dream_ex_ndim_gaussian.py:49-52: kind 0 = precision matrix
  * invC [d,d]; kind 1 = upper-triangular U with invC = U^T U.  logp = log_F - Q/2. */

@@ -35,7 +35,7 @@ XCHG_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 # every symbol include/dreamzs.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "dz_version", "dz_last_error", "dz_device_count", "dz_create", "dz_destroy", "dz_set_bounds", "dz_set_gamma_table",
-    "dz_set_history", "dz_set_state", "dz_set_cr_probs", "dz_set_gamma_probs", "dz_set_prior", "dz_set_likelihood_mvn",
+    "dz_set_history", "dz_set_state", "dz_set_cr_probs", "dz_set_gamma_probs", "dz_set_prior", "dz_set_prior_ext", "dz_prior_ext_host", "dz_set_likelihood_mvn",
     "dz_set_likelihood_mixture", "dz_set_likelihood_host", "dz_set_likelihood_module", "dz_set_likelihood_items", "dz_set_output_module", "dz_eval_outputs", "dz_hip_library", "dz_comm_library", "dz_comm_unique_id", "dz_comm_init_rccl", "dz_comm_count", "dz_comm_barrier", "dz_set_exchange", "dz_peer_export", "dz_peer_attach", "dz_peer_detach", "dz_exchange_stats", "dz_exchange_bytes", "dz_set_temperatures", "dz_get_swaps",
     "dz_step", "dz_continue_run", "dz_step_range", "dz_set_chain_state", "dz_get_chain_state", "dz_get_chain_probs", "dz_sync", "dz_trace_reset", "dz_generation", "dz_redraw_rounds", "dz_last_kernel_variant", "dz_last_kernel_tries", "dz_get_state", "dz_get_trace", "dz_get_trace_chains", "dz_trace_download_begin", "dz_trace_download_wait", "dz_host_register", "dz_host_unregister", "dz_get_history", "dz_get_history_range", "dz_history_checksum",
     "dz_get_cr_state", "dz_get_gamma_state", "dz_get_rhat", "dz_get_chain_moments", "dz_eval_logp", "dz_debug_propose",
@@ -81,6 +81,8 @@ def load_library():
     L.dz_set_cr_probs.argtypes = [V, V, C.c_int32]
     L.dz_set_gamma_probs.argtypes = [V, V, C.c_int32]
     L.dz_set_prior.argtypes = [V, V, V, V]
+    L.dz_set_prior_ext.argtypes = [V, V, V, V, V, V]
+    L.dz_prior_ext_host.argtypes = [V, V, V, V, V, C.c_int32, V, C.c_int64, V]
     L.dz_set_likelihood_mvn.argtypes = [V, V, V, C.c_int32, C.c_double]
     L.dz_set_likelihood_mixture.argtypes = [V, C.c_int32, V, V]
     L.dz_set_likelihood_host.argtypes = [V, LOGP_CB, V]
@@ -175,6 +177,22 @@ def history_checksum_host(Z):
         return int(np.sum(z, dtype=np.uint64))
 
 
+def prior_ext_host(kind, a, b, s1, s2, X):
+    """The log priors of the rows of X [n, d] under the extended device priors (include/dreamzs.h dz_prior_ext_host): the host twin of
+    k_prior_ext, the device's bits; needs no GPU."""
+    kind = np.ascontiguousarray(kind, dtype=np.int32)
+    a, b, s1, s2 = (_f64(v).reshape(-1) for v in (a, b, s1, s2))
+    d = len(kind)
+    if not all(len(v) == d for v in (a, b, s1, s2)):
+        raise ValueError("kind, a, b, s1 and s2 must have one entry per dimension")
+    X = _f64(X).reshape(-1, d)
+    out = np.zeros(len(X))
+    L = load_library()
+    if L.dz_prior_ext_host(_p(kind), _p(a), _p(b), _p(s1), _p(s2), d, _p(X), len(X), _p(out)) != 0:
+        raise DreamZSError(L.dz_last_error().decode())
+    return out
+
+
 PROFILE_CLASSES = {"propose": 0, "logp": 1, "accept": 2, "adapt": 3, "exchange": 4, "generations": 5, "empty": 6}
 
 
@@ -243,6 +261,14 @@ class Engine:
         kind = np.ascontiguousarray(kind, dtype=np.int32)
         a, b = _f64(a), _f64(b)
         self._chk(self.L.dz_set_prior(self.h, _p(kind), _p(a), _p(b)))
+
+    def set_prior_ext(self, kind, a, b, s1, s2):
+        """kinds 0..13 in scipy's parametrisation (include/dreamzs.h dz_set_prior_ext); every kind <= 2: the same as set_prior"""
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        a, b, s1, s2 = _f64(a), _f64(b), _f64(s1), _f64(s2)
+        if not all(len(v) == self.d for v in (kind, a, b, s1, s2)):
+            raise ValueError("kind, a, b, s1 and s2 must have one entry per dimension")
+        self._chk(self.L.dz_set_prior_ext(self.h, _p(kind), _p(a), _p(b), _p(s1), _p(s2)))
 
     def set_likelihood_mvn(self, mu, M, kind=0, log_F=0.0):
         mu, M = _f64(mu), _f64(M)

@@ -105,11 +105,13 @@ def _signature(step, kwargs, nchains, likelihood, engine):
     """everything a continued run must have in common with the run whose engine it takes over"""
     dev_prior = step.model.device_prior()
     pri = None if dev_prior is None else tuple(np.asarray(a).tobytes() for a in dev_prior)
+    ext_prior = step.model.device_prior_ext() if dev_prior is None else None
+    ext = None if ext_prior is None else tuple(np.asarray(a).tobytes() for a in ext_prior)
     return (nchains, step.total_var_dimension, int(step.multitry), len(step.DEpairs), int(step.nCR), int(step.ngamma), int(step.history_thin),
             bool(step.adapt_crossover), bool(step.adapt_gamma), bool(step.boundaries), float(step.lamb), float(step.zeta), float(step.snooker),
             float(step.p_gamma_unity), int(kwargs.get('device', 0)), int(kwargs.get('history_lag', 0)), int(kwargs.get('adapt_lag', 0)), bool(getattr(step, 'parallel', False)),
             np.asarray(step.mins).tobytes() if step.boundaries else None, np.asarray(step.maxs).tobytes() if step.boundaries else None,
-            np.asarray(step.gamma_arr).tobytes(), pri, id(likelihood))
+            np.asarray(step.gamma_arr).tobytes(), pri, ext, id(likelihood))
 
 
 def _file_stamps(prefix):
@@ -440,12 +442,18 @@ def _setup_mp_dream_pool(nchains, niterations, step_instance, start_pt=None, mp_
         eng.set_gamma_probs(np.asarray(step_instance.gamma_probabilities, dtype=float))
 
     model = step_instance.model
-    dev_prior = model.device_prior() if step_instance.variables is model.sampled_parameters or list(step_instance.variables) == list(model.sampled_parameters) else None
+    same_variables = step_instance.variables is model.sampled_parameters or list(step_instance.variables) == list(model.sampled_parameters)
+    dev_prior = model.device_prior() if same_variables else None
     if dev_prior is not None and live is None:
         eng.set_prior(*dev_prior)
     like = model.likelihood
+    # a prior beyond flat / normal / uniform that has a device form (parameters.device_prior_ext) beside a device likelihood: both on the device.
+    # (A Python-callable likelihood keeps the host evaluation of prior and likelihood.)
+    ext_prior = model.device_prior_ext() if dev_prior is None and same_variables and hasattr(like, "_dz_apply") else None
+    if ext_prior is not None and live is None:
+        eng.set_prior_ext(*ext_prior)
     host_eval = None
-    if hasattr(like, "_dz_apply") and dev_prior is not None:
+    if hasattr(like, "_dz_apply") and (dev_prior is not None or ext_prior is not None):
         like._dz_apply(eng)                           # likelihood AND priors on the device (also on a continued engine: the object may have been
                                                       # changed in place since the run before -- cheap next to the history upload that is saved)
     else:

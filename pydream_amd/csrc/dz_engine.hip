@@ -203,6 +203,8 @@ struct dz_engine {
     // Dream.py:281-289: a proposal set whose tries are all impossible is drawn again (redo_possible / one_generation)
     uint8_t* d_redo = nullptr; int32_t* d_redo_list = nullptr; uint8_t* h_redo = nullptr; int32_t* h_redo_list = nullptr;     // (host side: page-locked)
     std::vector<int32_t> h_pkind; std::vector<double> h_pa, h_pb, h_mins, h_maxs;     // host copies: is the uniform priors' support covered by the hard boundaries?
+    // dz_set_prior_ext with a kind above 2: the table k_prior_ext reads (its own kernel argument; Params does not know it) and the host copy of the shapes
+    bool prior_ext = false; dz::PriorExtTable xt = {}; int32_t* d_xkind = nullptr; double* d_xtab = nullptr; std::vector<double> h_ps1, h_ps2;
     hipStream_t copy_stream = nullptr; hipEvent_t copy_ev[8] = {nullptr};   // dz_trace_download_begin / _wait: trace rows leave while later generations run
     int64_t redraw_rounds = 0;      // redraw launches so far (dz_redraw_rounds)
     double *d_own_cr = nullptr, *d_own_g = nullptr; std::vector<char> own_init;      // per-instance probabilities of single-chain stepping (Params::own_cr)
@@ -443,6 +445,7 @@ int eval_logp(dz_engine* e, const double* pts, int n, double* prior, double* lik
     }
     if (P.prior_only) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_only<NCH>, g3(P.prior), b3(P.prior), 0, st, e->p, pts, n, prior));
     if (P.prior_add) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_add<NCH>, g3(P.prior), b3(P.prior), 0, st, e->p, pts, n, prior, like));
+    if (P.prior_ext) NCH_DISPATCH(e, hipLaunchKernelGGL(dz::k_prior_ext<NCH>, g3(P.ext), b3(P.ext), 0, st, e->xt, pts, n, e->p.d, e->p.ld, prior, like, P.ext_fix_like ? 1 : 0));
     return launch_check("logp kernel");
 }
 
@@ -688,8 +691,9 @@ int adapt_generation(dz_engine* e, uint32_t g, int gc0, int ngc, bool fused = fa
     return launch_check("adaptation kernels");
 }
 
-// Can every try of a multi-try proposal set be impossible (log density -inf or nan)?  Not with the built-in likelihoods under flat or
-// normal priors; yes with a host likelihood, and with a uniform prior unless hard boundaries keep every proposal inside its support.
+// Can every try of a multi-try proposal set be impossible (log density -inf or nan)?  Not with the built-in likelihoods under priors of
+// unbounded support; yes with a host likelihood, and with a prior of bounded support unless hard boundaries keep every proposal inside it
+// and away from an end where the log density is not finite (dz::covered, dz_prior_ext.h; for a uniform prior: inside its support).
 // Those configurations take the multi-kernel path, which checks after the proposal set's evaluation and draws again (Dream.py:281-289).
 bool redo_possible(const dz_engine* e)
 {
@@ -697,10 +701,10 @@ bool redo_possible(const dz_engine* e)
     if (p.k <= 1) return false;
     if (e->lk == LK_HOST) return true;
     if (e->lk == LK_MODULE && !e->lk_finite) return true;      // (a user's density may be -inf anywhere unless the caller promises otherwise: DZ_LIKE_ALWAYS_FINITE)
+    const double inf = __builtin_huge_val();
     for (size_t j = 0; j < e->h_pkind.size(); ++j) {
-        if (e->h_pkind[j] != 2) continue;
-        const bool covered = p.hard && j < e->h_mins.size() && e->h_mins[j] >= e->h_pa[j] && e->h_maxs[j] <= e->h_pa[j] + e->h_pb[j];
-        if (!covered) return true;
+        const bool have = j < e->h_mins.size(), shapes = e->prior_ext && j < e->h_ps1.size();
+        if (!dz::covered(e->h_pkind[j], e->h_pa[j], e->h_pb[j], shapes ? e->h_ps1[j] : 0.0, shapes ? e->h_ps2[j] : 0.0, p.hard && have, have ? e->h_mins[j] : -inf, have ? e->h_maxs[j] : inf)) return true;
     }
     return false;
 }
@@ -883,6 +887,7 @@ dz::MultiShape multi_shape(const dz_engine* e)
     s.adapt = e->adapt; s.tempering = e->tempering; s.world = e->world; s.thin = p.thin; s.burnin = p.burnin; s.history_lag = e->c.history_lag; s.adapt_lag = e->c.adapt_lag;
     s.adapt_groups = e->adapt_groups; s.trace = e->c.trace_capacity != 0;
     s.propose_split = e->propose_split; s.q_defer = e->q_defer; s.logp_gemm = e->logp_gemm;
+    s.prior_ext = e->prior_ext;
     return s;
 }
 dz::MegaShape mega_shape(const dz_engine* e)
@@ -897,6 +902,7 @@ dz::MegaShape mega_shape(const dz_engine* e)
     s.ad_multi = e->ad_multi; s.ad_R1 = e->ad_R1; s.ad_nbp = e->ad_nbp; s.adapt_lag = e->c.adapt_lag; s.adapt_fused = e->adapt_fused; s.adapt_groups = e->adapt_groups;
     s.tempering = e->tempering; s.world = e->world;
     s.mega = e->mega; s.mega_d2 = e->mega_d2; s.mega_kc = e->mega_kc; s.mega_redo = e->mega_redo_on;
+    s.prior_ext = e->prior_ext;
     return s;
 }
 // dz_step: the choice for its generations (nothing the selection reads changes inside a dz_step), and the two Params fields that follow from it
@@ -1399,6 +1405,57 @@ int dz_set_prior(dz_engine* e, const int32_t* kind, const double* a, const doubl
     DZCK(launch_check("k_prior_consts"));
     e->p.have_prior = any ? 1 : 0;
     e->h_pkind.assign(kind, kind + d); e->h_pa.assign(a, a + d); e->h_pb.assign(b, b + d);
+    e->prior_ext = false;
+    return 0;
+}
+
+// Every dimension's row of the extended priors' table (dz_prior_ext.h), or the first dimension that is refused
+static int prior_ext_rows(const int32_t* kind, const double* a, const double* b, const double* s1, const double* s2, int d, std::vector<dz::PriorExtRow>& rows)
+{
+    rows.assign((size_t)d, dz::PriorExtRow{0.0, 0.0, 0.0, 0.0, 0.0});
+    for (int j = 0; j < d; ++j) {
+        const bool shaped = kind[j] > 2;
+        if (const char* why = dz::prior_ext_row(kind[j], a[j], b[j], shaped && s1 ? s1[j] : 0.0, shaped && s2 ? s2[j] : 0.0, rows[j]))
+            return fail("dz_set_prior_ext: dimension " + std::to_string(j) + ": " + why);
+    }
+    return 0;
+}
+
+int dz_set_prior_ext(dz_engine* e, const int32_t* kind, const double* a, const double* b, const double* s1, const double* s2)
+{
+    HIPCK(hipSetDevice(e->c.device));
+    const int d = e->p.d, ld = e->p.ld;
+    std::vector<dz::PriorExtRow> rows;
+    DZCK(prior_ext_rows(kind, a, b, s1, s2, d, rows));
+    bool ext = false;
+    for (int j = 0; j < d; ++j) ext = ext || kind[j] > 2;
+    if (!ext) return dz_set_prior(e, kind, a, b);      // the same device constants, the same kernels, the same bits
+    if (!e->d_xkind) { DZCK(ealloc(e, &e->d_xkind, (size_t)ld)); DZCK(ealloc(e, &e->d_xtab, (size_t)5 * ld)); }
+    std::vector<int32_t> hk((size_t)ld, 0);
+    std::vector<double> tab((size_t)5 * ld, 0.0);
+    for (int j = 0; j < d; ++j) {
+        hk[j] = kind[j];
+        tab[j] = rows[j].a; tab[(size_t)ld + j] = rows[j].rb; tab[(size_t)2 * ld + j] = rows[j].c; tab[(size_t)3 * ld + j] = rows[j].p1; tab[(size_t)4 * ld + j] = rows[j].p2;
+    }
+    DZCK(sync_all(e));
+    HIPCK(hipMemcpy(e->d_xkind, hk.data(), sizeof(int32_t) * ld, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(e->d_xtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    e->xt = dz::PriorExtTable{e->d_xkind, e->d_xtab, e->d_xtab + ld, e->d_xtab + (size_t)2 * ld, e->d_xtab + (size_t)3 * ld, e->d_xtab + (size_t)4 * ld};
+    // the built-in kernels run without a prior of their own (they write a zero prior); k_prior_ext adds every dimension's
+    e->p.have_prior = 0; e->p.prior_nonormal = 1;
+    e->h_pkind.assign(kind, kind + d); e->h_pa.assign(a, a + d); e->h_pb.assign(b, b + d);
+    e->h_ps1.assign((size_t)d, 0.0); e->h_ps2.assign((size_t)d, 0.0);
+    for (int j = 0; j < d; ++j) { if (s1) e->h_ps1[j] = s1[j]; if (s2) e->h_ps2[j] = s2[j]; }
+    e->prior_ext = true;
+    return 0;
+}
+
+int dz_prior_ext_host(const int32_t* kind, const double* a, const double* b, const double* s1, const double* s2, int32_t d, const double* X, int64_t n, double* out)
+{
+    if (d < 1 || n < 0) return fail("dz_prior_ext_host: d >= 1 and n >= 0");
+    std::vector<dz::PriorExtRow> rows;
+    DZCK(prior_ext_rows(kind, a, b, s1, s2, d, rows));
+    for (int64_t i = 0; i < n; ++i) out[i] = dz::prior_ext_point_host(kind, rows.data(), d, X + (size_t)i * d);
     return 0;
 }
 

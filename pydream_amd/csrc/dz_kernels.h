@@ -10,6 +10,7 @@
 #include "dz_device.h"
 #include "dz_mega_select.h"      // MAXK, tri_row_offset and the persistent kernels' LDS layout: shared with the host-side selection
 #include "dz_multi_select.h"     // ... and the LDS carvings of k_logp_mvn_lds and k_accept_propose
+#include "dz_prior_ext.h"        // the priors beyond flat / normal / uniform: one dimension's term, shared with its host twin
 
 namespace dz {
 
@@ -1725,6 +1726,32 @@ __global__ __launch_bounds__(256) void k_prior_add(Params p, const double* __res
     }
     const double prior = prior_of_point<NCH>(p, x, lane);
     if (lane == 0) { prior_io[pt] = nan_to_ninf(p.have_prior ? prior_io[pt] + prior : prior_io[pt]); like_io[pt] = nan_to_ninf(like_io[pt]); }
+}
+
+// Extended priors (dz_set_prior_ext, dz_prior_ext.h): every dimension's prior, the kinds 0..2 included, from a table of its own -- Params does not
+// know it, and the built-in kernels, which then run with have_prior = 0, have left prior_io[pt] = 0 (after a host callback: what the callback returned).
+// A wave per point, two dimensions per lane in prior_of_point's order.  fix_like: map like_io's NaN too, where k_prior_add would have (LogpPlan::prior_add).
+struct PriorExtTable { const int32_t* kind; const double *a, *rb, *c, *p1, *p2; };
+template <int NCH>
+__global__ __launch_bounds__(256) void k_prior_ext(PriorExtTable t, const double* __restrict__ pts, int npts, int d, int ld, double* prior_io, double* like_io, int fix_like)
+{
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pt = blockIdx.x * 4 + wv;
+    if (pt >= npts) return;
+    double acc = 0.0;
+#pragma unroll 1
+    for (int it = 0; it < NCH; ++it) {
+        const int jj = 128 * it + 2 * lane;
+        double x[2] = {0.0, 0.0};
+        if (jj < ld) { const double2 v = *reinterpret_cast<const double2*>(pts + (size_t)pt * ld + jj); x[0] = v.x; x[1] = v.y; }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int j = jj + s;
+            if (j < d) acc = acc + prior_ext_term(t.kind[j], x[s], t.a[j], t.rb[j], t.c[j], t.p1[j], t.p2[j]);
+        }
+    }
+    const double prior = wave_bfly(acc);
+    if (lane == 0) { prior_io[pt] = nan_to_ninf(prior_io[pt] + prior); if (fix_like) like_io[pt] = nan_to_ninf(like_io[pt]); }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -98,6 +98,7 @@ struct MegaShape {
     bool redo_possible;                      // a whole proposal set can be impossible (redraw rounds, Dream.py:281-289)
     bool ad_multi; int ad_R1, ad_nbp, adapt_lag; bool adapt_fused, adapt_groups, tempering; int world;
     bool mega; int mega_d2; bool mega_kc, mega_redo;      // the path switches (read_switches): DZ_MEGA, DZ_MEGA_D2, DZ_MEGA_KC, DZ_MEGA_REDO
+    bool prior_ext = false;                               // dz_set_prior_ext with a kind above 2: no persistent kernel evaluates those (the multi-kernel path's k_prior_ext does)
 };
 enum MegaFamily { MEGA_NONE = 0, MEGA_CLASSIC, MEGA_W4, MEGA_D2, MEGA_MIX, MEGA_USER };
 struct MegaChoice {
@@ -272,6 +273,7 @@ inline MegaChoice mega_choose(const MegaShape& s)
     } else if (s.mega && s.lk == MEGA_LK_MVN && s.ld <= 128 && tries_ok && (!s.tri || s.mtp) && mega_fits(mega_lds(s, s.tri, false, c.ch, c.pb_lds))) {
         c.family = (c.ch == 4 && c.wpc == 4 && !c.pb && c.xlds && s.k >= 3 && s.k <= 6) ? MEGA_W4 : MEGA_CLASSIC;
     }
+    if (s.prior_ext) c.family = MEGA_NONE;
     c.burnin = c.family == MEGA_NONE ? 0 : mega_burnin_mode(s, c);
     return c;
 }

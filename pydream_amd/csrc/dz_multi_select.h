@@ -45,17 +45,18 @@ struct MultiShape {
     bool redo_possible;                                      // a whole proposal set can be impossible (redraw rounds, Dream.py:281-289)
     bool adapt, tempering; int world, thin, burnin, history_lag, adapt_lag; bool adapt_groups, trace;
     int propose_split; bool q_defer, logp_gemm;              // DZ_PROPOSE_SPLIT (0: by shape), DZ_QFIN, DZ_LOGP_GEMM
+    bool prior_ext = false;                                  // dz_set_prior_ext with a kind above 2: have_prior is false, the built-in kernels write a zero prior, k_prior_ext adds every dimension's
 };
 
 // The kernels of this path and the block size each is compiled for (__launch_bounds__; 1024 where it has none).
 enum MultiKernel { MK_DRAWS, MK_PROPOSE, MK_PROPOSE_STREAM, MK_ACCEPT, MK_ACCEPT_PROPOSE, MK_LOGP_LDS, MK_LOGP_MFMA, MK_LOGP_TILED, MK_LOGP_GEMM, MK_LOGP_MIX, MK_Q_FINISH,
-                   MK_PRIOR_ONLY, MK_PRIOR_ADD, MK_SUM_ITEMS, MK_MODULE, MK_REDO_FLAGS, MK_GATHER_SETS, MK_SCATTER_LOGP, MK_COUNT };
+                   MK_PRIOR_ONLY, MK_PRIOR_ADD, MK_SUM_ITEMS, MK_MODULE, MK_REDO_FLAGS, MK_GATHER_SETS, MK_SCATTER_LOGP, MK_PRIOR_EXT, MK_COUNT };
 inline int multi_max_threads(MultiKernel kern, int nch)
 {
     switch (kern) {
         case MK_PROPOSE: return nch >= 4 ? 256 : 1024;
         case MK_LOGP_LDS: return 512;
-        case MK_PROPOSE_STREAM: case MK_LOGP_MFMA: case MK_LOGP_TILED: case MK_LOGP_GEMM: case MK_LOGP_MIX: case MK_PRIOR_ONLY: case MK_PRIOR_ADD: case MK_MODULE: return 256;
+        case MK_PROPOSE_STREAM: case MK_LOGP_MFMA: case MK_LOGP_TILED: case MK_LOGP_GEMM: case MK_LOGP_MIX: case MK_PRIOR_ONLY: case MK_PRIOR_ADD: case MK_PRIOR_EXT: case MK_MODULE: return 256;
         default: return 1024;      // (k_accept, k_accept_propose: a wave per try -- fused only up to 16 tries)
     }
 }
@@ -74,6 +75,7 @@ struct LogpPlan {
     MultiLaunch finish, prior, sum;            // k_q_finish; k_prior_only / k_prior_add; k_sum_items
     int nrtb; size_t qpart_doubles;            // tiled families: row tiles of d, doubles of the row-tile sums
     unsigned per_block; long long items; bool grid_overflow; size_t scratch_doubles;      // module: points (items) per block, the item count, more items than one grid holds, the items' scratch
+    bool prior_ext, ext_fix_like; MultiLaunch ext;      // k_prior_ext, last of the call, in the place of k_prior_only / k_prior_add; ... which also maps the likelihood column's nan, as k_prior_add would have
 };
 constexpr int TILED_PT = 2, TILED_RTC = 4;      // k_logp_mvn_mfma_tiled: point tiles x row tiles per wave
 
@@ -148,6 +150,12 @@ inline LogpPlan logp_plan(const MultiShape& s, int n, bool defer_finish)
         P.family = LOGP_HOST;
         P.prior_add = true;
     }
+    if (s.prior_ext && P.family != LOGP_NONE) {
+        // extended priors: the family's kernels have written prior = 0 (have_prior is false; a host callback: its own prior column); one launch adds every
+        // dimension's prior where k_prior_only / k_prior_add would have run -- for the MVN kernels, k_logp_mix, the host callback, a module kernel (after k_sum_items)
+        P.prior_ext = true; P.ext_fix_like = P.prior_add; P.ext = P.prior;
+        P.prior_only = false; P.prior_add = false; P.one_kernel = false;
+    }
     return P;
 }
 
@@ -221,7 +229,7 @@ inline GenerationPlan generation_plan(const MultiShape& s, const MultiStep& t, c
     // (round 5: also the per-chain proposal kernels of 128 < d <= 256 -- the reference example's own d = 200 --: two launches of six fewer)
     const bool tiled_mvn = s.lk == MULTI_LK_MVN && s.ld / 16 > 8;
     const bool chain_sums = P.full && k >= 3 && !P.redo && s.nch < 4 && s.nlanes == 1;
-    P.qdefer = s.q_defer && tiled_mvn && (P.streamed || chain_sums);
+    P.qdefer = s.q_defer && tiled_mvn && (P.streamed || chain_sums) && !s.prior_ext;      // (the kernels that finish deferred sums write a zero prior beside them)
     P.prop0 = (P.streamed && P.have_prop) ? PROP_NONE : (P.streamed && !P.fused_in) ? PROP_STREAM : P.fused_in ? PROP_FUSED_ACCEPT : PROP_CHAIN;
     P.acc = P.fuse_next ? ACC_ACCEPT_PROPOSE : P.defer ? ACC_NONE : ACC_ACCEPT;
     for (int g = 0; g < P.L; ++g) {

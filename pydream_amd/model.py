@@ -98,6 +98,17 @@ class Model():
             parts.append(d)
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
+    def device_prior_ext(self):
+        """Concatenated (kind, a, b, s1, s2) for dz_set_prior_ext if EVERY parameter has an extended device prior, else None."""
+        parts = []
+        for param in self.sampled_parameters:
+            f = getattr(param, "device_prior_ext", None)
+            d = f() if f is not None else None
+            if d is None:
+                return None
+            parts.append(d)
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(5))
+
     def batch_logp(self, X, with_prior):
         """(prior[n], like[n]) for the rows of X; the prior column is zero when the device evaluates it."""
         n = len(X)

@@ -3,9 +3,16 @@
 
 Additionally each parameter can describe itself to the device (``device_prior``) so that
 ``scipy.stats.norm`` / ``scipy.stats.uniform`` / flat priors are evaluated inside the HIP kernels
-(``dz_set_prior``); any other distribution is evaluated on the host through ``.prior``.
+(``dz_set_prior``).  ``device_prior_ext`` does the same for eleven more families -- laplace, cauchy, t, lognorm,
+gamma (and expon), beta, halfnorm, halfcauchy, truncnorm, loguniform / reciprocal, invgamma -- which a kernel of the
+multi-kernel path adds beside a device likelihood (``dz_set_prior_ext``; the arithmetic: csrc/dz_prior_ext.h).
+Any other distribution, and every prior beside a Python-callable likelihood, is evaluated on the host through ``.prior``.
 """
 import numpy as np
+
+# scipy's name -> (kind of dz_set_prior_ext, number of shape parameters)
+_EXT_KINDS = {"norm": (1, 0), "uniform": (2, 0), "laplace": (3, 0), "cauchy": (4, 0), "t": (5, 1), "lognorm": (6, 1), "gamma": (7, 1), "expon": (7, 0),
+              "beta": (8, 2), "halfnorm": (9, 0), "halfcauchy": (10, 0), "truncnorm": (11, 2), "loguniform": (12, 2), "reciprocal": (12, 2), "invgamma": (13, 1)}
 
 
 class SampledParam():
@@ -50,6 +57,24 @@ class SampledParam():
         kind = np.full(self.dsize, 1 if name == "norm" else 2, dtype=np.int32)
         return kind, loc, scale
 
+    def device_prior_ext(self):
+        """(kind[d], a[d], b[d], s1[d], s2[d]) for dz_set_prior_ext -- scipy's loc, scale and shapes broadcast over the parameter's
+        dimensions --, or None if this distribution has no device form or its arguments cannot be parsed."""
+        name = getattr(getattr(self.dist, "dist", None), "name", None)
+        if name not in _EXT_KINDS:
+            return None
+        kind, nshapes = _EXT_KINDS[name]
+        try:
+            shapes, loc, scale = self.dist.dist._parse_args(*self.dist.args, **self.dist.kwds)
+            if len(shapes) != nshapes:
+                return None
+            cols = [np.broadcast_to(np.asarray(v, dtype=float), (self.dsize,)).copy() for v in (loc, scale) + tuple(shapes)]
+        except Exception:
+            return None
+        while len(cols) < 4:
+            cols.append(np.ones(self.dsize) if name == "expon" and len(cols) == 2 else np.zeros(self.dsize))      # (expon: gamma with k = 1)
+        return (np.full(self.dsize, kind, dtype=np.int32),) + tuple(cols)
+
 
 class FlatParam(SampledParam):
     """An improper flat prior: log density 0 everywhere, unbounded support (interface of
@@ -67,3 +92,6 @@ class FlatParam(SampledParam):
 
     def device_prior(self):
         return np.zeros(self.dsize, dtype=np.int32), np.zeros(self.dsize), np.ones(self.dsize)
+
+    def device_prior_ext(self):
+        return np.zeros(self.dsize, dtype=np.int32), np.zeros(self.dsize), np.ones(self.dsize), np.zeros(self.dsize), np.zeros(self.dsize)
