@@ -87,6 +87,8 @@ class _Network:
         self.settle = like._settles()          # the last output time is +inf (csrc/dz_ode.h, STEADY OUTPUT)
         self.inputs = [(u.species, u.gain) for u in like.inputs or ()]      # (species, gain): the tables are the data block's
         self.view = like._view_size() if like._has_view() else 0            # P of a network whose conditions view the point (csrc/dz_ode.h, VIEWS)
+        self.normalize = like.normalize        # None, or O entries None | Normalize (csrc/dz_ode.h, NORMALISED READOUTS)
+        self.knots = like._max_input_knots() if self.normalize else 0       # Kmax: the norm records sit behind the knots' records
         self.R = len(self.reactions)
         self.N = np.zeros((self.S, self.R), dtype=np.int64)
         for r, (reac, prod, _) in enumerate(self.reactions):
@@ -243,6 +245,8 @@ def _noise_members(net):
           "    DZO_HD static bool noise_terms(const double* nz, const double* o, const double* dat, const double* sd, double& acc)", "    {",
           "        bool good = true;"]
     for q, z in enumerate(net.noise):
+        if net.normalize and net.normalize[q] is not None:      # (csrc/dz_ode.h, NORMALISED READOUTS: its terms come behind the last row)
+            continue
         if z is None:                       # (the two statements this observable always ran)
             L.append("        { const double r = (o[%d] - dat[%d]) / sd[%d]; acc = acc - 0.5 * r * r; }" % (q, q, q))
             continue
@@ -258,6 +262,67 @@ def _noise_members(net):
               "            good = good && (!seen || (dzode::finite(m) && %sdzode::finite(s) && s > 0.0));" % ("m > 0.0 && " if log else ""),
               "        }"]
     return L + ["        return good;", "    }"]
+
+
+_NORM_KINDS = {"max": 1, "ref": 2, "minmax": 3}      # the record's first double
+_NORM_RECORD = 7                                      # kind, reference row, D, E, W, n_q, L_q
+
+
+def _normalize_members(net):
+    """The members of a generated network with normalised readouts (csrc/dz_ode.h's head, NORMALISED READOUTS), for the three emitters
+    alike, with q a constant.  Normalised observable number i (ascending q) reads record i of the block, rec[7 i ..], and owns the
+    accumulators na[b ..]: "max" and "ref" the sums A, B and the value g; "minmax" the sums A, B, C and the values hi, lo."""
+    entries = [(q, z) for q, z in enumerate(net.normalize) if z is not None]
+    base, b = [], 0
+    for _, z in entries:
+        base.append(b)
+        b += 5 if z.kind == "minmax" else 3
+    L = ["    static constexpr int NORMALIZE = %d, NORM_KNOTS = %d, NORM_ACC = %d;" % (len(entries), net.knots, b),
+         "    DZO_HD static bool normalized(int q) { return %s; }" % " || ".join("q == %d" % q for q, _ in entries),
+         "    DZO_HD static void norm_init(double* na)", "    {"]
+    for (q, z), b in zip(entries, base):
+        L += ["        na[%d] = 0.0;" % (b + m) for m in range(3 if z.kind == "minmax" else 2)]
+        if z.kind == "minmax":
+            L += ["        na[%d] = -__builtin_huge_val();" % (b + 3), "        na[%d] = __builtin_huge_val();" % (b + 4)]
+        else:
+            L.append("        na[%d] = %s;" % (b + 2, "-__builtin_huge_val()" if z.kind == "max" else "0.0"))
+    L += ["    }", "    DZO_HD static void norm_accumulate(const double* rec, int j, const double* o, const double* dat, const double* sd, double* na)", "    {"]
+    for i, ((q, z), b) in enumerate(zip(entries, base)):
+        L += ["        {", "            const double m = o[%d], iw = 1.0 / sd[%d];" % (q, q),
+              "            const double p = m * iw, e = dat[%d] * iw;" % q,
+              "            na[%d] = na[%d] + p * p;" % (b, b), "            na[%d] = na[%d] + p * e;" % (b + 1, b + 1)]
+        if z.kind == "max":
+            L.append("            na[%d] = m > na[%d] ? m : na[%d];" % (b + 2, b + 2, b + 2))
+        elif z.kind == "ref":
+            L.append("            na[%d] = j == (int)rec[%d] ? m : na[%d];" % (b + 2, _NORM_RECORD * i + 1, b + 2))
+        else:
+            L += ["            na[%d] = na[%d] + p * iw;" % (b + 2, b + 2), "            na[%d] = m > na[%d] ? m : na[%d];" % (b + 3, b + 3, b + 3),
+                  "            na[%d] = m < na[%d] ? m : na[%d];" % (b + 4, b + 4, b + 4)]
+        L.append("        }")
+    L += ["    }", "    DZO_HD static bool norm_finish(const double* rec, const double* nz, const double* na, double& acc)", "    {", "        bool good = true;"]
+    for i, ((q, z), b) in enumerate(zip(entries, base)):
+        r = _NORM_RECORD * i
+        L.append("        {")
+        if z.kind == "minmax":
+            L += ["            const double lo = na[%d], g = na[%d] - lo;" % (b + 4, b + 3),
+                  "            const double A = na[%d] - 2.0 * (lo * na[%d]) + (lo * lo) * rec[%d];" % (b, b + 2, r + 4),
+                  "            const double B = na[%d] - lo * rec[%d];" % (b + 1, r + 3)]
+        else:
+            L.append("            const double g = na[%d], A = na[%d], B = na[%d];" % (b + 2, b, b + 1))
+        L += ["            const double z = 1.0 / g;", "            const double Q = (A * z) * z - 2.0 * (B * z) + rec[%d];" % (r + 2)]
+        if net.noise and net.noise[q] is not None:
+            L += ["            const double a = nz[%d];" % (2 * q), "            acc = acc - (0.5 * Q) / (a * a);",
+                  "            acc = acc - rec[%d] * dzode::dlog(a);" % (r + 5), "            acc = acc - rec[%d];" % (r + 6)]
+        else:
+            L.append("            acc = acc - 0.5 * Q;")
+        L += ["            good = good && dzode::finite(g) && g > 0.0;", "        }"]
+    L += ["        return good;", "    }", "    DZO_HD static void norm_apply(const double* na, double* row)", "    {"]
+    for (q, z), b in zip(entries, base):
+        if z.kind == "minmax":
+            L.append("        row[%d] = (row[%d] - na[%d]) / (na[%d] - na[%d]);" % (q, q, b + 4, b + 3, b + 4))
+        else:
+            L.append("        row[%d] = row[%d] / na[%d];" % (q, q, b + 2))
+    return L + ["    }"]
 
 
 def _product(factors):
@@ -291,7 +356,8 @@ def _net_source(net, body):
     """The scaffolding every generated source shares: the include, the struct's head, the generator's own members (body, up to the
     closing brace of the last one), the members of a network with inputs (net.drive: where the emitter put their drives), of one with monomials, the observables and the entry macro.  net.events: the
     largest event count over the object's experiments; the member EVENTS only if there is one (csrc/dz_ode.h).  net.equilibrate: some
-    experiment equilibrates first; the member EQUILIBRATE only then.  net.settle: the object's t ends in inf; the member SETTLE only then."""
+    experiment equilibrates first; the member EQUILIBRATE only then.  net.settle: the object's t ends in inf; the member SETTLE only then.
+    net.normalize: some observable is normalised to its own time course; NORMALIZE, norm_accumulate and norm_finish only then."""
     if net.lanes == 1:
         header, entries = "dz_ode.h", "DZODE_ITEM_ENTRIES(Net)" if net.items else "DZODE_ENTRIES(Net)"
     else:
@@ -303,6 +369,7 @@ def _net_source(net, body):
     L += ["    static constexpr int VIEW = %d;" % net.view] if net.view else []
     L += _input_members(net, net.drive) if net.inputs else []
     L += body + (_monomial_members(net.mono) if net.mono else []) + (_noise_members(net) if net.noise else [])
+    L += _normalize_members(net) if net.normalize else []
     L += ["    DZO_HD static void obs(const double* y, double* o)", "    {"] + _obs_lines(net.S, net.observables) + ["    }", "};", entries, ""]
     return '#include "%s"\n' % header + "\n".join(L)
 

@@ -1,5 +1,5 @@
 """The limits of pydream_amd.likelihoods.MassActionODELogLike, the predicates its checks are made of, and the immutable values a network
-is written with: Monomial, Hill, RateLaw, Noise, Input."""
+is written with: Monomial, Hill, RateLaw, Noise, Input, Normalize."""
 import numpy as np
 
 ODE_LIMITS = dict(species=8, reactions=64, observables=8, times=4096)
@@ -307,3 +307,45 @@ class Input:
 
     def __repr__(self):
         return "Input(%r, %r, %r, %r)" % (self.species, list(self.times), list(self.values), self.gain)
+
+
+class Normalize:
+    """A readout known only relative to its own time course, for MassActionODELogLike(normalize=[...]): with m_j the observable after
+    `scale` at output row j of one experiment, the likelihood compares m'_j with the data.  kind "max": m' = m / max_j m (a fraction of
+    the trajectory's own maximum); "ref" with t= one of the object's output times (np.inf: the steady row): m' = m / m(t) (fold change
+    over a chosen point); "minmax": m' = (m - min_j m) / (max_j m - min_j m).  The extrema run over every output row, observed or not.
+    t is given exactly for "ref" and not otherwise.  An immutable value."""
+    __slots__ = ("kind", "t")
+
+    def __init__(self, kind, t=None):
+        if kind not in ("max", "ref", "minmax"):
+            raise ValueError('MassActionODELogLike: a Normalize\'s kind must be "max", "ref" or "minmax" (got %r)' % (kind,))
+        if kind == "ref":
+            if isinstance(t, bool) or not isinstance(t, _REAL) or np.isnan(t) or t == -np.inf:
+                raise ValueError('MassActionODELogLike: a Normalize of kind "ref" needs t=, one of the output times (np.inf: the steady row; got %r)' % (t,))
+            t = float(t)
+        elif t is not None:
+            raise ValueError('MassActionODELogLike: a Normalize of kind %r takes no t (got %r): only "ref" names a row' % (kind, t))
+        object.__setattr__(self, "kind", kind)
+        object.__setattr__(self, "t", t)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Normalize is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("a Normalize is immutable")
+
+    def _key(self):
+        return (self.kind, self.t)
+
+    def __eq__(self, other):
+        return isinstance(other, Normalize) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __reduce__(self):
+        return Normalize, (self.kind, self.t)
+
+    def __repr__(self):
+        return "Normalize(%r, %r)" % (self.kind, self.t)

@@ -250,6 +250,54 @@
 // Not supported: more than one steady row, a steady state between two finite outputs, Newton polishing of the state (conservation laws
 // make the Jacobian singular).
 //
+// NORMALISED READOUTS (likelihoods.Normalize, MassActionODELogLike(normalize=...)): a readout without an absolute unit -- a blot as a
+// fraction of its own maximum, fold change over a chosen point, a trace rescaled to [0, 1].  With m_j the observable after `scale` at
+// output row j of one experiment, the data is compared with m'_j = m_j / g ("max": g = max_j m_j; "ref": g = m at the reference row) or
+// m'_j = (m_j - lo) / (hi - lo) ("minmax").  g is known only behind the last row, so the rows feed running sums and the term is formed
+// once, at the end: for Gaussian residuals the normalised sum of squares is a quadratic form in 1 / g.  A network with at least one
+// normalised observable carries
+//     static constexpr int NORMALIZE = n;                              the normalised observables, 1..O; number i is the i-th in ascending q
+//     static constexpr int NORM_KNOTS = Kmax;                          the knot records of every experiment's block (0 without inputs)
+//     static constexpr int NORM_ACC;                                   the doubles beside acc: 2 sums + 1 value per "max" and "ref",
+//                                                                      3 sums + 2 values per "minmax" -- only what a kind needs exists
+//     static bool normalized(int q);                                   observable q is normalised (a select over constants)
+//     static void norm_init(double* na);
+//     static void norm_accumulate(const double* rec, int j, const double* o, const double* dat, const double* sd, double* na);
+//     static bool norm_finish(const double* rec, const double* nz, const double* na, double& acc);      false: a failed integration
+//     static void norm_apply(const double* na, double* row);           one row of sim: m' in m's place
+// straight-line code with q a constant, and each experiment's block (each sub-block, with conditions) grows by one RECORD of seven doubles
+// per normalised observable, in ascending q,
+//     kind (1 "max", 2 "ref", 3 "minmax"),   the reference row (0 unless "ref"),   D,   E,   W,   n_q,   L_q
+// which sit BEHIND the input knots (their count and Kmax records; without inputs behind SETTLE's six doubles or whatever is last) and IN
+// FRONT OF a view's pairs, which stay at the block's very end because viewed_row finds them there:
+//     header, y0, t, data, sd | E_c, events | equilibration's six | SETTLE's six | K_c, knots | norm records | view pairs
+// The block, the source and the code object of a network without the member are what they always were.  The contract, the same in both
+// builds and every shape:
+//   * INTEGRATION UNTOUCHED: steps, states and the un-normalised m have the bits of the object without `normalize`.  An observable
+//     without a Normalize adds its row terms exactly as before (the fixed-sd statements, or its part of noise_terms); noise_terms holds
+//     nothing for a normalised observable.
+//   * EXTREMA AND REFERENCE, at every row in ascending j, observed or not:  hi = m > hi ? m : hi  from -inf;  lo = m < lo ? m : lo  from
+//     +inf;  g_ref = m at the reference row ("max": g = hi).
+//   * RUNNING SUMS, at every row:  iw = 1.0 / sd  (an unobserved entry has sd = +inf and data 0, so it adds exactly 0),  p = m * iw,
+//     e = d * iw;   A = A + p * p;   B = B + p * e;   and for "minmax"  C = C + p * iw.
+//   * HOST-SIDE SUMS: D = sum e * e, E = sum e * iw and W = sum iw * iw are computed in Python over the rows from left to right and come
+//     from the record, with n_q, the observed count, and L_q = sum ln sd over the observed entries (for an observable with a Noise sd
+//     is the weight w).
+//   * THE FINISH, behind the last row and so behind all row terms, in ascending q:
+//         "max", "ref":   z = 1.0 / g;   Q = (A * z) * z - 2.0 * (B * z) + D
+//         "minmax":       g = hi - lo;   A' = A - 2.0 * (lo * C) + (lo * lo) * W;   B' = B - lo * E;   z = 1.0 / g;   Q likewise from A', B'
+//         without a Noise:   acc = acc - 0.5 * Q                       (the block's constant keeps -log sd - log(2 pi) / 2 per observed entry)
+//         with Noise(sigma): acc = acc - (0.5 * Q) / (a * a);   acc = acc - n_q * dlog(a);   acc = acc - L_q        (a = a_q, the spread is a w)
+//     Nothing is clamped.
+//   * FAILURE: a g that is not finite or not > 0 is a failed integration: -inf, and NaN in the item's sim slice.  A trajectory that is
+//     identically zero has no normalised form.
+//   * SIM: with sim given, a pass behind the finish rewrites the slice's normalised columns row by row: m / g, or (m - lo) / (hi - lo).
+//     In a lane group o is replicated over the lanes, every lane carries the same sums, and lane 0, which alone holds sim, reads back
+//     what it wrote.
+//   * VIEWS AND CONDITIONS: every item normalises on its own; item c's term has the bits of the object of condition c alone.
+// Only Noise(sigma) -- normal, "lin", no rel -- may stand on a normalised observable: Python refuses the others, whose residuals are no
+// quadratic form.  Not supported: a normaliser shared between conditions, a scale fitted to the data.
+//
 // The stepping loop (dzode::integrate), the controller's formulas, integrate_fixed and the host build's C functions exist once, here, for
 // this one-lane solver, for dz_ode_group.h's lane-group solver and for that solver's host twin: see "the one stepping loop" below.
 #pragma once
@@ -409,6 +457,17 @@ template <class Net> struct has_view<Net, decltype((void)Net::VIEW)> {
 };
 // the doubles of an item's viewed row (an array of at least one)
 template <class Net> constexpr int view_doubles() { return has_view<Net>::count > 0 ? has_view<Net>::count : 1; }
+
+// ... and normalised readouts (the head of the file, NORMALISED READOUTS): NORMALIZE records of seven doubles in every experiment's
+// block, NORM_ACC running sums and values beside acc
+template <class Net, class = void> struct has_normalize { static constexpr bool value = false; static constexpr int count = 0; };
+template <class Net> struct has_normalize<Net, decltype((void)Net::NORMALIZE)> {
+    static constexpr bool value = true;
+    static constexpr int count = Net::NORM_ACC;
+    static_assert(Net::NORMALIZE >= 1 && Net::NORMALIZE <= Net::O && Net::NORM_KNOTS >= 0 && Net::NORM_KNOTS <= 128, "1..O normalised observables");
+};
+// the doubles of an experiment's running sums and values (an array of at least one)
+template <class Net> constexpr int norm_doubles() { return has_normalize<Net>::count > 0 ? has_normalize<Net>::count : 1; }
 
 // Entry i of a condition's view: a select between x[j_i] and v_i, no arithmetic; x is not read where j_i < 0.
 DZO_HD double view_entry(const double* x, const double* tab, int i)
@@ -740,6 +799,14 @@ DZO_HD double next_knot(const double* blk, int kn)
     return kn < (int)dmin(inp[0], (double)MAX_INPUT_KNOTS) ? inp[1 + 4 * kn] : __builtin_huge_val();
 }
 
+// The records of an experiment's normalised observables (the head of the file, NORMALISED READOUTS): behind the knots' count and Kmax
+// records of a network with inputs -- Kmax is the network's NORM_KNOTS --, else where those would begin.  Formed where it is used.
+template <class Shape>
+DZO_HD const double* norm_records(const double* blk)
+{
+    return input_knots<Shape>(blk) + (Shape::INPUTS > 0 ? 1 + 4 * Shape::Net::NORM_KNOTS : 0);
+}
+
 // (AT_END: the same loop on the steady output's record, which sits behind the equilibration's, from the state at t_last -- the head of
 // the file, STEADY OUTPUT; dzode::settle below.  One loop in the source, an instantiation per phase.)
 template <class Shape, bool AT_END = false>
@@ -812,6 +879,9 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
     double t = t0, acc = 0.0;
     constexpr int EV = Shape::EVENTS, IN = Shape::INPUTS;
     constexpr bool SEG = EV > 0 || IN > 0;                                   // the loop's passes are segments between breakpoints
+    constexpr bool NORM = has_normalize<typename Shape::Net>::value;          // some observable is normalised to its own time course
+    [[maybe_unused]] double na[norm_doubles<typename Shape::Net>()];         // its running sums and values
+    if constexpr (NORM) Shape::Net::norm_init(na);
     double h = 0.0;
     bool ok = live, rejected = false;
     int nsteps = 0;
@@ -897,12 +967,23 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             if (tend < tout) continue;                                       // landed on an event or a knot, not on the output time
         }
         sh.observe(y, o);
+        if constexpr (NORM)                                                  // (the head of the file, NORMALISED READOUTS: extrema and sums, every row)
+            Shape::Net::norm_accumulate(norm_records<Shape>(blk), j, o, dat + (long long)j * O, sd + (long long)j * O, na);
         if constexpr (has_noise<typename Shape::Net>::value) {               // (the head of the file, NOISE: the network's own terms)
             const bool fine = Shape::Net::noise_terms(sh.noise(), o, dat + (long long)j * O, sd + (long long)j * O, acc);
 #pragma unroll
             for (int q = 0; q < O; ++q)
                 if (sim) sim[(long long)j * O + q] = o[q];
             if (!fine) { ok = false; break; }
+        } else if constexpr (NORM) {                                         // (the statements below for the observables that are not normalised)
+#pragma unroll
+            for (int q = 0; q < O; ++q) {
+                if (!Shape::Net::normalized(q)) {
+                    const double r = (o[q] - dat[(long long)j * O + q]) / sd[(long long)j * O + q];
+                    acc = acc - 0.5 * r * r;
+                }
+                if (sim) sim[(long long)j * O + q] = o[q];
+            }
         } else {
 #pragma unroll
             for (int q = 0; q < O; ++q) {
@@ -912,6 +993,15 @@ DZO_HD double integrate(const Shape& sh, const double* blk, bool live, double* s
             }
         }
         ++j;
+    }
+    if constexpr (NORM) {                                                    // (the head of the file, NORMALISED READOUTS: the finish, behind all row terms)
+        if (ok) {
+            if constexpr (has_noise<typename Shape::Net>::value) ok = Shape::Net::norm_finish(norm_records<Shape>(blk), sh.noise(), na, acc);
+            else ok = Shape::Net::norm_finish(norm_records<Shape>(blk), nullptr, na, acc);
+        }
+        if (ok && sim) {                                                     // (the lane that wrote the slice reads it back: m' in m's place)
+            for (int j = 0; j < T; ++j) Shape::Net::norm_apply(na, sim + (long long)j * O);
+        }
     }
     if (nsteps_out) *nsteps_out = nsteps;
     return ok ? blk[0] + acc : -__builtin_huge_val();

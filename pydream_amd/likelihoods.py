@@ -12,7 +12,7 @@ from ._ode_source import _LOG_2PI_HALF, _hill_slots, _indices_read, _rate, _rate
 from ._ode_values import (ODE_EQUILIBRATE_MAX_STEPS, ODE_GROUP_LIMITS, ODE_LIMITS, ODE_MAX_CONDITIONS, ODE_MAX_CONSTRAINTS,      # noqa: F401
                           ODE_MAX_EVENTS, ODE_MAX_HILL_EXPONENT, ODE_MAX_INPUT_KNOTS, ODE_MAX_INPUTS, ODE_MAX_RATE_FACTORS, ODE_MAX_VIEW_COORDINATES,
                           ODE_SETTLE_MAX_STEPS, ODE_WAVE_LIMITS,
-                          Hill, Input, Monomial, Noise, RateLaw, _checked_constant, _is_int, _is_real)
+                          Hill, Input, Monomial, Noise, Normalize, RateLaw, _checked_constant, _is_int, _is_real)
 
 
 class MVNormalLogLike:
@@ -467,6 +467,25 @@ class MassActionODELogLike:
     of Nones generate the source and the data block the object always had.  Not supported: Student-t residuals, a per-condition
     noise, a sampled offset on the log scale; fixed_steps has no likelihood and ignores noise.
 
+    Normalised readouts: normalize=[...], None or O entries, each None or a Normalize(kind, t=None), shared by all conditions like
+    `scale` and `noise` -- a western blot, a reporter trace or a FACS time course reported as a fraction of its own maximum, as fold
+    change over a chosen point, or rescaled to [0, 1].  With m_j the observable after `scale` at output row j of one experiment (the
+    single experiment, or one condition on its own): "max": m'_j = m_j / max_j m_j, the maximum over EVERY output row, observed or
+    not (rows with NaN data sample the peak more densely); "ref" with t= one of the object's output times (np.inf: the steady row):
+    m'_j = m_j / m(t); "minmax": m'_j = (m_j - lo) / (hi - lo) over every row.  The residual is (m' - d) / sd with `data` on the
+    normalised scale; simulate, device().simulate and posterior_predictive return m'.  An observable without a Noise keeps its fixed
+    sd; with Noise(sigma) the spread is sigma times the weight, as always.  The contract (csrc/dz_ode.h's head, NORMALISED READOUTS):
+    the integration and the un-normalised m have the bits of the object without `normalize`; the rows feed running sums
+    (A = sum p p, B = sum p e, p = m / sd, e = d / sd) and the term is formed once behind the last row as a quadratic form in 1 / g;
+    a g that is not finite or not > 0 -- a trajectory that is identically zero -- is a failed integration (-inf, NaN in simulate);
+    every experiment's block grows by seven doubles per normalised observable, behind the input knots and in front of a view's pairs.
+    with_outputs(t) carries the setting over and normalises over the NEW grid: the maximum over a denser grid is a different (larger
+    or equal) number, so dense curves of a "max" or "minmax" readout do not pass exactly through simulate's values; a "ref" whose
+    time is not in the new t is refused.  normalize=None and a list of Nones are the object it always was: source, data block and
+    cache key.  Not supported: Noise with rel, dist="laplace" or scale="log" on a normalised observable (refused: their residuals are
+    no quadratic form, and the likelihood kernel stores no trajectory); a normaliser shared between conditions (the lanes of one gel
+    across doses); a scale fitted to the data.
+
     Condition-specific parameters: a condition's "params" = {i: target} makes the experiments differ in the SYSTEM and not only in what
     is done to it -- a knock-down or a mutant that changes a rate constant, an inhibitor in the treated arms only, a sampled readout
     scale per gel, a noise level per assay, a cell line's own expression level (PEtab's condition table).  i is a parameter index the
@@ -525,10 +544,11 @@ class MassActionODELogLike:
     scale, constraints, y0_monomials = None, (), {}     # (likewise: before Monomial existed)
     noise = None            # (likewise: before Noise existed)
     inputs = None           # (likewise: before Input existed)
+    normalize = None        # (likewise: before Normalize existed)
 
     def __init__(self, n_species, reactions, y0, t, observables, data, sd, rate_scale="log10", t0=0.0, rtol=1.49012e-8, atol=1.49012e-8,
                  max_steps=500, ndim=None, path=None, lanes_per_point=1, conditions=None, scale=None, constraints=None, events=None,
-                 equilibrate=None, noise=None, inputs=None, settle=None):
+                 equilibrate=None, noise=None, inputs=None, settle=None, normalize=None):
         self.n_species, self.lanes_per_point, lim = self._checked_shape(n_species, lanes_per_point, len(reactions))
         noise = self._checked_noise(noise)      # None, or the entries (None | Noise); their number is tested below, once O is known
         if sd is None and noise is not None and all(z is not None for z in noise):
@@ -544,6 +564,7 @@ class MassActionODELogLike:
         if noise is not None and len(noise) != len(self.observables):
             raise ValueError("MassActionODELogLike: noise must be None or hold O = %d entries, each None or a Noise (got %d)" % (len(self.observables), len(noise)))
         self.noise = noise if noise is not None and any(z is not None for z in noise) else None
+        self.normalize = self._checked_normalize(normalize)     # None, or O entries None | Normalize with at least one Normalize
         self.data, self.sd = self._checked_data(data, sd, "") if data is not None and sd is not None else (data, sd)
         events = self._checked_events(events, "")
         if not (rtol > 0 and atol > 0 and np.isfinite(rtol) and np.isfinite(atol)) or int(max_steps) < 1:
@@ -707,6 +728,51 @@ class MassActionODELogLike:
         if isinstance(noise, Noise) or not all(z is None or isinstance(z, Noise) for z in entries):
             raise ValueError("MassActionODELogLike: noise must be None or a sequence of O entries, each None or a Noise (got %r)" % (noise,))
         return entries
+
+    def _checked_normalize(self, normalize, t=None):
+        """None, or the normalisations as a list of None | Normalize, at least one of them a Normalize (csrc/dz_ode.h, NORMALISED
+        READOUTS); t: the output times a "ref" must name (default: the object's)."""
+        if normalize is None:
+            return None
+        try:
+            entries = list(normalize)
+        except TypeError:
+            entries = [normalize]
+        O, t = len(self.observables), self.t if t is None else t
+        if isinstance(normalize, Normalize) or len(entries) != O or not all(z is None or isinstance(z, Normalize) for z in entries):
+            raise ValueError("MassActionODELogLike: normalize must be None or hold O = %d entries, each None or a Normalize (got %r)" % (O, normalize))
+        for q, z in enumerate(entries):
+            if z is None:
+                continue
+            if z.kind == "ref" and not np.any(t == z.t):
+                raise ValueError('MassActionODELogLike: normalize[%d]: the reference time %r is not one of the output times %r' % (q, z.t, t.tolist()))
+            nz = self.noise[q] if self.noise is not None else None
+            if nz is not None and (nz.rel is not None or nz.dist != "normal" or nz.scale != "lin"):
+                raise ValueError('MassActionODELogLike: observable %d is normalised, so its Noise must be Noise(sigma): normal residuals on the "lin" '
+                                 'scale without rel (got %r).  Other residuals are no quadratic form in 1 / g, and the likelihood kernel stores '
+                                 'no trajectory' % (q, nz))
+        return entries if any(z is not None for z in entries) else None
+
+    def _norm_records(self, data, sd):
+        """One experiment's records of its normalised observables (csrc/dz_ode.h, NORMALISED READOUTS), seven doubles each in ascending
+        q: kind (1 "max", 2 "ref", 3 "minmax"), the reference row (0 unless "ref"), D = sum e e, E = sum e iw, W = sum iw iw with
+        iw = 1 / sd and e = d iw over the rows from left to right (an unobserved entry: d = 0, sd = inf, so exactly 0), the observed
+        count n_q and L_q = sum ln sd over the observed entries.  data, sd: O x T."""
+        seen = np.isfinite(data)
+        rec = []
+        for q, z in enumerate(self.normalize):
+            if z is None:
+                continue
+            D = E = W = L = 0.0
+            for j in range(data.shape[1]):
+                iw = 1.0 / float(sd[q, j]) if seen[q, j] else 0.0
+                e = (float(data[q, j]) if seen[q, j] else 0.0) * iw
+                D, E, W = D + e * e, E + e * iw, W + iw * iw
+                if seen[q, j]:
+                    L = L + float(np.log(sd[q, j]))
+            row = float(np.flatnonzero(self.t == z.t)[0]) if z.kind == "ref" else 0.0
+            rec += [float(_ode_source._NORM_KINDS[z.kind]), row, D, E, W, float(np.sum(seen[q])), L]
+        return rec
 
     def _indices(self):
         """The parameter indices the network reads -- a rate, a Hill K, a Monomial, a Noise or a gain --, ascending."""
@@ -1000,6 +1066,7 @@ class MassActionODELogLike:
 
     def _experiment_block(self, y0, data, sd, events=(), equilibrate=None, inputs=(), params=None, settle=None):
         seen = np.isfinite(data)
+        norm = self._norm_records(data, sd) if self.normalize else None
         if self.noise is None:
             C = float(np.sum(-np.log(sd[seen]) - _LOG_2PI_HALF))
         else:                                   # (csrc/dz_ode.h, NOISE: an entry's constant by its observable's model; "log": ln d in the data slot)
@@ -1032,6 +1099,8 @@ class MassActionODELogLike:
             rec = np.zeros((self._max_input_knots(), 4))
             rec[:len(knots)] = np.asarray(knots, dtype=float).reshape(-1, 4)
             blk += [[float(len(knots))], rec.reshape(-1)]
+        if norm:                                # (csrc/dz_ode.h, NORMALISED READOUTS: behind the knots, in front of the view's pairs)
+            blk += [norm]
         if params is not None:                  # (csrc/dz_ode.h, VIEWS: the P pairs (j_i, v_i) at the very end)
             blk += [self._view_table(params)]
         return np.concatenate(blk)
@@ -1102,13 +1171,16 @@ class MassActionODELogLike:
 
     def with_outputs(self, t, t0=None):
         """A sibling object with the output times t (and start time t0, default: this object's) and every data entry NaN: the same
-        network, conditions, y0, events, equilibration, scale and noise (the class docstring, Prediction)."""
+        network, conditions, y0, events, equilibration, scale and noise (the class docstring, Prediction).  `normalize` carries over
+        too: it is checked again against the new times -- a "ref" whose time is not among them is refused -- and the extrema and the
+        reference are taken over the new grid, so the maximum over a denser grid is a different number."""
         import copy
         new = copy.copy(self)
         lim = self._checked_shape(self.n_species, self.lanes_per_point, len(self.reactions))[2]
         new.t, new.t0, _ = self._checked_times(t, self.t0 if t0 is None else t0, self.observables, self.n_species, lim)
         shape = (len(self.observables), len(new.t))
         new.data, new.sd = np.full(shape, np.nan), np.ones(shape)
+        new.normalize = new._checked_normalize(self.normalize, new.t)    # (a "ref" must name one of the new times; extrema run over the new grid)
         resettle = lambda st, who: (st or new._checked_settle(None, who)) if new._settles() else None      # noqa: E731  (the phase's settings carry over)
         new.settle = resettle(self.settle, "")
         new.events = new._checked_events(self.events, "") or None

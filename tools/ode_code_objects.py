@@ -66,6 +66,24 @@ def objects():
     for lanes in (1, 16, 32, 64):
         out["view.readers@%d" % lanes] = lambda lanes=lanes: VN.readers(lanes)[0]
         out["view.readers@%d.twin" % lanes] = lambda lanes=lanes: VN.readers(lanes, view=False)[0]
+    import tests
+    if not os.path.exists(os.path.join(os.path.dirname(tests.__file__), "ode_normalize_networks.py")):
+        return out                          # (a checkout from before `normalize`: the list ends here)
+    from tests import ode_normalize_networks as NN
+    # the networks with normalised readouts, each beside its twin without the keyword: one lane (4 species; 8 species, the shape with
+    # the most registers; items), 16, 32 and 64 lanes
+    from tests import ode_networks as NW
+    for kind in NN.KINDS:
+        out["normalize.mm.%s" % kind] = lambda kind=kind: NN.mm(NN.mm_normalize(kind))
+    out["normalize.mm.twin"] = lambda: NN.mm_twin(None)
+    out["normalize.mm.minmax+noise"] = lambda: NN.mm(NN.mm_normalize("minmax"), noisy=True)
+    out["normalize.mm_conditions"] = lambda: NN.mm_conditions(NN.mm_normalize("max"))[0]
+    out["normalize.mm_conditions.twin"] = lambda: NN.mm_conditions(None)[0]
+    out["normalize.chain8"] = lambda: NW.chain8(normalize=NN.group_normalize(8, NW.CHAIN_T))
+    out["normalize.chain8.twin"] = lambda: NW.chain8()
+    for name in ("enzyme13", "chain17", wave):
+        out["normalize.%s" % name] = lambda name=name: NN.group(name)[0]
+        out["normalize.%s.twin" % name] = lambda name=name: EQ.single(name, equilibrate=False)
     return out
 
 

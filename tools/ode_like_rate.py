@@ -12,6 +12,7 @@
     python tools/ode_like_rate.py [chains] [tries] [generations] [--kernel-only] [--network robertson|mm|chain8|enzyme13|chain32|chain64|cascade|binding_cycle|<example>]
                                   [--lanes 1|16|32|64] [--conditions C [--events E | --equilibrate]] [--host-twin] [--noise] [--input] [--view]
                                   [--settle [--t-big T | --search-only] [--before CODE_OBJECT]]
+                                  [--normalize max|ref|minmax [--before CODE_OBJECT]]
 
 --conditions C: the network under C experimental conditions (MassActionODELogLike(conditions=...): the start amounts scaled by 0.5 .. 2,
 geometrically) -- ONE launch over points x C items plus the engine's sum against the same C conditions as C single-condition launches
@@ -61,6 +62,15 @@ points first rest at each power of ten; --t-big T skips the search and takes T, 
 Kernel only.  The same run times the network WITHOUT the phase (t = [.., t_last]) in the same rounds, and with --before CODE_OBJECT also the
 code object that another checkout -- the commit before the phase existed -- built for that network (MassActionODELogLike(path=...)):
 networks without the phase generate the source they always did, so the two should take the same time within the rounds' spread.
+
+--normalize KIND: what normalising the readouts to their own time course costs (MassActionODELogLike(normalize=...), csrc/dz_ode.h,
+NORMALISED READOUTS) -- --network mm | enzyme13 | chain17 | chain33 (tests/ode_networks.py and tests/ode_equilibrate_networks.py; 1, 16, 32
+and 64 lanes per point) with EVERY observable normalised by KIND ("ref": at the last output time) against the same network, data and
+points without the keyword; alternately, the median of 7 rounds of 10 calls each and the rounds' spread; proposals/s for both, their
+registers, scratch and LDS from the code objects' notes, and the values compared with the host build's bit for bit.  With --before
+CODE_OBJECT also the code object that another checkout -- the commit before the keyword existed -- built for the plain network
+(MassActionODELogLike(path=...)): a network without the keyword generates the source it always did, so the two should take the same
+time within the rounds' spread.  The expected cost of normalising is a few registers and one divide per observable per point.  Kernel only.
 
 --host-twin: the likelihood kernel against the host build of the same solver on the same points, for networks whose host pass is too
 long to repeat (chain64, cascade: 0.02 .. 0.04 s per point) -- the device by the protocol above, the median of 7 rounds of 10 eval_logp
@@ -426,6 +436,50 @@ def settle_rate(N, k, name, t_big=None, rounds=7, reps=10, search_only=False, be
     return out
 
 
+def normalize_rate(N, k, name, kind, rounds=7, reps=10, before=None):
+    """Every observable normalised by `kind` against the same network without the keyword: see the head"""
+    import multiprocessing
+    from pydream_amd.likelihoods import MassActionODELogLike, Normalize
+    from tests.ode_support import notes
+    if name == "mm":
+        from tests import ode_networks as NW
+        plain, nominal = NW.michaelis_menten(), NW.MM_NOMINAL
+    else:
+        from tests import ode_equilibrate_networks as EQ
+        plain, nominal = EQ.single(name, equilibrate=False), EQ.network(name)[5]
+    z = Normalize("ref", float(plain.t[-1])) if kind == "ref" else Normalize(kind)
+    make = lambda **kw: MassActionODELogLike(plain.n_species, plain.reactions, plain.y0, plain.t, plain.observables, plain.data, plain.sd,      # noqa: E731
+                                             lanes_per_point=plain.lanes_per_point, **kw)
+    objs = dict(plain=plain, normalized=make(normalize=[z] * len(plain.observables)))
+    if before is not None:
+        objs["plain_before"] = make(path=before)
+    n = N * k
+    X = box_points(nominal, 1.0, n)
+    workers = int(os.environ.get("DREAMZS_HOST_WORKERS", "16"))
+    for obj in objs.values():
+        obj.host_library()
+    with multiprocessing.get_context("fork").Pool(workers) as pool:      # (the workers are forked before this process opens the device)
+        hosts = {key: pool.map(_host_part, [(obj, part) for part in np.array_split(X, workers)]) for key, obj in objs.items()}
+    engines = {key: engine_for(obj, N, k, nominal, 1.0) for key, obj in objs.items()}
+    last, t = timed({key: (lambda eng=eng: eng.eval_logp(X)[1]) for key, eng in engines.items()}, rounds, reps)
+    out = dict(network=name, lanes=plain.lanes_per_point, species=plain.n_species, observables=len(plain.observables), times=len(plain.t), kind=kind,
+               chains=N, tries=k, points=n)
+    for key, lk in last.items():
+        host, steps = np.concatenate([p[0] for p in hosts[key]]), np.concatenate([p[1] for p in hosts[key]])
+        assert lk.tobytes() == host.tobytes(), "device and host builds differ (%s)" % key
+        us = float(np.median(t[key]))
+        out[key] = dict(steps_median=float(np.median(steps)), failed_points=int(np.sum(lk == -np.inf)), us_per_launch=round(us, 1),
+                        us_per_launch_min_max=[round(min(t[key]), 1), round(max(t[key]), 1)], proposals_per_s=round(n / us * 1e6),
+                        code_object=notes(objs[key].code_object()))
+    ratio = lambda a, b: (round(float(np.median(t[a])) / float(np.median(t[b])), 4), [round(min(t[a]) / max(t[b]), 4), round(max(t[a]) / min(t[b]), 4)])      # noqa: E731
+    out["normalized_over_plain"], out["ratio_over_the_rounds_spread"] = ratio("normalized", "plain")
+    if before is not None:
+        assert last["plain"].tobytes() == last["plain_before"].tobytes(), "the two code objects of the plain network differ in their values"
+        out["plain_after_over_before"], out["plain_ratio_over_the_rounds_spread"] = ratio("plain", "plain_before")
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def _host_rows(args):
     like, part = args
     return like.simulate(part)
@@ -520,7 +574,7 @@ def main(N=4096, k=5, G=20, kernel_only=False, name="robertson", lanes=None):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--network", "--lanes", "--conditions", "--events", "--t-big", "--before"):
+    for flag in ("--network", "--lanes", "--conditions", "--events", "--t-big", "--before", "--normalize"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
@@ -536,6 +590,8 @@ if __name__ == "__main__":
         input_rate(*nums, name)
     elif "--view" in argv:
         view_rate(*nums, name)
+    elif "--normalize" in opt:
+        normalize_rate(*nums, name, opt["--normalize"], before=opt.get("--before"))
     elif "--settle" in argv:
         settle_rate(*nums, name, float(opt["--t-big"]) if "--t-big" in opt else None, search_only="--search-only" in argv, before=opt.get("--before"))
     elif "--equilibrate" in argv:
